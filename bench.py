@@ -9,10 +9,15 @@ N GPUs:        python bench.py --gpus N           (starts N rank processes itsel
                python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
                    --master-addr 127.0.0.1 --master-port P bench.py --gpus N
 
+A plain run does only what the headline needs: build the job, W untimed steps,
+K timed steps, the outputs of the last timed step to ``--dump-outputs DIR`` if
+asked, one JSON line.  Everything else below (the bf16 companion, the sub-runs
+of the other BASELINE.json configs) runs only with ``--full``.
+
 Precision: the reference computes in Keras float32 (`src/node.py:177`,
 `test/local_infer.py:22`), so the primary ``value`` is fp32 end to end
-(fp32 activations and weights on the fp32 matrix cores).  The same run also
-times the bf16 build (fp32 accumulation) and reports it as ``value_bf16``.
+(fp32 activations and weights on the fp32 matrix cores).  With ``--full`` the
+same run also times the bf16 build (fp32 accumulation) as ``value_bf16``.
 
 Parallelism (``--mode``) of the headline:
   dp    every GPU runs the whole model on its own bs=32 batch (replicas)
@@ -28,7 +33,7 @@ on a host (gloo) process group; activations move over the native RCCL p2p
 layer (`parallel/rccl.py`), so no eager ProcessGroupNCCL stream competes with
 the pipeline's compute and link streams for the 4 hardware queues.
 
-With N > 1 (dp mode) the same invocation then measures BASELINE.json's other
+With ``--full`` and N > 1 (dp mode) the same invocation then measures BASELINE.json's other
 configs as *sub-runs*: after the headline ranks are done, rank 0 starts each
 one as a fresh job of its own (`parallel/launch.py`, one process per GPU, a
 time limit each, stdout to stderr), so a failing or hanging sub-run is killed
@@ -85,14 +90,20 @@ def parse(argv=None):
     ap.add_argument("--dtype", default="fp32", choices=["bf16", "fp32"],
                     help="headline precision: fp32 end to end (the reference's Keras float32, default) or bf16 "
                          "(fp32 accumulation)")
-    ap.add_argument("--no-bf16", action="store_true", help="skip the bf16 companion timing (value_bf16)")
-    ap.add_argument("--no-pp", action="store_true", help="N > 1: skip the pipeline sub-benchmark")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the bf16 companion (value_bf16) and, "
+                         "with N > 1, the sub-runs of the other BASELINE.json configs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the model outputs of the last timed step to DIR/<name>.npy "
+                         "(float32; rank r of N > 1 writes <name>.rank<r>.npy)")
+    ap.add_argument("--no-bf16", action="store_true", help="--full: skip the bf16 companion timing (value_bf16)")
+    ap.add_argument("--no-pp", action="store_true", help="--full, N > 1: skip the pipeline sub-benchmark")
     ap.add_argument("--pp-dtype", default="", choices=["", "bf16", "fp32"],
                     help="precision of the pipeline sub-benchmark (default: --dtype)")
     ap.add_argument("--codec", default="none", choices=["none", "lz4", "zvc"],
                     help="pp/ppdp: compress stage-boundary activations on a side stream (BASELINE config 3)")
-    ap.add_argument("--no-fault", action="store_true", help="N > 1: skip the kill/recovery sub-run (config 4)")
-    ap.add_argument("--no-subruns", action="store_true", help="N > 1: headline only")
+    ap.add_argument("--no-fault", action="store_true", help="--full, N > 1: skip the kill/recovery sub-run (config 4)")
+    ap.add_argument("--no-subruns", action="store_true", help="--full, N > 1: headline (and bf16 companion) only")
     ap.add_argument("--sub-budget", type=float, default=420.0,
                     help="seconds all sub-runs together may take (each also has its own limit)")
     ap.add_argument("--fault-duration", type=float, default=10.0)
@@ -197,6 +208,54 @@ def timed(job, steps: int, warmup: int, dev, world: int, stamps=None) -> float:
     if hasattr(job, "finish"):
         job.finish()
     return _max_over_ranks(elapsed, world)
+
+
+def synthetic_input(batch: int, image, rank: int, dev) -> torch.Tensor:
+    """The headline's input batch: seeded per rank, so every run with the same arguments sees the same data."""
+    gen = torch.Generator(device=dev).manual_seed(1234 + rank)
+    return torch.randn((batch,) + tuple(image), generator=gen, device=dev)
+
+
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: all files together
+
+
+def job_outputs(job) -> dict:
+    """What a caller of the timed path receives on this rank: the model's output
+    buffers as the last step left them (a pipeline's last stage holds them;
+    other stages return {}), plus the pre-softmax logits where the model ends
+    in a softmax classifier."""
+    if hasattr(job, "outputs"):
+        outs = dict(job.outputs())
+    elif getattr(job, "next", None) is None:
+        outs = {o: job.ex.output_buf(o) for o in job.ex.outputs}
+    else:
+        return {}
+    logits = job.ex.logits()
+    if logits is not None and "logits" not in outs:
+        outs["logits"] = logits
+    return outs
+
+
+def dump_outputs(dirpath: str, arrays: dict, suffix: str = "", limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """Write {name: tensor or array} as ``dirpath/<name><suffix>.npy`` in float32
+    (float64 stays float64).  An array over its share of `limit` is stored as a
+    fixed sample: the elements of the flattened array at sorted indices drawn
+    once from a generator seeded with 0, so two runs sample the same elements.
+    Returns {name: number of elements written}."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    share = limit // max(1, len(arrays)) - 1024          # 1 KiB for each file's .npy header
+    written = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().to("cpu", torch.float64 if a.dtype == torch.float64 else torch.float32).numpy()
+        a = np.asarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirpath, name.replace("/", "_") + suffix + ".npy"), a)
+        written[name] = int(a.size)
+    return written
 
 
 def _p2p_rates(job, dev, world: int, mib: int = 64, reps: int = 10) -> dict:
@@ -338,8 +397,8 @@ SUB_LIMIT_S = {"pp": 90.0, "pp_r152": 90.0, "fault": 240.0}   # N = 4 worst case
 
 def plan_subruns(args, world: int, backend: str) -> list:
     """(name, kind, argv, nprocs, limit_s, label) of the BASELINE.json configs a
-    `--gpus N` dp run measures after its headline."""
-    if args.no_subruns or args.mode != "dp" or world < 2:
+    `--full --gpus N` dp run measures after its headline."""
+    if not args.full or args.no_subruns or args.mode != "dp" or world < 2:
         return []
     common = ["--steps", str(args.steps), "--warmup", str(args.warmup), "--batch", str(args.batch),
               "--backend", backend, "--seed", str(args.seed)] + (["--no-graph"] if args.no_graph else [])
@@ -527,14 +586,13 @@ def main(argv=None):
     part_at = [s for s in args.part_at.split(",") if s]
     image = tuple(g.layers[g.input].out_shape)          # 224x224x3 (ResNet-50); the model's own size otherwise
 
-    def headline(precision: str, warmup: int):
+    def headline(precision: str, warmup: int, dump: str = ""):
         job = runner.build_job(g, weights, mode=args.mode, world=world, rank=rank, device=dev, batch=args.batch,
                                stages=args.stages, part_at=part_at, graph=not args.no_graph, tune=args.tune,
                                host_staged=(backend != "nccl"), streams=args.streams, codec=args.codec,
                                precision=precision)
         # synthetic input, resident on device (data="synthetic")
-        gen = torch.Generator(device=dev).manual_seed(1234 + rank)
-        job.set_synthetic_input(torch.randn((args.batch,) + image, generator=gen, device=dev))
+        job.set_synthetic_input(synthetic_input(args.batch, image, rank, dev))
         elapsed = timed(job, args.steps, warmup, dev, world)
         info = {"global_batch": job.global_batch, "parallelism": job.parallelism, "part_at": job.part_at}
         link = getattr(job, "link", None)
@@ -542,15 +600,17 @@ def main(argv=None):
             info["codec"] = args.codec
             info["wire_ratio"] = round(link.ratio, 4) if link.ratio else None
         value = job.images_per_step * args.steps / elapsed
+        if dump:
+            dump_outputs(dump, job_outputs(job), suffix=f".rank{rank}" if world > 1 else "")
         if hasattr(job, "close"):
             job.close()
         del job
         torch.cuda.empty_cache()
         return value, elapsed, info
 
-    value, elapsed, info = headline(args.dtype, args.warmup)
+    value, elapsed, info = headline(args.dtype, args.warmup, dump=args.dump_outputs)
     bf16 = None
-    if args.dtype == "fp32" and not args.no_bf16:
+    if args.full and args.dtype == "fp32" and not args.no_bf16:
         # the companion runs after the headline's teardown, on a card whose clocks dropped while the bf16 job
         # was built: at least 20 untimed steps (3 ms of work at W = 5 left 20-step timings 2-3 % low); still
         # exactly K timed steps

@@ -19,6 +19,7 @@ def test_defaults_are_reference_precision():
     b = _bench()
     a = b.parse([])
     assert a.dtype == "fp32" and a.gpus >= 1 and a.mode == "dp" and not a.no_bf16 and not a.no_pp
+    assert not a.full and a.dump_outputs == ""          # a plain run: the headline only, nothing written
 
 
 def test_record_fields_and_pp_subobject():
@@ -64,8 +65,9 @@ def test_subrun_plan_covers_every_baseline_config():
     """N=2: config 2's multi-tensor cut; N=4: config 5 (R152 4-stage bf16);
     N=8: config 3 (lz4 on the links); N>=2: config 4 (kill + recovery)."""
     b = _bench()
-    a = b.parse(["--steps", "20", "--warmup", "5"])
+    a = b.parse(["--full", "--steps", "20", "--warmup", "5"])
     assert b.plan_subruns(a, 1, "nccl") == []
+    assert b.plan_subruns(b.parse(["--steps", "20", "--warmup", "5"]), 8, "nccl") == []   # sub-runs need --full
     s2 = _names(b.plan_subruns(a, 2, "nccl"))
     assert set(s2) == {"pp", "fault"}
     pp = s2["pp"][2]
@@ -85,16 +87,16 @@ def test_subrun_plan_covers_every_baseline_config():
     assert s8["fault"][1] == "fault" and s8["fault"][3] == 1
     # the steps / warmup / backend of the headline reach the pipeline sub-runs
     assert pp8[pp8.index("--steps") + 1] == "20" and pp8[pp8.index("--backend") + 1] == "nccl"
-    assert b.plan_subruns(b.parse(["--no-subruns"]), 8, "nccl") == []
-    assert set(_names(b.plan_subruns(b.parse(["--no-fault"]), 8, "nccl"))) == {"pp"}
-    assert b.plan_subruns(b.parse(["--mode", "pp"]), 8, "nccl") == []
+    assert b.plan_subruns(b.parse(["--full", "--no-subruns"]), 8, "nccl") == []
+    assert set(_names(b.plan_subruns(b.parse(["--full", "--no-fault"]), 8, "nccl"))) == {"pp"}
+    assert b.plan_subruns(b.parse(["--full", "--mode", "pp"]), 8, "nccl") == []
 
 
 def test_subrun_time_limits_fit_the_driver():
     """Worst case (every sub-run of N hits its limit) stays under the budget, and the fault sub-run
     (last) keeps its whole limit even when the pipeline sub-runs before it hit theirs."""
     b = _bench()
-    a = b.parse([])
+    a = b.parse(["--full"])
     assert a.sub_budget <= 420
     assert all(v <= a.sub_budget for v in b.SUB_LIMIT_S.values())
     for world in (2, 4, 8):
@@ -233,13 +235,57 @@ def test_pp_record_carries_pair_rates_and_phases():
         assert key in src
 
 
+def test_dump_outputs_writes_float32_npy_and_samples_large_arrays(tmp_path):
+    """`--dump-outputs`: one .npy per output in float32 (float64 kept), '/' in a
+    layer name made a file name, and an array over its share of the byte limit
+    stored as the same seeded sample on every call."""
+    import numpy as np
+    import torch
+    b = _bench()
+    assert b.DUMP_LIMIT_BYTES == 64 << 20
+    big = torch.arange(5000, dtype=torch.float32).reshape(50, 100)
+    arrays = {"predictions": torch.linspace(0, 1, 12, dtype=torch.bfloat16).reshape(3, 4),
+              "head/logits": np.arange(6, dtype=np.float64).reshape(2, 3), "big": big}
+    d1, d2 = tmp_path / "a", tmp_path / "b" / "nested"
+    n1 = b.dump_outputs(str(d1), arrays, limit=3 * 5024)             # 4000 bytes of data per file
+    n2 = b.dump_outputs(str(d2), arrays, suffix=".rank1", limit=3 * 5024)
+    assert sorted(p.name for p in d1.iterdir()) == ["big.npy", "head_logits.npy", "predictions.npy"]
+    assert sorted(p.name for p in d2.iterdir()) == ["big.rank1.npy", "head_logits.rank1.npy",
+                                                    "predictions.rank1.npy"]
+    p = np.load(d1 / "predictions.npy")
+    assert p.dtype == np.float32 and p.shape == (3, 4)
+    assert np.array_equal(p, arrays["predictions"].float().numpy())
+    lg = np.load(d1 / "head_logits.npy")
+    assert lg.dtype == np.float64 and np.array_equal(lg, arrays["head/logits"])
+    s1, s2 = np.load(d1 / "big.npy"), np.load(d2 / "big.rank1.npy")
+    assert s1.dtype == np.float32 and s1.shape == (1000,) and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) > 0) and set(s1.tolist()) <= set(range(5000))     # distinct elements, in order
+    assert n1 == n2 == {"predictions": 12, "head/logits": 6, "big": 1000}
+    assert sum(f.stat().st_size for f in d1.iterdir()) <= 3 * 5024
+
+
+def test_job_outputs_of_replicas_and_pipeline_stages():
+    """What `--dump-outputs` takes from a job: a replica's output buffers and its
+    logits; of a pipeline only the last stage holds any."""
+    import types
+    b = _bench()
+    ex = types.SimpleNamespace(outputs=["predictions"], output_buf=lambda o: f"buf:{o}", logits=lambda: "lg")
+    dp = types.SimpleNamespace(ex=ex, outputs=lambda: {"predictions": "probs"})
+    assert b.job_outputs(dp) == {"predictions": "probs", "logits": "lg"}
+    last = types.SimpleNamespace(ex=ex, next=None)
+    assert b.job_outputs(last) == {"predictions": "buf:predictions", "logits": "lg"}
+    assert b.job_outputs(types.SimpleNamespace(ex=ex, next=3)) == {}
+    ex.logits = lambda: None
+    assert b.job_outputs(last) == {"predictions": "buf:predictions"}
+
+
 def test_every_planned_subrun_gets_time_at_n4():
     """Round 6's N=4 rehearsal skipped the plain pipeline sub-run ("budget spent"):
     the later sub-runs' reserved limits exceeded the budget.  Every planned
     sub-run now starts with at least 60 s even when the ones before it used
     their whole limits."""
     b = _bench()
-    a = b.parse([])
+    a = b.parse(["--full"])
     for world in (2, 4, 8):
         plan = b.plan_subruns(a, world, "nccl")
         left = a.sub_budget

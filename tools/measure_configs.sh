@@ -18,7 +18,7 @@ run() {   # secs name cmd...
 [ -n "$SKIP_LOCAL" ] || run 300 local_cpu_bs1 $M local-infer --model resnet50 --batch 1 --requests 10 --device cpu
 [ -n "$SKIP_LOCAL" ] || run 300 local_gpu_bs1 $M local-infer --model resnet50 --batch 1 --requests 200 --device cuda
 [ -n "$SKIP_LOCAL" ] || run 300 local_gpu_bs32 $M local-infer --model resnet50 --batch 32 --requests 200 --device cuda
-[ -n "$SKIP_LOCAL" ] || run 300 bench_r152 python bench.py --model resnet152 --steps 50 --warmup 10
+[ -n "$SKIP_LOCAL" ] || run 300 bench_r152 python bench.py --full --model resnet152 --steps 50 --warmup 10
 run 400 serve_2stage_tcp $M serve --model resnet50 --batch 32 --part-at conv3_block1_1_conv --spawn 2 --device cuda:0 --codec none --requests 300
 run 300 serve_2stage_bs1 $M serve --model resnet50 --batch 1 --part-at conv3_block1_1_conv --spawn 2 --device cuda:0 --codec none --requests 500
 run 400 serve_2stage_zvc $M serve --model resnet50 --batch 32 --part-at conv3_block1_1_conv --spawn 2 --device cuda:0 --codec zvc --requests 300

@@ -565,13 +565,20 @@ WINO4_AT = np.array([[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0
 # ring stage, R ring slots, block order 0 = channel blocks fastest / 1 = tile blocks fastest.  ksplit >= 1
 # (C / 16 divisible by it; > 1 adds the split-K reduce launch).  Workspace: V (36 x 16-tile groups x C) then
 # the split-K partial outputs (wino4s_ws_elems).
+# 238+: row split, id -> (WT, WN, PG, R, order, RG): a block owns RG of the 6 rows of the 6x6 position grid and
+# all of K (ksplit 1 only); it leaves its rows half-transformed, tr[6][tiles][4][N] behind V, and
+# wino4s_finish_kernel completes A^T M A + bias / ReLU.  Nothing is summed across blocks.
 WINO4S_F32_CFGS = {220: (2, 2, 6, 4, 0), 221: (2, 2, 6, 3, 0), 222: (1, 2, 6, 4, 0), 223: (2, 4, 4, 4, 0),
                    224: (2, 2, 6, 4, 1), 225: (2, 1, 6, 4, 0), 226: (1, 1, 9, 4, 0), 227: (2, 2, 4, 4, 0),
                    228: (4, 2, 4, 4, 0), 229: (4, 2, 4, 4, 1), 230: (2, 2, 12, 3, 0), 231: (2, 2, 12, 3, 1),
                    # fragments of the next stage read under the current stage's MFMAs
                    232: (2, 2, 4, 4, 0), 233: (2, 2, 6, 3, 0), 234: (2, 2, 6, 4, 0), 235: (2, 4, 4, 4, 0),
                    236: (2, 2, 4, 5, 0), 237: (2, 2, 2, 8, 0),      # deeper rings, 2 blocks per CU
+                   238: (2, 2, 6, 2, 0, 1), 239: (2, 2, 4, 3, 0, 2), 240: (2, 2, 6, 3, 0, 1),
+                   241: (1, 2, 6, 2, 0, 1), 242: (2, 1, 6, 2, 0, 1), 243: (1, 2, 2, 8, 0, 1),
+                   244: (2, 2, 6, 2, 0, 2), 245: (2, 2, 6, 2, 0, 3), 246: (2, 2, 2, 6, 0, 1),
                    299: (2, 2, 6, 3, 0)}     # 299: 221 with per-wave stamps (tools/wino4s_timeline.py), never tuned
+WINO4S_ROW_CFGS = frozenset(c for c, g in WINO4S_F32_CFGS.items() if len(g) > 5)
 
 
 def wino4s_supported(pc: "PackedConv") -> bool:
@@ -591,8 +598,15 @@ def wino4s_pack_np(kernel_hwio: np.ndarray) -> np.ndarray:
                                 .astype(np.float32))
 
 
-def wino4s_ws_elems(B: int, H: int, W: int, C: int, N: int, ksplit: int) -> int:
-    return int(kernels().wino4s_ws_floats(B, H, W, C, N, ksplit))
+def wino4s_ws_elems(B: int, H: int, W: int, C: int, N: int, ksplit: int, cfg: Optional[int] = None) -> int:
+    """Workspace floats of config `cfg` (V, then the split-K slabs or the row split's half-transformed rows);
+    without `cfg`, enough for every config at this split."""
+    if cfg is not None:
+        return int(kernels().wino4s_ws_floats_cfg(int(cfg), B, H, W, C, N, ksplit))
+    need = int(kernels().wino4s_ws_floats(B, H, W, C, N, ksplit))
+    if ksplit == 1:
+        need = max(need, int(kernels().wino4s_ws_floats_cfg(min(WINO4S_ROW_CFGS), B, H, W, C, N, 1)))
+    return need
 
 
 def wino4s_splits(C: int) -> list:
@@ -668,15 +682,17 @@ def pack_pw_f32(kernel_hwio: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(w.transpose(3, 0, 1, 4, 2).reshape(N // 16, K // 16, 64, 4).astype(np.float32))
 
 
-def f32_cfg_supported(cfg: int, cin: int, cout: int, pc: Optional["PackedConv"] = None) -> bool:
+def f32_cfg_supported(cfg: int, cin: int, cout: int, pc: Optional["PackedConv"] = None,
+                      residual: bool = False) -> bool:
     """Whether fp32 tile config `cfg` runs a conv with `cin` input / `cout` output channels
     (Winograd configs also need the conv itself: 3x3 / s1 / p1 with its transformed weights;
-    the pointwise configs a 1x1 / s1 conv with its fragment-packed weights)."""
+    the pointwise configs a 1x1 / s1 conv with its fragment-packed weights).  `residual`: the conv has a
+    fused residual input, which the F(4x4) split configs do not take."""
     if cfg in PW_F32_CFGS:
         return (pc is not None and pc.pwf is not None and PW_F32_CFGS[cfg] in PW_F32_BMS[pc.cin]
                 and pw_f32_shape_ok(pc, PW_F32_CFGS[cfg]))
     if cfg in WINO4S_F32_CFGS:
-        return (pc is not None and pc.wino4s is not None and wino4s_supported(pc)
+        return (not residual and pc is not None and pc.wino4s is not None and wino4s_supported(pc)
                 and bool(kernels().wino4s_ok(cfg, cin, cout, 1)))
     if cfg in F32S_CFGS:
         return pc is not None and f32s_supported(pc)
@@ -813,11 +829,13 @@ def conv_forward_f32(x: torch.Tensor, pc: PackedConv, out: torch.Tensor, residua
         # Winograd F(4x4, 3x3): input transform -> V (workspace), pure-MFMA GEMM with the output transform in
         # its epilogue, and for ksplit > 1 the split-K reduce (bias / ReLU there)
         ksplit = int(ksplit) or 1
-        if (not f32_cfg_supported(cfg, C, N, pc) or (OH, OW) != (H, W) or x.dim() != 4 or residual is not None
-                or not kernels().wino4s_ok(cfg, C, N, ksplit)):
+        if (not f32_cfg_supported(cfg, C, N, pc, residual is not None) or (OH, OW) != (H, W) or x.dim() != 4
+                or not kernels().wino4s_ok(cfg, C, N, ksplit)
+                or not kernels().wino4s_range_ok(cfg, B, H, W, C, N, ksplit)):
             raise ValueError(f"Winograd F(4x4) split config {cfg}: 3x3/s1/p1 conv with wino4s weights, C % 16 == 0, "
-                             f"N % (16 x WN) == 0, no residual, |ksplit| in {wino4s_splits(C)} (fused: <= -2)")
-        need = wino4s_ws_elems(B, H, W, C, N, ksplit)
+                             f"N % (16 x WN) == 0, no residual, |ksplit| in {wino4s_splits(C)} (fused: <= -2; "
+                             f"row-split configs {min(WINO4S_ROW_CFGS)}+: ksplit 1), V / U / slabs / rows below 2 GiB")
+        need = wino4s_ws_elems(B, H, W, C, N, ksplit, cfg)
         if workspace is None:
             workspace = torch.empty(need, dtype=torch.float32, device=x.device)
         if workspace.numel() < need or workspace.dtype != torch.float32:

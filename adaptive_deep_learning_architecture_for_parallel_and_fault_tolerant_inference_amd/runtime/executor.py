@@ -476,7 +476,7 @@ class SliceExecutor:
             if self.fp32:
                 if cfg in conv_ops.WINO4S_F32_CFGS:        # V and the split-K partials, whatever the split
                     B, H, W, C, OH, OW, pc = self._conv_geom(i)
-                    need = max(need, conv_ops.wino4s_ws_elems(B, H, W, C, pc.cout, ks))
+                    need = max(need, conv_ops.wino4s_ws_elems(B, H, W, C, pc.cout, ks, cfg))
                     ctr = max(ctr, conv_ops.f32_counter_elems(cfg, ks, B, H, W, OH, OW, pc.cout, pc.Kpad))
                     continue
                 if ks != 1:
@@ -509,6 +509,8 @@ class SliceExecutor:
             if self.fp32:
                 key = "f32|" + conv_key(B, H, W, C, pc)
                 cfg, ks = table[key][:2] if key in table else conv_ops.choose_cfg_f32(B * OH * OW, pc.cout, pc.Kpad)
+                if cfg in conv_ops.WINO4S_F32_CFGS and len(st.ins) > 1:     # the key does not see a fused residual
+                    cfg, ks = conv_ops.choose_cfg_f32(B * OH * OW, pc.cout, pc.Kpad)
                 self.cfg[i] = (int(cfg), int(ks))
                 continue
             if pc.cout % 8:
@@ -571,13 +573,16 @@ class SliceExecutor:
             best = None
             for cfg in (list(conv_ops.F32_TILES) + list(conv_ops.WINO_F32_CFGS) + list(conv_ops.WINO4S_F32_CFGS)
                         + list(conv_ops.PW_F32_CFGS) + list(conv_ops.F32S_CFGS)):
-                if (not conv_ops.f32_cfg_supported(cfg, C, pc.cout, pc) or cfg in conv_ops.WINO_MEASURE_CFGS
+                if (not conv_ops.f32_cfg_supported(cfg, C, pc.cout, pc, len(st.ins) > 1)
+                        or cfg in conv_ops.WINO_MEASURE_CFGS
                         or cfg in conv_ops.F32_UNTUNED):
                     continue
                 if cfg in conv_ops.WINO4S_F32_CFGS:       # F(4x4) transform + GEMM: split-K, fused fixup
                     sp = [k for k in conv_ops.wino4s_splits(C) if k > 1]
                     tiles, kts, sks = int(conv_ops.kernels().wino4s_blocks(cfg, B, H, W, N)), C // 16, \
                         tuple(-k for k in sp)
+                    if cfg in conv_ops.WINO4S_ROW_CFGS:   # row split: whole K only
+                        kts, sks = 1, ()
                 elif cfg in conv_ops.PW_F32_CFGS:            # persistent pointwise: whole K, one launch
                     tiles, kts, sks = 0, 1, ()
                 elif cfg in conv_ops.F32S_CFGS:             # big-tile 1x1 GEMM: tiles, or stream-K over 256
@@ -604,7 +609,7 @@ class SliceExecutor:
                         continue
                     if -100 < ks < 0 and cfg in conv_ops.WINO_F32_CFGS and (kts // -ks < 2 or tiles >= 2 * conv_ops.NUM_CUS):
                         continue
-                    nws = (conv_ops.wino4s_ws_elems(B, H, W, C, N, ks) if cfg in conv_ops.WINO4S_F32_CFGS
+                    nws = (conv_ops.wino4s_ws_elems(B, H, W, C, N, ks, cfg) if cfg in conv_ops.WINO4S_F32_CFGS
                            else conv_ops.workspace_elems_f32(M, N, pc.Kpad, cfg, ks))
                     ws = torch.empty(nws, dtype=torch.float32, device=self.device) if nws else None
                     nctr = conv_ops.f32_counter_elems(cfg, ks, B, H, W, OH, OW, N, pc.Kpad)

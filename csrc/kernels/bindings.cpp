@@ -221,6 +221,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("wino4s_set_debug", [](u64 buf) { adapt::wino4s_set_debug(P<unsigned long long>(buf)); });
   m.def("wino4s_ok", &adapt::wino4s_ok);
   m.def("wino4s_ws_floats", &adapt::wino4s_ws_floats);
+  m.def("wino4s_ws_floats_cfg", &adapt::wino4s_ws_floats_cfg);
+  m.def("wino4s_range_ok", &adapt::wino4s_range_ok);
   m.def("pw_f32_tail_plan", [](int M, int K, int N, int n_split, int bm) {
     int tail = 0, parts = 0;
     adapt::pw_f32_tail_plan(M, K, N, n_split, bm, &tail, &parts);

@@ -175,10 +175,11 @@ bool conv_wino_f32_ok(int cfg, int C, int N);
 bool conv_wino_f32_cfg(int cfg, int* nw, int* fn);
 hipError_t conv_wino_f32_launch(const WinoF32Params& p, int cfg, hipStream_t s);
 
-// fp32 Winograd F(4x4, 3x3) as transform + pure-MFMA GEMM (wino4s_f32.hip, cfg ids 220-235; the fused
+// fp32 Winograd F(4x4, 3x3) as transform + pure-MFMA GEMM (wino4s_f32.hip, cfg ids 220-246; the fused
 // F(4x4) kernels of round 5, cfg 200 / 210, are retired to tools/experiments/): u = weights in
 // fragment order [N/16][C/16][36 positions][64 lanes][4] (ops/conv.py wino4s_pack_np); ws holds V (then the
-// split-K slabs), wino4s_ws_floats of it
+// split-K slabs, or for the row-split configs 238+ the half-transformed rows tr[6][tiles][4][N]),
+// wino4s_ws_floats_cfg of it
 struct Wino4sParams {
   const float* x;
   float* v;           // set by wino4s_forward (= ws)
@@ -196,6 +197,8 @@ void wino4s_set_debug(unsigned long long* buf);
 bool wino4s_ok(int cfg, int C, int N, int ksplit);
 int wino4s_blocks(int cfg, int B, int H, int W, int N);
 size_t wino4s_ws_floats(int B, int H, int W, int C, int N, int ksplit);
+size_t wino4s_ws_floats_cfg(int cfg, int B, int H, int W, int C, int N, int ksplit);   // row split (238+): V + tr
+bool wino4s_range_ok(int cfg, int B, int H, int W, int C, int N, int ksplit);   // 32-bit byte offsets stay < 2^31
 hipError_t wino4s_forward(const Wino4sParams& p, int cfg, hipStream_t s);
 // fp32 big-tile 1x1 GEMM (gemm_f32s.hip, cfg ids 300+): tile (BM, BN) per cfg; ksplit 1 (tiles) or -1 (stream-K
 // over 256 blocks: gemm_f32s_ws_elems floats of workspace, one zeroed int32 counter per tile)

@@ -8,6 +8,12 @@
 //                         registers (every lane holds all 36 positions of its (tile, channel) pairs).
 //   3. wino4s_reduce_kernel (split-K only): the splits' partial outputs summed in split order + bias / ReLU.
 //
+// Row split (cfg ids 238+, template parameter RG): where tiles x channels alone give too few blocks for the
+// chip, a block owns RG of the 6 rows a of the 6x6 position grid instead of a share of K.  The output
+// transform y = A^T M A is separable, so the block runs all of K on its 6 RG accumulators, applies A^T along
+// b to its rows and writes tr[a][tile][j][N] (4 values per row, tile and channel; no partial sums, nothing
+// is added across blocks); wino4s_finish_kernel applies A^T along a, adds bias / ReLU and scatters to NHWC.
+//
 // Why this shape (MI355X-first): the fused F(4x4) kernels (conv_wino4_f32.hip) transform the input inside
 // the K loop, and that fp32 VALU work takes issue cycles from the MFMA of the partner wave on the same SIMD
 // (profiles/r5/wino4_attribution.md: 33.4 -> 38.6 cycles per MFMA).  Here the K loop issues nothing but
@@ -144,14 +150,18 @@ __global__ __launch_bounds__(256) void wino4s_in_kernel(Wino4sParams p) {
 // shader clock at start / first stage landed / K loop done / epilogue done, the summed clocks spent in the
 // per-stage land wait (vmcnt + barrier), the summed clocks from each barrier to the stage's last MFMA issue,
 // the stage count and HW_ID
-template <int WT, int WN, int PG, int R, bool PIPE, bool STAMP = false>
+// RG > 0: row split -- the block index that is the K split otherwise selects rows RG s .. RG s + RG - 1; the
+// block walks their 6 RG positions of every chunk and its epilogue writes the half-transformed rows
+template <int WT, int WN, int PG, int R, bool PIPE, bool STAMP = false, int RG = 0>
 __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sParams p) {
   constexpr int NW = WT * WN;
-  constexpr int NST = 36 / PG;                   // stages per 16-channel chunk
+  constexpr int NP = RG ? 6 * RG : 36;           // positions (= accumulator fragments) of a wave
+  constexpr int NST = NP / PG;                   // stages per 16-channel chunk
   constexpr int PIECES = (WT + WN) * PG;         // 1 KiB units per stage
   constexpr int PPW = PIECES / NW;               // LDS-DMA pieces per wave per stage
   constexpr int SLOT = PIECES * 1024;
-  static_assert(36 % PG == 0 && (WT * PG) % NW == 0 && (WN * PG) % NW == 0, "stage geometry");
+  static_assert(NP % PG == 0 && (WT * PG) % NW == 0 && (WN * PG) % NW == 0, "stage geometry");
+  static_assert(RG == 0 || 6 % RG == 0, "row groups");
   static_assert(R >= 2 && R * SLOT <= 160 * 1024, "LDS ring");
   static_assert((R - 2) * PPW < 64, "vmcnt range");
   __shared__ __attribute__((aligned(16))) char smem[R * SLOT];
@@ -160,7 +170,7 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
   const int wt = wave / WN, wn = wave - wt * WN;
   // block -> (split, tile block, channel block); blocks whose index differs by a multiple of 8 run on one XCD,
   // so consecutive logical ids (which share operands) are gathered onto one XCD when the grid allows
-  const int TBn = (p.TG + WT - 1) / WT, NBn = p.N / (16 * WN), S = p.ksplit;
+  const int TBn = (p.TG + WT - 1) / WT, NBn = p.N / (16 * WN), S = RG ? 6 / RG : p.ksplit;
   const int nblk = TBn * NBn * S;
   int L = blockIdx.x;
   if ((nblk & 7) == 0) L = (L & 7) * (nblk >> 3) + (L >> 3);
@@ -176,7 +186,8 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
     nb = L % NBn;
     s = L / NBn;
   }
-  const int KCs = p.KC / S, kc0 = s * KCs;
+  const int KCs = RG ? p.KC : p.KC / S, kc0 = RG ? 0 : s * KCs;
+  const int pr0 = RG ? 6 * RG * s : 0;           // first position of the block's rows
   const int NS = KCs * NST;
   const u32x4 rv = w4s_desc(p.v), ru = w4s_desc(p.u);
   const unsigned lds0 = (unsigned)(uintptr_t)smem;
@@ -204,7 +215,7 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
   }
   const unsigned vlane = (unsigned)lane * 16u;
   auto issue = [&](int st) {
-    const int kc = kc0 + st / NST, p0 = (st % NST) * PG;
+    const int kc = kc0 + st / NST, p0 = pr0 + (st % NST) * PG;
     const unsigned soff = (unsigned)((kc * 36 + p0) * 1024);
     const unsigned slot = lds0 + (unsigned)((st % R) * SLOT) + (unsigned)wave * 1024u;
 #pragma unroll
@@ -214,9 +225,9 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
     }
   };
 
-  f32x4v acc[36];
+  f32x4v acc[NP];
 #pragma unroll
-  for (int q = 0; q < 36; ++q) acc[q] = (f32x4v){0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < NP; ++q) acc[q] = (f32x4v){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int st = 0; st < R - 1; ++st)
     if (st < NS) issue(st);
@@ -297,24 +308,31 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
   // ---- output transform on the accumulators: lane l holds M_p[tile 16 tg + 4 (l >> 4) + i][cout] at acc[p][i]
   const int tg = tb * WT + wt;
   const int n = (nb * WN + wn) * 16 + (lane & 15);
-  float y[4][16];
+  constexpr int NR = RG ? 4 * RG : 16;            // rows of N channels a tile leaves: pixels, or tr[a][j]
+  float y[4][16];                                 // the first NR of every y[i] are used
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    float tr[6][4];                                 // A^T applied along b: tr[a][j]
+    float tr[NP / 6][4];                            // A^T applied along b: tr[a][j]
 #pragma unroll
-    for (int a = 0; a < 6; ++a)
+    for (int a = 0; a < NP / 6; ++a)
       w4s_at(acc[a * 6 + 0][i], acc[a * 6 + 1][i], acc[a * 6 + 2][i], acc[a * 6 + 3][i], acc[a * 6 + 4][i],
              acc[a * 6 + 5][i], tr[a][0], tr[a][1], tr[a][2], tr[a][3]);
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-      w4s_at(tr[0][j], tr[1][j], tr[2][j], tr[3][j], tr[4][j], tr[5][j], y[i][j], y[i][4 + j], y[i][8 + j],
-             y[i][12 + j]);
+    for (int j = 0; j < 4; ++j) {
+      if constexpr (RG > 0) {
+#pragma unroll
+        for (int a = 0; a < RG; ++a) y[i][a * 4 + j] = tr[a][j];
+      } else {
+        w4s_at(tr[0][j], tr[1][j], tr[2][j], tr[3][j], tr[4][j], tr[5][j], y[i][j], y[i][4 + j], y[i][8 + j],
+               y[i][12 + j]);
+      }
+    }
   }
   // Output rows leave through LDS: the block's (tile, pixel) rows of WN x 16 channels are staged, then stored
   // as 16-B chunks, 8 lanes per 128-B row segment (direct from the fragments every store instruction would
   // write 4 x 64 B with 4-B lanes: 12 us of the stage-2 epilogue, tools/wino4s_timeline.py)
   constexpr int CB = WN * 16, RP = CB + 4;
-  constexpr bool STAGE = WT * 16 * 16 * RP * 4 <= R * SLOT;      // the padded rows fit in the ring
+  constexpr bool STAGE = WT * 16 * NR * RP * 4 <= R * SLOT;      // the padded rows fit in the ring
   const int per = p.TH * p.TW;
   auto store_rows = [&](auto&& rowp) {
     if constexpr (STAGE) {
@@ -323,21 +341,21 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int u = 0; u < 16; ++u)
-          stg[((wt * 16 + 4 * (lane >> 4) + i) * 16 + u) * RP + wn * 16 + (lane & 15)] = y[i][u];
+        for (int u = 0; u < NR; ++u)
+          stg[((wt * 16 + 4 * (lane >> 4) + i) * NR + u) * RP + wn * 16 + (lane & 15)] = y[i][u];
       __syncthreads();
-      constexpr int C4 = CB / 4, TOTAL = WT * 16 * 16 * C4;
+      constexpr int C4 = CB / 4, TOTAL = WT * 16 * NR * C4;
       for (int e = threadIdx.x; e < TOTAL; e += NW * 64) {
         const int c4 = e % C4, row = e / C4;
-        const int t = tb * WT * 16 + row / 16;
-        float* dst = rowp(t, row & 15);
+        const int t = tb * WT * 16 + row / NR;
+        float* dst = rowp(t, row % NR);
         if (dst) *(f32x4v*)(dst + nb * CB + c4 * 4) = *(const f32x4v*)(stg + row * RP + c4 * 4);
       }
     } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int u = 0; u < 16; ++u) {
+        for (int u = 0; u < NR; ++u) {
           float* dst = rowp(tg * 16 + 4 * (lane >> 4) + i, u);
           if (dst) dst[n] = y[i][u];
         }
@@ -360,6 +378,14 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
       }
     }
   };
+  if constexpr (RG > 0) {
+    // row split: tr[a][tile][j][N] for the block's rows a = RG s + (u >> 2), j = u & 3 (wino4s_finish_kernel)
+    store_rows([&](int t, int u) -> float* {
+      return t < p.T ? p.ws + (((size_t)(RG * s + (u >> 2)) * p.T + t) * 4 + (u & 3)) * p.N : nullptr;
+    });
+    write_stamps();
+    return;
+  }
   if (S > 1 && p.counters == nullptr) {
     // split-K through wino4s_reduce_kernel: partial outputs [split][tile][16 pixels][N]
     store_rows([&](int t, int u) -> float* {
@@ -505,33 +531,79 @@ __global__ __launch_bounds__(256) void wino4s_reduce_ks_kernel(Wino4sParams p) {
   *((f32x4v*)(p.out + (((size_t)b * p.H + h) * p.W + w) * p.N) + n4) = o;
 }
 
+// ---------------------------------------------------------------- 3'. row split: the other half of A^T M A
+// one thread per (tile, column j, 4 channels): the six tr[a][tile][j] (all loads in flight at once), A^T
+// along a, bias, activation, the 4 pixels of column j to NHWC; 32-bit index math (wino4s_forward checks the
+// range)
+__global__ __launch_bounds__(256) void wino4s_finish_kernel(Wino4sParams p) {
+  const unsigned N4 = (unsigned)p.N >> 2;
+  const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+  const unsigned rowsz = (unsigned)p.T * 4u * N4;                          // f32x4 per row a
+  if (idx >= rowsz) return;
+  const unsigned tj = idx / N4;
+  const int n4 = (int)(idx - tj * N4);
+  const int j = (int)(tj & 3u), t = (int)(tj >> 2);
+  const f32x4v* src = (const f32x4v*)p.ws + idx;
+  f32x4v m[6];
+#pragma unroll
+  for (int a = 0; a < 6; ++a) m[a] = src[a * rowsz];
+  const int per = p.TH * p.TW;
+  const int b = t / per, rem = t - b * per;
+  const int th = rem / p.TW, tw = rem - th * p.TW;
+  const int w = 4 * tw + j;
+  if (w >= p.W) return;
+  const f32x4v bv = *((const f32x4v*)p.bias + n4);
+  float o[4][4];                                   // [channel][pixel row]
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    w4s_at(m[0][e], m[1][e], m[2][e], m[3][e], m[4][e], m[5][e], o[e][0], o[e][1], o[e][2], o[e][3]);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int h = 4 * th + i;
+    if (h >= p.H) break;
+    f32x4v v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = act_relu(o[e][i] + bv[e], p.relu);
+    *((f32x4v*)(p.out + (((size_t)b * p.H + h) * p.W + w) * p.N) + n4) = v;
+  }
+}
+
 struct W4sCfg {
-  int wt, wn, pg, r, order;
+  int wt, wn, pg, r, order, rg;     // rg > 0: row split, rg rows of the position grid per block
 };
 
 // cfg id -> geometry (WT x WN waves, PG positions per stage, R-slot ring, block order 0: channel blocks
 // fastest / 1: tile blocks fastest)
 bool w4s_cfg(int cfg, W4sCfg* c) {
   switch (cfg) {
-    case 220: *c = {2, 2, 6, 4, 0}; return true;
-    case 221: *c = {2, 2, 6, 3, 0}; return true;
-    case 222: *c = {1, 2, 6, 4, 0}; return true;
-    case 223: *c = {2, 4, 4, 4, 0}; return true;
-    case 224: *c = {2, 2, 6, 4, 1}; return true;
-    case 225: *c = {2, 1, 6, 4, 0}; return true;
-    case 226: *c = {1, 1, 9, 4, 0}; return true;
-    case 227: *c = {2, 2, 4, 4, 0}; return true;
-    case 228: *c = {4, 2, 4, 4, 0}; return true;
-    case 229: *c = {4, 2, 4, 4, 1}; return true;
-    case 230: *c = {2, 2, 12, 3, 0}; return true;
-    case 231: *c = {2, 2, 12, 3, 1}; return true;
-    case 232: *c = {2, 2, 4, 4, 0}; return true;     // 232-235: pipelined fragment reads (PIPE)
-    case 233: *c = {2, 2, 6, 3, 0}; return true;
-    case 234: *c = {2, 2, 6, 4, 0}; return true;
-    case 235: *c = {2, 4, 4, 4, 0}; return true;
-    case 236: *c = {2, 2, 4, 5, 0}; return true;     // 236-237: deeper rings at 2 blocks per CU
-    case 237: *c = {2, 2, 2, 8, 0}; return true;
-    case 299: *c = {2, 2, 6, 3, 0}; return true;     // 221 + per-wave stamps (measurement, wino4s_set_debug)
+    case 220: *c = {2, 2, 6, 4, 0, 0}; return true;
+    case 221: *c = {2, 2, 6, 3, 0, 0}; return true;
+    case 222: *c = {1, 2, 6, 4, 0, 0}; return true;
+    case 223: *c = {2, 4, 4, 4, 0, 0}; return true;
+    case 224: *c = {2, 2, 6, 4, 1, 0}; return true;
+    case 225: *c = {2, 1, 6, 4, 0, 0}; return true;
+    case 226: *c = {1, 1, 9, 4, 0, 0}; return true;
+    case 227: *c = {2, 2, 4, 4, 0, 0}; return true;
+    case 228: *c = {4, 2, 4, 4, 0, 0}; return true;
+    case 229: *c = {4, 2, 4, 4, 1, 0}; return true;
+    case 230: *c = {2, 2, 12, 3, 0, 0}; return true;
+    case 231: *c = {2, 2, 12, 3, 1, 0}; return true;
+    case 232: *c = {2, 2, 4, 4, 0, 0}; return true;     // 232-235: pipelined fragment reads (PIPE)
+    case 233: *c = {2, 2, 6, 3, 0, 0}; return true;
+    case 234: *c = {2, 2, 6, 4, 0, 0}; return true;
+    case 235: *c = {2, 4, 4, 4, 0, 0}; return true;
+    case 236: *c = {2, 2, 4, 5, 0, 0}; return true;     // 236-237: deeper rings at 2 blocks per CU
+    case 237: *c = {2, 2, 2, 8, 0, 0}; return true;
+    case 238: *c = {2, 2, 6, 2, 0, 1}; return true;     // 238-246: row split (rg rows per block), whole K
+    case 239: *c = {2, 2, 4, 3, 0, 2}; return true;     //   238 / 239 / 244-246: 48 KiB rings, 3 blocks per CU
+    case 240: *c = {2, 2, 6, 3, 0, 1}; return true;
+    case 241: *c = {1, 2, 6, 2, 0, 1}; return true;     //   241-243: two waves, for 7x7x512 (768 blocks)
+    case 242: *c = {2, 1, 6, 2, 0, 1}; return true;
+    case 243: *c = {1, 2, 2, 8, 0, 1}; return true;
+    case 244: *c = {2, 2, 6, 2, 0, 2}; return true;
+    case 245: *c = {2, 2, 6, 2, 0, 3}; return true;
+    case 246: *c = {2, 2, 2, 6, 0, 1}; return true;
+    case 299: *c = {2, 2, 6, 3, 0, 0}; return true;     // 221 + per-wave stamps (measurement, wino4s_set_debug)
   }
   return false;
 }
@@ -544,6 +616,14 @@ hipError_t launch_gemm(const Wino4sParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 
+template <int WT, int WN, int PG, int R, int RG>
+hipError_t launch_rows(const Wino4sParams& p, hipStream_t s) {
+  const int TBn = (p.TG + WT - 1) / WT, NBn = p.N / (16 * WN);
+  hipLaunchKernelGGL((wino4s_gemm_kernel<WT, WN, PG, R, false, false, RG>), dim3(TBn * NBn * (6 / RG)),
+                     dim3(WT * WN * 64), 0, s, p);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 // ksplit >= 1: whole K (1) or split-K through the reduce launch; <= -2: split-K with the fixup fused (needs
@@ -552,6 +632,7 @@ bool wino4s_ok(int cfg, int C, int N, int ksplit) {
   W4sCfg c;
   const int ks = ksplit < 0 ? -ksplit : ksplit;
   if (!w4s_cfg(cfg, &c) || C % 16 || N % (16 * c.wn) || ks < 1 || ks > 8 || ksplit == -1) return false;
+  if (c.rg > 0 && ksplit != 1) return false;       // the row split runs whole K
   return (C / 16) % ks == 0;
 }
 
@@ -574,6 +655,31 @@ size_t wino4s_ws_floats(int B, int H, int W, int C, int N, int ksplit) {
   return v;
 }
 
+// the same for one config: the row-split configs keep tr[6][T][4][N] behind V instead of split slabs
+size_t wino4s_ws_floats_cfg(int cfg, int B, int H, int W, int C, int N, int ksplit) {
+  W4sCfg c;
+  if (!w4s_cfg(cfg, &c) || c.rg == 0) return wino4s_ws_floats(B, H, W, C, N, ksplit);
+  const size_t T = (size_t)B * ((H + 3) / 4) * ((W + 3) / 4);
+  return wino4s_ws_floats(B, H, W, C, N, 1) + 6 * T * 4 * N;
+}
+
+// Whether every area the kernels address with 32-bit byte offsets stays below 2^31 bytes: V and U (LDS-DMA
+// descriptors), the fused split-K slabs (ksplit <= -2: [split][block][wave][4096] floats) and the row split's
+// tr[6][T][4][N].  wino4s_forward refuses a launch for which this is false.
+bool wino4s_range_ok(int cfg, int B, int H, int W, int C, int N, int ksplit) {
+  W4sCfg c;
+  if (!w4s_cfg(cfg, &c)) return false;
+  const size_t lim = 0x7fffffffu;
+  const size_t T = (size_t)B * ((H + 3) / 4) * ((W + 3) / 4), TG = (T + 15) / 16;
+  if (TG * 16 * C * 36 * 4 >= lim || (size_t)(N / 16) * (C / 16) * 36 * 1024 >= lim) return false;
+  if (c.rg > 0 && T * 24 * N * 4 >= lim) return false;
+  if (ksplit < -1) {
+    const size_t blocks = ((TG + c.wt - 1) / c.wt) * (size_t)(N / (16 * c.wn));
+    if ((size_t)-ksplit * blocks * c.wt * c.wn * 4096 * 4 >= lim) return false;
+  }
+  return true;
+}
+
 static unsigned long long* g_w4s_dbg = nullptr;
 void wino4s_set_debug(unsigned long long* buf) { g_w4s_dbg = buf; }
 
@@ -582,6 +688,7 @@ hipError_t wino4s_forward(const Wino4sParams& p_in, int cfg, hipStream_t s) {
   p.dbg = g_w4s_dbg;
   W4sCfg c;
   if (!wino4s_ok(cfg, p.C, p.N, p.ksplit) || !w4s_cfg(cfg, &c)) return hipErrorInvalidValue;
+  if (!wino4s_range_ok(cfg, p.B, p.H, p.W, p.C, p.N, p.ksplit)) return hipErrorInvalidValue;
   const bool fused = p.ksplit < 0;
   if (fused && !p.counters) return hipErrorInvalidValue;
   if (!fused) p.counters = nullptr;
@@ -593,7 +700,6 @@ hipError_t wino4s_forward(const Wino4sParams& p_in, int cfg, hipStream_t s) {
   p.KC = p.C / 16;
   p.order = c.order;
   const size_t vfl = (size_t)p.TG * 16 * p.C * 36;
-  if (vfl * 4 >= 0x7fffffffu || (size_t)(p.N / 16) * p.KC * 36 * 1024 >= 0x7fffffffu) return hipErrorInvalidValue;
   if (!p.ws) return hipErrorInvalidValue;
   p.v = p.ws;
   float* slabs = p.ws + vfl;
@@ -625,7 +731,20 @@ hipError_t wino4s_forward(const Wino4sParams& p_in, int cfg, hipStream_t s) {
     case 223: e = launch_gemm<2, 4, 4, 4>(q, s); break;
     case 225: e = launch_gemm<2, 1, 6, 4>(q, s); break;
     case 226: e = launch_gemm<1, 1, 9, 4>(q, s); break;
+    case 238: e = launch_rows<2, 2, 6, 2, 1>(q, s); break;
+    case 239: e = launch_rows<2, 2, 4, 3, 2>(q, s); break;
+    case 240: e = launch_rows<2, 2, 6, 3, 1>(q, s); break;
+    case 241: e = launch_rows<1, 2, 6, 2, 1>(q, s); break;
+    case 242: e = launch_rows<2, 1, 6, 2, 1>(q, s); break;
+    case 243: e = launch_rows<1, 2, 2, 8, 1>(q, s); break;
+    case 244: e = launch_rows<2, 2, 6, 2, 2>(q, s); break;
+    case 245: e = launch_rows<2, 2, 6, 2, 3>(q, s); break;
+    case 246: e = launch_rows<2, 2, 2, 6, 1>(q, s); break;
     default: return hipErrorInvalidValue;
+  }
+  if (e == hipSuccess && c.rg > 0) {
+    hipLaunchKernelGGL(wino4s_finish_kernel, dim3((unsigned)(((size_t)p.T * p.N + 255) / 256)), dim3(256), 0, s, q);
+    return hipGetLastError();
   }
   if (e != hipSuccess || p.ksplit == 1 || fused) return e;
   const long total = (long)p.T * 16 * (p.N / 4);

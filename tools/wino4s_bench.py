@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Isolated timing of the fp32 3x3 paths on the ResNet-50 bs=32 shapes: the tuned config of the plan
-(tuning table) against every Winograd F(4x4) split config (csrc/kernels/wino4s_f32.hip) and split-K.
+(tuning table) against every Winograd F(4x4) split config (csrc/kernels/wino4s_f32.hip), split-K and row-split (238+, whole K).
 Each candidate runs 20 launches captured in one hipGraph (device time per launch).
 
     python tools/wino4s_bench.py [--json out.json]
@@ -55,7 +55,7 @@ def main():
             for ks in C_.wino4s_splits(C) + [-k for k in C_.wino4s_splits(C) if k > 1]:
                 if (kss and ks not in kss) or not C_.kernels().wino4s_ok(cfg, C, C, ks):
                     continue
-                need = C_.wino4s_ws_elems(B, H, H, C, C, ks)
+                need = C_.wino4s_ws_elems(B, H, H, C, C, ks, cfg)
                 w2 = ws if ws.numel() >= need else torch.empty(need, dtype=torch.float32, device="cuda")
                 us = 1e3 * SliceExecutor._time_graph(
                     lambda: C_.conv_forward_f32(x, pc, out, relu=1, cfg=cfg, ksplit=ks, workspace=w2, counters=ctr),

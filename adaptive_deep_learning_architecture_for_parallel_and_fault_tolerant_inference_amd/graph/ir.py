@@ -21,7 +21,8 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 OPS = (
     "input",      # graph input, attrs: shape
     "zeropad",    # attrs: pad=((t,b),(l,r))
-    "conv",       # attrs: filters, kernel=(kh,kw), stride, padding('valid'|'same'), use_bias, activation
+    "conv",       # attrs: filters, kernel=(kh,kw), stride, padding('valid'|'same'), use_bias, activation,
+                  # groups (optional, > 1 only: Keras Conv2D(groups=G); absent means 1)
     "dwconv",     # DepthwiseConv2D, multiplier 1: kernel, stride, padding, use_bias, activation
     "bn",         # attrs: epsilon
     "relu",       # attrs: max_value (None | 6.0: Keras ReLU(6.))
@@ -91,7 +92,8 @@ class Layer:
         if self.op == "conv":
             kh, kw = self.attrs["kernel"]
             cin = in_shapes[0][-1]
-            out = [(f"{self.name}/kernel", (kh, kw, cin, self.attrs["filters"]))]
+            # grouped (Keras layout): output channel o belongs to group o // (filters // groups)
+            out = [(f"{self.name}/kernel", (kh, kw, cin // self.attrs.get("groups", 1), self.attrs["filters"]))]
             if self.attrs.get("use_bias", True):
                 out.append((f"{self.name}/bias", (self.attrs["filters"],)))
             return out
@@ -124,7 +126,7 @@ class Layer:
         if self.op == "conv":
             kh, kw = self.attrs["kernel"]
             oh, ow, co = self.out_shape
-            return oh * ow * co * kh * kw * in_shapes[0][-1]
+            return oh * ow * co * kh * kw * in_shapes[0][-1] // self.attrs.get("groups", 1)
         if self.op == "dwconv":
             kh, kw = self.attrs["kernel"]
             oh, ow, co = self.out_shape
@@ -178,6 +180,11 @@ class Graph:
         for i in layer.inputs:
             if i not in self.layers:
                 raise ValueError(f"layer {layer.name!r} consumes unknown tensor {i!r}")
+        if layer.op == "conv" and layer.attrs.get("groups", 1) != 1:
+            gr, cin = layer.attrs["groups"], self.layers[layer.inputs[0]].out_shape[-1]
+            if not isinstance(gr, int) or gr < 1 or cin % gr or layer.attrs["filters"] % gr:
+                raise ValueError(f"conv {layer.name!r}: groups={gr} must divide the input channels ({cin}) "
+                                 f"and filters ({layer.attrs['filters']})")
         layer.out_shape = tuple(layer.out_shape) or self._infer_shape(layer)
         self.layers[layer.name] = layer
         self.order.append(layer.name)

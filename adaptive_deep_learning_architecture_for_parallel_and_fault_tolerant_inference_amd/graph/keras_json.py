@@ -116,8 +116,8 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
     if cls == "ZeroPadding2D":
         return Layer(name, "zeropad", inputs, {"pad": _padding2d(cfg["padding"])})
     if cls in ("Conv2D", "DepthwiseConv2D"):
-        if _pair(cfg.get("dilation_rate", 1)) != (1, 1) or cfg.get("groups", 1) != 1:
-            raise NotImplementedError(f"{name}: dilated / grouped convolution")
+        if _pair(cfg.get("dilation_rate", 1)) != (1, 1):
+            raise NotImplementedError(f"{name}: dilated convolution (dilation_rate={cfg['dilation_rate']})")
         a = {"kernel": _pair(cfg["kernel_size"]), "stride": _stride(cfg, name),
              "padding": cfg.get("padding", "valid"), "use_bias": bool(cfg.get("use_bias", True))}
         act = _activation(cfg.get("activation", "linear"), name)
@@ -127,6 +127,8 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
             a["activation"] = act
         if cls == "Conv2D":
             a["filters"] = int(cfg["filters"])
+            if int(cfg.get("groups", 1) or 1) != 1:     # the attr exists on grouped convs only
+                a["groups"] = int(cfg["groups"])
             return Layer(name, "conv", inputs, a)
         if int(cfg.get("depth_multiplier", 1)) != 1:
             raise NotImplementedError(f"{name}: depth_multiplier != 1")
@@ -251,7 +253,7 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
                    padding=a.get("padding", "valid"), data_format="channels_last", dilation_rate=[1, 1],
                    activation=a.get("activation") or "linear", use_bias=a.get("use_bias", True))
         if L.op == "conv":
-            cfg.update(filters=a["filters"], groups=1)
+            cfg.update(filters=a["filters"], groups=a.get("groups", 1))
         else:
             cfg.update(depth_multiplier=1)
     elif L.op == "bn":

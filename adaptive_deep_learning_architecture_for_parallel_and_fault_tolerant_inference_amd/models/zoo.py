@@ -13,10 +13,11 @@ takes an arbitrary Keras JSON):
 * DenseNet121/169/201 (pre-activation BN-ReLU, Concatenate, AveragePooling2D)
 * EfficientNetB0-B7   (Rescaling/Normalization inside the model, swish, squeeze-excite Multiply)
 * InceptionV3         (BatchNormalization(scale=False), asymmetric 1x7 / 7x1 kernels, multi-branch concats)
+* ResNeXt-50 / -101 (32x4d)  (Conv2D(groups=32) 3x3 in every block, ResNet layer names)
 
 Parameter totals (Keras, include_top, 1000 classes; checked by tests):
 VGG16 138,357,544; VGG19 143,667,240; MobileNetV2 3,538,984; DenseNet121 8,062,504;
-EfficientNetB0 5,330,571; InceptionV3 23,851,784.
+EfficientNetB0 5,330,571; InceptionV3 23,851,784; ResNeXt50 25,097,128; ResNeXt101 44,315,560.
 """
 from __future__ import annotations
 
@@ -305,6 +306,48 @@ def build_inception_v3(name: str = "inception_v3", classes: int = 1000, input_sh
     return g
 
 
+# ----------------------------------------------------------------- ResNeXt
+RESNEXT_STACKS = {"resnext50_32x4d": (3, 4, 6, 3), "resnext101_32x4d": (3, 4, 23, 3),
+                  "resnext_tiny": (1, 1, 1, 1)}     # tiny: same naming/structure, for fast tests
+RESNEXT_EPS = 1.001e-5
+
+
+def build_resnext(name: str = "resnext50_32x4d", classes: int = 1000, input_shape=(224, 224, 3),
+                  groups: int = 32) -> Graph:
+    """Keras' ResNeXt (`block3` / `stack3` of keras.applications.resnet) with the ResNet layer names of
+    models/resnet.py: 1x1 (w) -> ZeroPadding2D + grouped 3x3 (w, stride s) -> 1x1 (2w), projection
+    shortcut on block 1, no conv bias."""
+    g = Graph(name)
+    x = g.add(Layer("input_1", "input", [], {"shape": tuple(input_shape)}))
+    x = g.add(Layer("conv1_pad", "zeropad", [x], {"pad": ((3, 3), (3, 3))}))
+    x = _conv(g, x, "conv1_conv", 64, 7, stride=2, use_bias=False)
+    x = g.add(Layer("conv1_bn", "bn", [x], {"epsilon": RESNEXT_EPS}))
+    x = g.add(Layer("conv1_relu", "relu", [x]))
+    x = g.add(Layer("pool1_pad", "zeropad", [x], {"pad": ((1, 1), (1, 1))}))
+    x = g.add(Layer("pool1_pool", "maxpool", [x], {"pool": 3, "stride": 2, "padding": "valid"}))
+
+    def bn(x: str, nm: str) -> str:
+        return g.add(Layer(nm, "bn", [x], {"epsilon": RESNEXT_EPS}))
+
+    for s, (w, blocks) in enumerate(zip((128, 256, 512, 1024), RESNEXT_STACKS[name]), start=2):
+        for b in range(1, blocks + 1):
+            nm = f"conv{s}_block{b}"
+            stride = 2 if (b == 1 and s > 2) else 1
+            sc = bn(_conv(g, x, f"{nm}_0_conv", 2 * w, 1, stride=stride, use_bias=False), f"{nm}_0_bn") if b == 1 else x
+            y = g.add(Layer(f"{nm}_1_relu", "relu", [bn(_conv(g, x, f"{nm}_1_conv", w, 1, use_bias=False), f"{nm}_1_bn")]))
+            y = g.add(Layer(f"{nm}_2_pad", "zeropad", [y], {"pad": ((1, 1), (1, 1))}))
+            y = g.add(Layer(f"{nm}_2_conv", "conv", [y], {"filters": w, "kernel": (3, 3), "stride": stride,
+                                                         "padding": "valid", "use_bias": False, "groups": groups}))
+            y = g.add(Layer(f"{nm}_2_relu", "relu", [bn(y, f"{nm}_2_bn")]))
+            y = bn(_conv(g, y, f"{nm}_3_conv", 2 * w, 1, use_bias=False), f"{nm}_3_bn")
+            y = g.add(Layer(f"{nm}_add", "add", [sc, y]))
+            x = g.add(Layer(f"{nm}_out", "relu", [y]))
+    x = g.add(Layer("avg_pool", "gap", [x]))
+    g.add(Layer("predictions", "dense", [x], {"units": classes, "activation": "softmax", "use_bias": True}))
+    g.output_names = ["predictions"]
+    return g
+
+
 BUILDERS: Dict[str, Callable[..., Graph]] = {
     "vgg16": lambda **kw: build_vgg("vgg16", **kw),
     "vgg19": lambda **kw: build_vgg("vgg19", **kw),
@@ -314,6 +357,7 @@ BUILDERS: Dict[str, Callable[..., Graph]] = {
     "densenet201": lambda **kw: build_densenet("densenet201", **kw),
     **{n: (lambda n: lambda **kw: build_efficientnet(n, **kw))(n) for n in EFFNET_SCALE},
     "inception_v3": lambda **kw: build_inception_v3(**kw),
+    **{n: (lambda n: lambda **kw: build_resnext(n, **kw))(n) for n in RESNEXT_STACKS},
 }
 
 

@@ -1205,3 +1205,100 @@ def pair_forward(x: torch.Tensor, res: torch.Tensor, pp: PackedPair, y: torch.Te
     kernels().pw_pair_forward(ptr(x), ptr(pp.w3), ptr(pp.b3), ptr(res), ptr(pp.w1), ptr(pp.b1), ptr(y), ptr(z),
                               M, pp.cin, pp.co, pp.cm, bm, stream_handle(stream))
     return y, z
+
+
+# ------------------------------------------------------------------ grouped convolution (fp32)
+GCONV_MFMA_CG = (4, 8, 16, 32)        # channels per group the MFMA path of csrc/kernels/gconv_f32.hip takes
+GCONV_MAX_TAPS = 256                  # its smallest tile (one output pixel) stages kh x kw halo pixels in LDS
+
+
+def gconv_path(cin: int, cout: int, groups: int, kh: int = 3, kw: int = 3) -> str:
+    """Which kernel of gconv_f32.hip runs a grouped conv: "mfma" when the per-group widths are equal
+    (Cin/G == Cout/G == CG), CG is 4, 8, 16 or 32 and Cout % 16 == 0; "generic" for every other legal
+    `groups`.  A static shape rule (no device needed); the launcher re-checks it."""
+    if groups < 1 or cin % groups or cout % groups:
+        raise ValueError(f"groups={groups} must divide the input ({cin}) and output ({cout}) channels")
+    ok = cin == cout and cin // groups in GCONV_MFMA_CG and cout % 16 == 0 and kh * kw <= GCONV_MAX_TAPS
+    return "mfma" if ok else "generic"
+
+
+@dataclass
+class PackedGconv:
+    """Device-resident weights of one (BN-folded) grouped conv, packed for `path`."""
+    w: torch.Tensor          # mfma: [Cout/16][taps][chunks][64 lanes][4] fp32; generic: [kh][kw][Cin/G][Cout]
+    bias: torch.Tensor       # [Cout] fp32
+    kh: int
+    kw: int
+    cin: int
+    cout: int
+    groups: int
+    stride: int
+    pad_t: int
+    pad_l: int
+    pad_b: int
+    pad_r: int
+    path: str
+
+    def out_hw(self, h: int, w: int):
+        oh = (h + self.pad_t + self.pad_b - self.kh) // self.stride + 1
+        ow = (w + self.pad_l + self.pad_r - self.kw) // self.stride + 1
+        return oh, ow
+
+
+def gconv_fragments_np(kernel: np.ndarray, groups: int) -> np.ndarray:
+    """Grouped kernel (kh, kw, CG, Cout), CG == Cout / groups -> the MFMA path's weights.
+
+    N tile t (output channels 16t .. 16t+15) multiplies the contiguous input channels of the group(s) it
+    covers: 16 channels from 16t for CG <= 16 (off-group entries zero for CG 4 / 8), the group's 32 for
+    CG = 32, in chunks of 16.  Per tile, tap and chunk one A fragment set of v_mfma_f32_16x16x4_f32:
+    lane (fr = output channel, fq) holds, for k-step s = 0..3, the weight of input channel 4 fq + s of
+    the chunk -- the channel the kernel's 16-byte activation read puts in the same slot."""
+    kh, kw, cg, cout = kernel.shape
+    taps, nj = kh * kw, (2 if cg == 32 else 1)
+    k = np.asarray(kernel, np.float32).reshape(taps, cg, cout)
+    dense = np.zeros((cout // 16, taps, nj * 16, 16), np.float32)      # [tile][tap][channel in range][o]
+    for n in range(cout):
+        t, o = divmod(n, 16)
+        cbase = (16 * t) // (nj * 16) * (nj * 16)
+        lo = (n // cg) * cg - cbase
+        dense[t, :, lo:lo + cg, o] = k[:, :, n]
+    # [tile][tap][chunk][fq][s][o] -> [tile][tap][chunk][fq][o][s]: lane = 16 fq + o
+    d = dense.reshape(cout // 16, taps, nj, 4, 4, 16).transpose(0, 1, 2, 3, 5, 4)
+    return np.ascontiguousarray(d).reshape(cout // 16, taps, nj, 64, 4)
+
+
+def pack_gconv_f32(kernel: np.ndarray, bias: np.ndarray, groups: int, stride: int, pads, device) -> PackedGconv:
+    """kernel: Keras' grouped layout (kh, kw, Cin / groups, Cout), BN already folded."""
+    kh, kw, cgi, cout = kernel.shape
+    cin = cgi * groups
+    path = gconv_path(cin, cout, groups, kh, kw)
+    if stride not in (1, 2):
+        raise ValueError(f"grouped conv: stride {stride} (1 or 2)")
+    w = gconv_fragments_np(kernel, groups) if path == "mfma" else np.ascontiguousarray(kernel, np.float32)
+    (pt, pb), (pl, pr) = pads
+    return PackedGconv(w=torch.from_numpy(w).to(device=device).contiguous(),
+                       bias=torch.from_numpy(np.ascontiguousarray(bias, np.float32)).to(device),
+                       kh=kh, kw=kw, cin=cin, cout=cout, groups=groups, stride=int(stride),
+                       pad_t=int(pt), pad_l=int(pl), pad_b=int(pb), pad_r=int(pr), path=path)
+
+
+def gconv_forward_f32(x: torch.Tensor, pg: PackedGconv, out: torch.Tensor, relu: int = 0, stream=None) -> torch.Tensor:
+    """Grouped conv: x [B,H,W,Cin] fp32 -> out [B,OH,OW,Cout] fp32 = act(gconv(x) + bias), act 0 / 1 (ReLU) /
+    2 (ReLU6).  One launch on `stream`, no workspace; the path is the one the weights were packed for."""
+    for t, nm in ((x, "x"), (out, "out")):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"grouped conv: {nm} must be contiguous fp32")
+    if x.dim() != 4 or x.shape[3] != pg.cin:
+        raise ValueError(f"grouped conv expects [B,H,W,{pg.cin}] input, got {tuple(x.shape)}")
+    B, H, W, _ = x.shape
+    OH, OW = pg.out_hw(H, W)
+    if OH < 1 or OW < 1 or tuple(out.shape) != (B, OH, OW, pg.cout):
+        raise ValueError(f"grouped conv output must be {(B, OH, OW, pg.cout)}, got {tuple(out.shape)}")
+    if int(relu) not in (0, 1, 2):
+        raise ValueError("grouped conv activation must be 0 (none), 1 (ReLU) or 2 (ReLU6)")
+    if pg.w.device != x.device or pg.bias.numel() != pg.cout:
+        raise ValueError("grouped conv: weights on another device / bias size")
+    kernels().gconv_f32_forward(ptr(x), ptr(pg.w), ptr(pg.bias), ptr(out), B, H, W, pg.cin, OH, OW, pg.cout,
+                                pg.groups, pg.kh, pg.kw, pg.stride, pg.pad_t, pg.pad_l, int(relu),
+                                pg.path == "mfma", stream_handle(stream))
+    return out

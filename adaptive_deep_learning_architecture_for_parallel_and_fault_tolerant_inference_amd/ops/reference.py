@@ -83,7 +83,7 @@ class ReferenceExecutor:
             s = a.get("stride", 1)
             if a.get("padding", "valid") == "same":
                 x = _same(x, *a["kernel"], s)
-            y = F.conv2d(x, k, bias, stride=s)
+            y = F.conv2d(x, k, bias, stride=s, groups=a.get("groups", 1))
             return _act(y.permute(0, 2, 3, 1), a.get("activation"), a.get("alpha", 0.3))
         if L.op == "dwconv":
             x = ins[0].permute(0, 3, 1, 2)

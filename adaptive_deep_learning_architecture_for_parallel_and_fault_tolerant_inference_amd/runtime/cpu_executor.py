@@ -54,7 +54,7 @@ def _pad_cout(k: np.ndarray, cob: int) -> np.ndarray:
 class CpuExecutor:
     """Runs one (sub)graph on the host CPU with the native `_cpu` ops (fp32)."""
 
-    KINDS = ("conv", "dwconv", "maxpool", "avgpool", "bn", "add", "relu", "act", "binary", "affine", "gmp", "copy",
+    KINDS = ("conv", "gconv", "dwconv", "maxpool", "avgpool", "bn", "add", "relu", "act", "binary", "affine", "gmp", "copy",
              "concat", "gap", "dense", "softmax", "pad")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], outputs: Optional[Sequence[str]] = None):
@@ -88,6 +88,9 @@ class CpuExecutor:
             if st.kind == "conv":
                 k, b = self._folded(weights, st.p)
                 self.packed[i] = (_pad_cout(k, cob), np.ascontiguousarray(b, np.float32))
+            elif st.kind == "gconv":                # Keras' grouped layout (kh, kw, cin / groups, cout) as it is
+                k, b = self._folded(weights, st.p)
+                self.packed[i] = (np.ascontiguousarray(k, np.float32), np.ascontiguousarray(b, np.float32))
             elif st.kind == "dense":
                 name = st.p.get("layer", st.out)
                 k = np.asarray(weights[f"{name}/kernel"], np.float32)
@@ -138,6 +141,10 @@ class CpuExecutor:
                 ins[0] = ins[0].reshape((batch,) + tuple(self.g.layers[self.g.layers[p["conv"]].inputs[0]].out_shape))
             m.conv2d(ins[0], w, b, y, int(p["stride"]), int(pt), int(pl), int(p["relu"]), 0.3,
                      ins[1] if p.get("residual") else None)
+        elif k == "gconv":
+            w, b = self.packed[i]
+            (pt, _), (pl, _) = p["pads"]
+            m.gconv2d(ins[0], w, b, y, int(p["stride"]), int(pt), int(pl), int(p["groups"]), int(p["relu"]), 0.3)
         elif k == "dwconv":
             w, b = self.packed[i]
             (pt, _), (pl, _) = p["pads"]

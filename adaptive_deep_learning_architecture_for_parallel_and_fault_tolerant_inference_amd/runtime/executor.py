@@ -78,7 +78,7 @@ class SliceExecutor:
     """Runs one (sub)graph for a fixed batch on one device with our HIP kernels."""
 
     FP32_KINDS = ("conv", "pair", "dense", "maxpool", "gap", "softmax", "add", "bn", "relu", "pad", "copy",
-                  "dwconv", "avgpool", "concat", "act", "binary", "affine", "stem_f32")
+                  "dwconv", "avgpool", "concat", "act", "binary", "affine", "stem_f32", "gconv")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], batch: int, device="cuda",
                  outputs: Optional[Sequence[str]] = None, tune: bool = False, num_sets: int = 1,
@@ -102,6 +102,11 @@ class SliceExecutor:
         self.precision = precision
         self.fp32 = precision == "fp32"
         self.steps: List[Step] = compile_plan(g, self.outputs, fp32=self.fp32)
+        if not self.fp32:
+            grouped = [st.p["conv"] for st in self.steps if st.kind == "gconv"]
+            if grouped:
+                raise NotImplementedError(f"bf16 execution has no grouped-convolution kernel ({grouped[0]}, model "
+                                          f"{g.name}); precision=\"fp32\" supports Conv2D(groups > 1)")
         if self.fp32:
             bad = sorted({st.kind for st in self.steps if st.kind not in self.FP32_KINDS})
             if bad:
@@ -245,6 +250,9 @@ class SliceExecutor:
             elif st.kind == "stem_f32":
                 kf, bf = self._folded(weights, st.p)
                 self.packed[i] = conv_ops.pack_stem_f32(kf, bf, st.p["pads"], dev)
+            elif st.kind == "gconv":
+                kf, bf = self._folded(weights, st.p)      # BN scales the last (output channel) axis
+                self.packed[i] = conv_ops.pack_gconv_f32(kf, bf, st.p["groups"], st.p["stride"], st.p["pads"], dev)
             elif st.kind == "pair":
                 k3, b3 = self._folded(weights, st.p["c3"])
                 k1, b1 = self._folded(weights, st.p["c1"])
@@ -970,6 +978,8 @@ class SliceExecutor:
             w, bias = self.packed[i]
             E.dwconv_f32(b[st.ins[0]], w, bias, b[st.out], st.p["stride"], st.p["pads"], act=st.p["relu"],
                          stream=stream)
+        elif k == "gconv":
+            conv_ops.gconv_forward_f32(b[st.ins[0]], self.packed[i], b[st.out], relu=st.p["relu"], stream=stream)
         elif k == "avgpool":
             E.avgpool_f32(b[st.ins[0]], b[st.out], st.p["pool"], st.p["stride"], st.p["pads"], stream=stream)
         elif k == "concat":

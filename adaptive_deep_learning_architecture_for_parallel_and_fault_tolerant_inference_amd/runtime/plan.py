@@ -12,6 +12,9 @@ kernels:
 * ``maxpool``  [ZeroPadding2D +] MaxPooling2D ('same' padding excluded from the max)
 * ``avgpool``  AveragePooling2D (padding excluded from the mean)
 * ``dwconv``   DepthwiseConv2D [+BN folded] [+ReLU/ReLU6], explicit pads
+* ``gconv``    Conv2D(groups > 1) [+BN folded] [+ReLU/ReLU6], explicit pads; no
+               residual fusion, and a kind of its own so that no pass written
+               for dense convs (pair, siblings, stem, bottleneck) ever sees it
 * ``concat``   Concatenate along channels (one copy launch per input)
 * ``copy``     a Flatten/Dropout that the slice emits under its own name
                (otherwise they alias their input: Dropout everywhere,
@@ -152,6 +155,7 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
             res = None
             out = n
             post_act = 0                        # an activation the MFMA epilogue does not take (swish, ...)
+            grouped = L.op == "conv" and a.get("groups", 1) > 1
             if own_act(n, L):
                 relu = own_act(n, L)            # Conv2D(activation=...): nothing after it fuses
                 if L.op == "conv" and relu > 2:
@@ -172,7 +176,7 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                         relu = act_mode(c2)
                         cover.append(c2)
                         out = c2
-                    elif (L.op == "conv" and c2 is not None and g.layers[c2].op == "add"
+                    elif (L.op == "conv" and not grouped and c2 is not None and g.layers[c2].op == "add"
                           and len(g.layers[c2].inputs) == 2):
                         other = [i for i in g.layers[c2].inputs if i != feed]
                         if len(other) == 1 and alias.get(other[0], other[0]) in produced:
@@ -193,6 +197,13 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                 steps.append(Step("dwconv", out, [R(src)], cover,
                                   {"conv": n, "bn": bn, "relu": relu, "pads": pads, "stride": a.get("stride", 1),
                                    "kernel": kernel}))
+            elif grouped:
+                cv_out = out if not post_act else n + "#preact"
+                steps.append(Step("gconv", cv_out, [R(src)], cover,
+                                  {"conv": n, "bn": bn, "relu": relu, "pads": pads, "stride": a.get("stride", 1),
+                                   "kernel": kernel, "filters": a["filters"], "groups": a["groups"]}))
+                if post_act:
+                    steps.append(Step("act", out, [cv_out], [], {"mode": post_act, "alpha": 0.3}))
             else:
                 cv_out = out if not post_act else n + "#preact"
                 steps.append(Step("conv", cv_out, [R(src)] + ([res] if res else []), cover,

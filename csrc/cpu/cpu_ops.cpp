@@ -178,6 +178,60 @@ void conv2d(const Arr<float>& x, const Arr<float>& w, const Arr<float>& bias, Ar
   }
 }
 
+// ------------------------------------------------------------------ grouped conv
+// Keras Conv2D(groups = G): output channel o reads the C / G input channels of
+// group o / (CO / G).  A task owns one output row of one group and accumulates
+// CO / G sums per pixel over (kh, kw, ci) with the filter row contiguous in cout.
+// x [N,H,W,C]; w [KH,KW,C/G,CO]; bias [CO]; y [N,OH,OW,CO]
+ADAPT_CLONES
+void gconv_row(const float* __restrict x, const float* __restrict w, const float* __restrict b, float* __restrict y,
+               int n, int oh, int g, int H, int W, int C, int OH, int OW, int CO, int G, int KH, int KW, int S, int PT,
+               int PL, int act, float alpha) {
+  const int cgi = C / G, cgo = CO / G;
+  std::vector<float> accv(cgo);
+  float* a = accv.data();
+  const float* bg = b + g * cgo;
+  for (int ow = 0; ow < OW; ++ow) {
+    std::copy(bg, bg + cgo, a);
+    for (int kh = 0; kh < KH; ++kh) {
+      const int ih = oh * S - PT + kh;
+      if (ih < 0 || ih >= H) continue;
+      for (int kw = 0; kw < KW; ++kw) {
+        const int iw = ow * S - PL + kw;
+        if (iw < 0 || iw >= W) continue;
+        const float* xv = x + (((size_t)n * H + ih) * W + iw) * C + (size_t)g * cgi;
+        const float* wr = w + ((size_t)(kh * KW + kw) * cgi) * CO + (size_t)g * cgo;
+        for (int ci = 0; ci < cgi; ++ci) {
+          const float xc = xv[ci];
+          const float* wv = wr + (size_t)ci * CO;
+#pragma omp simd
+          for (int j = 0; j < cgo; ++j) a[j] += xc * wv[j];
+        }
+      }
+    }
+    float* yo = y + (((size_t)n * OH + oh) * OW + ow) * CO + (size_t)g * cgo;
+    for (int j = 0; j < cgo; ++j) yo[j] = act_f(a[j], act, alpha);
+  }
+}
+
+void gconv2d(const Arr<float>& x, const Arr<float>& w, const Arr<float>& bias, Arr<float>& y, int stride, int pad_t,
+             int pad_l, int groups, int act, float alpha) {
+  need(x.ndim() == 4 && w.ndim() == 4 && y.ndim() == 4 && bias.ndim() == 1, "gconv2d ranks");
+  const int N = x.shape(0), H = x.shape(1), W = x.shape(2), C = x.shape(3), OH = y.shape(1), OW = y.shape(2),
+            CO = y.shape(3), KH = w.shape(0), KW = w.shape(1);
+  need(groups >= 1 && C % groups == 0 && CO % groups == 0 && w.shape(2) == C / groups && w.shape(3) == CO &&
+           y.shape(0) == N && bias.shape(0) == CO && stride >= 1,
+       "gconv2d shapes");
+  const float *xp = cptr(x), *wp = cptr(w), *bp = cptr(bias);
+  float* yp = mptr(y);
+  py::gil_scoped_release nogil;
+#pragma omp parallel for collapse(3) schedule(static)
+  for (int n = 0; n < N; ++n)
+    for (int oh = 0; oh < OH; ++oh)
+      for (int g = 0; g < groups; ++g)
+        gconv_row(xp, wp, bp, yp, n, oh, g, H, W, C, OH, OW, CO, groups, KH, KW, stride, pad_t, pad_l, act, alpha);
+}
+
 // ------------------------------------------------------------------ depthwise
 // x [N,H,W,C]; w [KH,KW,C]; bias [C]; y [N,OH,OW,C]
 ADAPT_CLONES
@@ -416,6 +470,8 @@ PYBIND11_MODULE(_cpu, m) {
   m.def("conv2d", &conv2d, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("stride"),
         py::arg("pad_t"), py::arg("pad_l"), py::arg("act") = 0, py::arg("alpha") = 0.3f,
         py::arg("residual") = py::none());
+  m.def("gconv2d", &gconv2d, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("stride"),
+        py::arg("pad_t"), py::arg("pad_l"), py::arg("groups"), py::arg("act") = 0, py::arg("alpha") = 0.3f);
   m.def("dwconv2d", &dwconv2d, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("stride"),
         py::arg("pad_t"), py::arg("pad_l"), py::arg("act") = 0, py::arg("alpha") = 0.3f);
   m.def("pool2d", &pool2d, py::arg("x"), py::arg("y"), py::arg("kind"), py::arg("kh"), py::arg("kw"),

@@ -386,6 +386,13 @@ PYBIND11_MODULE(_C, m) {
     check(adapt::dwconv_f32(P<const float>(x), P<const float>(w), P<const float>(b), P<float>(y), B, H, W, C, OH, OW,
                             KH, KW, Sd, pt, pl, act, alpha, S(s)), "dwconv_f32");
   });
+  m.def("gconv_f32_mfma_ok", &adapt::gconv_f32_mfma_ok);
+  m.def("gconv_f32_forward", [](u64 x, u64 w, u64 b, u64 y, int B, int H, int W, int Cin, int OH, int OW, int Cout,
+                                int G, int KH, int KW, int Sd, int pt, int pl, int act, bool mfma, u64 s) {
+    adapt::GconvF32Params p{P<const float>(x), P<const float>(w), P<const float>(b), P<float>(y), B, H, W, Cin, OH,
+                            OW, Cout, G, KH, KW, Sd, pt, pl, act};
+    check(adapt::gconv_f32_forward(p, mfma, S(s)), "gconv_f32_forward");
+  });
   m.def("avgpool_f32", [](u64 x, u64 y, int B, int H, int W, int C, int OH, int OW, int KH, int KW, int Sd, int pt,
                           int pl, u64 s) {
     check(adapt::avgpool_f32(P<const float>(x), P<float>(y), B, H, W, C, OH, OW, KH, KW, Sd, pt, pl, S(s)),

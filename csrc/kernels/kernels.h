@@ -330,6 +330,17 @@ hipError_t pw_res_forward(const PwParams& p, int K, int N, int pt, int blocks, h
 bool pw_slice_cfg(int code, int* cf, int* waves, int* pt);
 int pw_slice_supported(int K, int N, int code);
 hipError_t pw_slice_forward(const PwParams& p, int K, int N, int code, int blocks, hipStream_t s);
+// grouped convolution, fp32 NHWC (gconv_f32.hip): out = act(gconv(x) + bias), Keras Conv2D(groups = G)
+struct GconvF32Params {
+  const float* x;      // [B][H][W][Cin]
+  const float* w;      // MFMA path: fragment-packed [Cout/16][taps][chunks][64 lanes][4]; generic: [KH][KW][Cin/G][Cout]
+  const float* bias;   // [Cout]
+  float* out;          // [B][OH][OW][Cout]
+  int B, H, W, Cin, OH, OW, Cout, G, KH, KW, S, PT, PL, act;
+};
+bool gconv_f32_mfma_ok(int Cin, int Cout, int G);     // shape rule of the MFMA path
+// mfma: which path to launch (the caller packed w for it); an ineligible shape is an error, never a fall-through
+hipError_t gconv_f32_forward(const GconvF32Params& p, bool mfma, hipStream_t s);
 // serving ingest (ingest.hip): uint8 NHWC -> fp32, y = x[rev(c)] * scale[c] + shift[c] (host scale/shift, C <= 4)
 hipError_t ingest_u8(const uint8_t* x, float* y, size_t n, int C, int reverse, const float* scale,
                      const float* shift, hipStream_t s);

@@ -42,6 +42,8 @@ OPS = (
     "reshape",    # attrs: shape (element order unchanged: NHWC row-major)
     "rescale",    # Keras Rescaling: attrs scale, offset (scalars or per-channel lists)
     "normalization",  # Keras Normalization(axis=-1): weights mean, variance, count
+    "layernorm",  # Keras LayerNormalization over the last axis: attrs epsilon; center / scale only when False
+    "layerscale",  # ConvNeXt LayerScale: y = x * gamma (per channel); attrs init_values
 )
 
 # activations the runtime executes (fused into conv / dense / eltwise epilogues,
@@ -61,6 +63,21 @@ def bn_params(weights, name: str) -> Dict:
     return {"gamma": weights.get(f"{name}/gamma", np.ones_like(mu)),
             "beta": weights.get(f"{name}/beta", np.zeros_like(mu)),
             "moving_mean": mu, "moving_variance": weights[f"{name}/moving_variance"]}
+
+
+def depthwise_kernel(weights, name: str):
+    """(kh, kw, C) kernel of a depthwise step: a DepthwiseConv2D's `depthwise_kernel` (kh, kw, C, 1), or the
+    `kernel` (kh, kw, 1, C) of a Conv2D(groups=C) with one channel per group."""
+    if f"{name}/depthwise_kernel" in weights:
+        return weights[f"{name}/depthwise_kernel"][..., 0]
+    return weights[f"{name}/kernel"][:, :, 0, :]
+
+
+def conv_kernel(weights, p: Dict):
+    """HWIO kernel of a conv step's layer `p["conv"]`; a Dense on (H, W, C) (p["dense"]) keeps the Keras
+    (cin, units) shape in the weights and is a 1x1 kernel here."""
+    k = weights[f"{p['conv']}/kernel"]
+    return k.reshape((1, 1) + tuple(k.shape)) if p.get("dense") else k
 
 
 def same_pads(size: int, k: int, s: int) -> Tuple[int, int]:
@@ -113,6 +130,13 @@ class Layer:
         if self.op == "normalization":
             c = in_shapes[0][-1]
             return [(f"{self.name}/mean", (c,)), (f"{self.name}/variance", (c,)), (f"{self.name}/count", ())]
+        if self.op == "layernorm":
+            # Keras omits gamma for scale=False and beta for center=False, as BatchNormalization does
+            c = in_shapes[0][-1]
+            keep = (("gamma", self.attrs.get("scale", True)), ("beta", self.attrs.get("center", True)))
+            return [(f"{self.name}/{n}", (c,)) for n, k in keep if k]
+        if self.op == "layerscale":
+            return [(f"{self.name}/gamma", (in_shapes[0][-1],))]
         if self.op == "dense":
             cin = in_shapes[0][-1]
             out = [(f"{self.name}/kernel", (cin, self.attrs["units"]))]
@@ -132,7 +156,10 @@ class Layer:
             oh, ow, co = self.out_shape
             return oh * ow * co * kh * kw
         if self.op == "dense":
-            return in_shapes[0][-1] * self.attrs["units"]
+            px = 1
+            for d in in_shapes[0][:-1]:         # a Dense on (H, W, C) is a GEMM per pixel
+                px *= d
+            return px * in_shapes[0][-1] * self.attrs["units"]
         return 0
 
     def to_json(self) -> Dict:
@@ -210,7 +237,8 @@ class Graph:
             if a.get("padding", "valid") == "same":
                 return (-(-h // s), -(-w // s), co)
             return ((h - kh) // s + 1, (w - kw) // s + 1, co)
-        if layer.op in ("bn", "relu", "softmax", "identity", "act", "rescale", "normalization"):
+        if layer.op in ("bn", "relu", "softmax", "identity", "act", "rescale", "normalization", "layernorm",
+                        "layerscale"):
             return ins[0]
         if layer.op == "binary":
             return ins[0]
@@ -246,7 +274,7 @@ class Graph:
         if layer.op in ("gap", "gmp"):
             return (1, 1, ins[0][-1]) if a.get("keepdims") else (ins[0][-1],)
         if layer.op == "dense":
-            return (a["units"],)
+            return tuple(ins[0][:-1]) + (a["units"],)     # Keras Dense acts on the last axis
         raise ValueError(f"unknown op {layer.op}")
 
     # -------------------------------------------------------------- queries

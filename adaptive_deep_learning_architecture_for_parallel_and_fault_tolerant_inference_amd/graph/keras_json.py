@@ -89,6 +89,14 @@ def _activation(act, name: str):
     return act
 
 
+def _check_last_axis(axis, rank: int, name: str) -> None:
+    """LayerNormalization normalises the last axis only: -1, [-1], or that axis given positively
+    (`rank` counts the batch axis: [3] for NHWC, [1] for a (batch, C) input)."""
+    ax = list(axis) if isinstance(axis, (list, tuple)) else [axis]
+    if len(ax) != 1 or ax[0] not in (-1, rank - 1):
+        raise NotImplementedError(f"{name}: LayerNormalization over axis {axis} (only the last axis is supported)")
+
+
 def _layers_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str]) -> List[Layer]:
     """Most classes map to one IR layer; SeparableConv2D lowers to a depthwise + a pointwise conv (same
     get_weights() order: depthwise_kernel, pointwise_kernel, bias), the pointwise one keeping the Keras name."""
@@ -143,6 +151,17 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
             if not cfg.get(k, True):
                 a[k] = False
         return Layer(name, "bn", inputs, a)
+    if cls == "LayerNormalization":
+        # the axis is checked against the input's rank where that is known (from_keras_json)
+        a = {"epsilon": float(cfg.get("epsilon", 1e-3))}
+        for k in ("center", "scale"):
+            if not cfg.get(k, True):
+                a[k] = False
+        return Layer(name, "layernorm", inputs, a)
+    if cls == "LayerScale":
+        return Layer(name, "layerscale", inputs, {"init_values": float(cfg.get("init_values", 1e-6))})
+    if cls == "StochasticDepth":                       # drops whole residual branches in training only
+        return Layer(name, "identity", inputs)
     if cls == "ReLU":
         if float(cfg.get("threshold", 0.0) or 0.0) != 0.0:
             raise NotImplementedError(f"{name}: thresholded ReLU")
@@ -226,6 +245,8 @@ def from_keras_json(s) -> Graph:
         name = ld.get("name") or ld["config"]["name"]
         for layer in _layers_from_keras(ld["class_name"], ld["config"], name, _inbound_names(ld)):
             g.add(layer)
+        if ld["class_name"] == "LayerNormalization":
+            _check_last_axis(ld["config"].get("axis", -1), len(g.layers[name].out_shape) + 1, name)
 
     def names(v) -> List[str]:
         if isinstance(v, list) and v and isinstance(v[0], str):
@@ -260,6 +281,13 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
         cls = "BatchNormalization"
         cfg.update(axis=[3], momentum=0.99, epsilon=a.get("epsilon", 1e-3), center=a.get("center", True),
                    scale=a.get("scale", True))
+    elif L.op == "layernorm":
+        cls = "LayerNormalization"
+        cfg.update(axis=[-1], epsilon=a.get("epsilon", 1e-3), center=a.get("center", True),
+                   scale=a.get("scale", True))
+    elif L.op == "layerscale":
+        cls = "LayerScale"
+        cfg.update(init_values=a.get("init_values", 1e-6), projection_dim=L.out_shape[-1])
     elif L.op == "relu":
         if a.get("max_value") is None:
             cls = "Activation"

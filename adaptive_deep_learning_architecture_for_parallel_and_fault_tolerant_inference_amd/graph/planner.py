@@ -121,7 +121,7 @@ def layer_costs(g: Graph, batch: int = 32, hw: Optional[HwModel] = None) -> Dict
             continue
         macs = g.layer_macs(n) * batch
         byts = sum(g.tensor_bytes(i, hw.act_bytes) for i in L.inputs) * batch + g.tensor_bytes(n, hw.act_bytes) * batch
-        if L.op in ("bn", "relu", "zeropad"):
+        if L.op in ("bn", "relu", "zeropad", "layerscale"):
             # fused into the producing conv / pool at runtime
             out[n] = 0.0
             continue

@@ -134,6 +134,15 @@ def init_weights(g: Graph, seed: int = 0, layers: Optional[List[str]] = None) ->
                     "moving_variance": rng.uniform(0.5, 1.5, c).astype(np.float32)}
             for wname, _ in specs:                 # scale=False / center=False drop gamma / beta
                 out[wname] = vals[wname.rsplit("/", 1)[1]]
+        elif L.op == "layernorm":
+            c = g.in_shapes(n)[0][-1]
+            vals = {"gamma": rng.uniform(0.8, 1.2, c).astype(np.float32),
+                    "beta": (rng.standard_normal(c) * 0.05).astype(np.float32)}
+            for wname, _ in specs:                 # scale=False / center=False drop gamma / beta
+                out[wname] = vals[wname.rsplit("/", 1)[1]]
+        elif L.op == "layerscale":
+            # O(1), not Keras' 1e-6: with that every residual branch would vanish from the output
+            out[specs[0][0]] = rng.uniform(0.1, 0.3, specs[0][1][0]).astype(np.float32)
         elif L.op == "normalization":
             c = specs[0][1][0]
             out[specs[0][0]] = (rng.standard_normal(c) * 0.1).astype(np.float32)

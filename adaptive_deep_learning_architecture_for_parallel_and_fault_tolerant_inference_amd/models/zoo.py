@@ -14,10 +14,12 @@ takes an arbitrary Keras JSON):
 * EfficientNetB0-B7   (Rescaling/Normalization inside the model, swish, squeeze-excite Multiply)
 * InceptionV3         (BatchNormalization(scale=False), asymmetric 1x7 / 7x1 kernels, multi-branch concats)
 * ResNeXt-50 / -101 (32x4d)  (Conv2D(groups=32) 3x3 in every block, ResNet layer names)
+* ConvNeXt-Tiny ... -XLarge  (LayerNormalization, Dense on (H, W, C), LayerScale, a 7x7 Conv2D(groups=C))
 
 Parameter totals (Keras, include_top, 1000 classes; checked by tests):
 VGG16 138,357,544; VGG19 143,667,240; MobileNetV2 3,538,984; DenseNet121 8,062,504;
-EfficientNetB0 5,330,571; InceptionV3 23,851,784; ResNeXt50 25,097,128; ResNeXt101 44,315,560.
+EfficientNetB0 5,330,571; InceptionV3 23,851,784; ResNeXt50 25,097,128; ResNeXt101 44,315,560;
+ConvNeXt Tiny 28,589,128, Small 50,223,688, Base 88,591,464, Large 197,767,336, XLarge 350,196,968.
 """
 from __future__ import annotations
 
@@ -348,7 +350,58 @@ def build_resnext(name: str = "resnext50_32x4d", classes: int = 1000, input_shap
     return g
 
 
+# ---------------------------------------------------------------- ConvNeXt
+# name -> (depths, dims, default input); micro: same naming / structure, for fast tests
+CONVNEXT = {
+    "convnext_tiny": ((3, 3, 9, 3), (96, 192, 384, 768), (224, 224, 3)),
+    "convnext_small": ((3, 3, 27, 3), (96, 192, 384, 768), (224, 224, 3)),
+    "convnext_base": ((3, 3, 27, 3), (128, 256, 512, 1024), (224, 224, 3)),
+    "convnext_large": ((3, 3, 27, 3), (192, 384, 768, 1536), (224, 224, 3)),
+    "convnext_xlarge": ((3, 3, 27, 3), (256, 512, 1024, 2048), (224, 224, 3)),
+    "convnext_micro": ((1, 1, 2, 1), (24, 48, 96, 192), (64, 64, 3)),
+}
+CONVNEXT_EPS = 1e-6
+
+
+def build_convnext(name: str = "convnext_tiny", classes: int = 1000, input_shape=None) -> Graph:
+    """`keras.applications.convnext` (include_top=True, no preprocessing layer) as flat layers: Keras nests
+    the stem and the downsampling blocks in `Sequential` sub-models and adds the residual with a
+    `TFOpLambda`; here they are plain layers and an `Add`, in the same order, so the flat `get_weights()`
+    list is the same.  The 7x7 depthwise layer is Keras' `Conv2D(groups=C)` with kernel (7, 7, 1, C), the
+    two pointwise layers are `Dense` on (H, W, C)."""
+    depths, dims, default_shape = CONVNEXT[name]
+    g = Graph(name)
+    x = g.add(Layer("input_1", "input", [], {"shape": tuple(input_shape or default_shape)}))
+
+    def ln(x: str, nm: str) -> str:
+        return g.add(Layer(nm, "layernorm", [x], {"epsilon": CONVNEXT_EPS}))
+
+    x = ln(_conv(g, x, f"{name}_stem_conv", dims[0], 4, stride=4), f"{name}_stem_layernorm")
+    for i, (depth, c) in enumerate(zip(depths, dims)):
+        if i:
+            x = _conv(g, ln(x, f"{name}_downsampling_layernorm_{i - 1}"), f"{name}_downsampling_conv_{i - 1}", c, 2,
+                      stride=2)
+        for j in range(depth):
+            nm = f"{name}_stage_{i}_block_{j}"
+            y = g.add(Layer(f"{nm}_depthwise_conv", "conv", [x],
+                            {"filters": c, "kernel": (7, 7), "stride": 1, "padding": "same", "use_bias": True,
+                             "groups": c}))
+            y = ln(y, f"{nm}_layernorm")
+            y = g.add(Layer(f"{nm}_pointwise_conv_1", "dense", [y], {"units": 4 * c, "use_bias": True}))
+            y = g.add(Layer(f"{nm}_gelu", "act", [y], {"fn": "gelu"}))
+            y = g.add(Layer(f"{nm}_pointwise_conv_2", "dense", [y], {"units": c, "use_bias": True}))
+            y = g.add(Layer(f"{nm}_layer_scale", "layerscale", [y], {"init_values": 1e-6}))
+            y = g.add(Layer(f"{nm}_identity", "identity", [y]))
+            x = g.add(Layer(f"{nm}_add", "add", [x, y]))
+    x = g.add(Layer("avg_pool", "gap", [x]))
+    x = ln(x, f"{name}_head_layernorm")
+    g.add(Layer(f"{name}_head_dense", "dense", [x], {"units": classes, "activation": "softmax", "use_bias": True}))
+    g.output_names = [f"{name}_head_dense"]
+    return g
+
+
 BUILDERS: Dict[str, Callable[..., Graph]] = {
+    **{n: (lambda n: lambda **kw: build_convnext(n, **kw))(n) for n in CONVNEXT},
     "vgg16": lambda **kw: build_vgg("vgg16", **kw),
     "vgg19": lambda **kw: build_vgg("vgg19", **kw),
     "mobilenet_v2": lambda **kw: build_mobilenet_v2(**kw),

@@ -79,8 +79,10 @@ def cfg_supported(cfg: int, pc: "PackedConv", pure: bool) -> bool:
 NUM_CUS = 256
 
 
-def fold_bn(kernel_hwio: np.ndarray, bias: Optional[np.ndarray], bn: Optional[dict], eps: float = 1.001e-5):
-    """Fold inference BN into conv weights: returns (kernel_hwio, bias) fp32."""
+def fold_bn(kernel_hwio: np.ndarray, bias: Optional[np.ndarray], bn: Optional[dict], eps: float = 1.001e-5,
+            scale: Optional[np.ndarray] = None):
+    """Fold inference BN into conv weights: returns (kernel_hwio, bias) fp32.  `scale`: a per-output-channel
+    factor applied after the conv (LayerScale's gamma), folded the same way."""
     k = kernel_hwio.astype(np.float64)
     cout = k.shape[-1]
     b = np.zeros(cout) if bias is None else bias.astype(np.float64)
@@ -88,6 +90,9 @@ def fold_bn(kernel_hwio: np.ndarray, bias: Optional[np.ndarray], bn: Optional[di
         s = bn["gamma"].astype(np.float64) / np.sqrt(bn["moving_variance"].astype(np.float64) + eps)
         k = k * s
         b = (b - bn["moving_mean"]) * s + bn["beta"]
+    if scale is not None:
+        k = k * scale.astype(np.float64)
+        b = b * scale.astype(np.float64)
     return k.astype(np.float32), b.astype(np.float32)
 
 

@@ -362,6 +362,34 @@ def dwconv_f32(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.
     return out
 
 
+def layernorm_f32(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: torch.Tensor, eps: float,
+                  stream=None) -> torch.Tensor:
+    """fp32 LayerNormalization over the last axis (csrc/kernels/layernorm.hip): x [..., C], gamma / beta [C]."""
+    _chk(x, torch.float32, "x"); _chk(out, torch.float32, "out")
+    _chk(gamma, torch.float32, "gamma"); _chk(beta, torch.float32, "beta")
+    C = x.shape[-1]
+    if out.shape != x.shape or gamma.numel() != C or beta.numel() != C or x.numel() == 0 or x.numel() // C >= 2 ** 31:
+        raise ValueError(f"layernorm_f32: bad shapes x{tuple(x.shape)} out{tuple(out.shape)} gamma{tuple(gamma.shape)}")
+    kernels().layernorm_f32(ptr(x), ptr(gamma), ptr(beta), ptr(out), x.numel() // C, C, float(eps),
+                            stream_handle(stream))
+    return out
+
+
+def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: torch.Tensor, C: int, eps: float,
+              stream=None) -> torch.Tensor:
+    """bf16 LayerNormalization over the first C of the Cp stored channels: x [..., Cp], gamma / beta fp32 [Cp].
+    Channels C..Cp-1 are layout padding: out of the statistics whatever they hold, zeros in `out`."""
+    _chk(x, name="x"); _chk(out, name="out")
+    _chk(gamma, torch.float32, "gamma"); _chk(beta, torch.float32, "beta")
+    Cp = x.shape[-1]
+    if (out.shape != x.shape or gamma.numel() != Cp or beta.numel() != Cp or Cp % 8 or not 0 < C <= Cp
+            or x.numel() == 0 or x.numel() // Cp >= 2 ** 31):
+        raise ValueError(f"layernorm: bad shapes x{tuple(x.shape)} out{tuple(out.shape)} gamma{tuple(gamma.shape)} C={C}")
+    kernels().layernorm(ptr(x), ptr(gamma), ptr(beta), ptr(out), x.numel() // Cp, Cp, int(C), float(eps),
+                        stream_handle(stream))
+    return out
+
+
 def avgpool_f32(x: torch.Tensor, out: torch.Tensor, k, s: int, pads=((0, 0), (0, 0)), stream=None) -> torch.Tensor:
     _chk(x, torch.float32, "x"); _chk(out, torch.float32, "out")
     kh, kw = (k, k) if isinstance(k, int) else k

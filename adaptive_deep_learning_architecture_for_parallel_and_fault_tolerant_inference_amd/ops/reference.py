@@ -100,6 +100,12 @@ class ReferenceExecutor:
             g_ = self.w.get(f"{L.name}/gamma", 1.0)         # scale=False / center=False defaults
             b_ = self.w.get(f"{L.name}/beta", 0.0)
             return (ins[0] - m_) / torch.sqrt(v_ + a.get("epsilon", 1e-3)) * g_ + b_
+        if L.op == "layernorm":
+            c = ins[0].shape[-1]
+            return F.layer_norm(ins[0], (c,), self.w.get(f"{L.name}/gamma"), self.w.get(f"{L.name}/beta"),
+                                a.get("epsilon", 1e-3))
+        if L.op == "layerscale":
+            return ins[0] * self.w[f"{L.name}/gamma"]
         if L.op == "relu":
             y = torch.relu(ins[0])
             return y if a.get("max_value") is None else torch.clamp(y, max=float(a["max_value"]))

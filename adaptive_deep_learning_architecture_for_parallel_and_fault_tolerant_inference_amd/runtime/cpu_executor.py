@@ -20,7 +20,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from ..graph.ir import Graph, bn_params
+from ..graph.ir import Graph, bn_params, conv_kernel, depthwise_kernel
 from ..ops.conv import fold_bn
 from .plan import Step, compile_plan
 
@@ -55,7 +55,7 @@ class CpuExecutor:
     """Runs one (sub)graph on the host CPU with the native `_cpu` ops (fp32)."""
 
     KINDS = ("conv", "gconv", "dwconv", "maxpool", "avgpool", "bn", "add", "relu", "act", "binary", "affine", "gmp", "copy",
-             "concat", "gap", "dense", "softmax", "pad")
+             "concat", "gap", "dense", "softmax", "pad", "layernorm")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], outputs: Optional[Sequence[str]] = None):
         self.g = g
@@ -79,7 +79,8 @@ class CpuExecutor:
         if p.get("bn"):
             bn = bn_params(weights, p["bn"])
             eps = self.g.layers[p["bn"]].attrs.get("epsilon", 1e-3)
-        return fold_bn(weights[f"{p['conv']}/kernel"], weights.get(f"{p['conv']}/bias"), bn, eps)
+        return fold_bn(conv_kernel(weights, p), weights.get(f"{p['conv']}/bias"), bn, eps,
+                       scale=weights[f"{p['scale']}/gamma"] if p.get("scale") else None)
 
     def _pack(self, weights: Dict[str, np.ndarray]) -> None:
         cob = int(self.mod.COB)
@@ -98,7 +99,7 @@ class CpuExecutor:
                 self.packed[i] = (_pad_cout(k.reshape(1, 1, *k.shape), cob), np.ascontiguousarray(b))
             elif st.kind == "dwconv":
                 p = st.p
-                k = weights[f"{p['conv']}/depthwise_kernel"][..., 0]          # (kh, kw, C), multiplier 1
+                k = depthwise_kernel(weights, p["conv"])                      # (kh, kw, C), multiplier 1
                 bn, eps = None, 1e-3
                 if p["bn"]:
                     bn = bn_params(weights, p["bn"])
@@ -112,12 +113,18 @@ class CpuExecutor:
                 eps = self.g.layers[st.p["bn"]].attrs.get("epsilon", 1e-3)
                 sc = gm / np.sqrt(var + eps)
                 self.packed[i] = (sc.astype(np.float32), (bt - mu * sc).astype(np.float32))
+            elif st.kind == "layernorm":         # Keras' defaults for scale=False / center=False
+                c = self.g.layers[st.p["layer"]].out_shape[-1]
+                self.packed[i] = tuple(np.ascontiguousarray(weights.get(f"{st.p['layer']}/{w}", d), np.float32)
+                                       for w, d in (("gamma", np.ones(c)), ("beta", np.zeros(c))))
             elif st.kind == "affine":            # Keras Rescaling / Normalization: y = x * scale + shift
                 L = self.g.layers[st.p["layer"]]
                 c = L.out_shape[-1]
                 if L.op == "rescale":
                     sc = np.broadcast_to(np.asarray(L.attrs.get("scale", 1.0), np.float64), (c,))
                     sh = np.broadcast_to(np.asarray(L.attrs.get("offset", 0.0), np.float64), (c,))
+                elif L.op == "layerscale":
+                    sc, sh = weights[f"{L.name}/gamma"].astype(np.float64), np.zeros(c)
                 else:
                     mu = weights[f"{L.name}/mean"].astype(np.float64)
                     sd = np.maximum(np.sqrt(weights[f"{L.name}/variance"].astype(np.float64)), 1e-7)
@@ -157,6 +164,9 @@ class CpuExecutor:
         elif k in ("bn", "affine"):
             sc, sh = self.packed[i]
             m.affine(ins[0], sc, sh, y, int(p.get("relu", 0)), 0.3)
+        elif k == "layernorm":
+            gm, bt = self.packed[i]
+            m.layernorm(ins[0], gm, bt, y, float(p["eps"]))
         elif k == "add":
             m.binary(ins[0], ins[1], y, 0, int(p["relu"]), 0.3)
         elif k == "relu":

@@ -30,7 +30,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ..graph.ir import Graph, bn_params
+from ..graph.ir import Graph, bn_params, conv_kernel, depthwise_kernel
 from ..ops import conv as conv_ops
 from ..ops import eltwise as E
 from ..ops._lib import private_stream
@@ -78,7 +78,7 @@ class SliceExecutor:
     """Runs one (sub)graph for a fixed batch on one device with our HIP kernels."""
 
     FP32_KINDS = ("conv", "pair", "dense", "maxpool", "gap", "softmax", "add", "bn", "relu", "pad", "copy",
-                  "dwconv", "avgpool", "concat", "act", "binary", "affine", "stem_f32", "gconv")
+                  "dwconv", "avgpool", "concat", "act", "binary", "affine", "stem_f32", "gconv", "layernorm")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], batch: int, device="cuda",
                  outputs: Optional[Sequence[str]] = None, tune: bool = False, num_sets: int = 1,
@@ -134,7 +134,8 @@ class SliceExecutor:
         if (L.op == "input" and base == name and len(L.out_shape) == 3
                 and L.attrs.get("stands_for", "input") == "input"):
             return torch.float32          # user image input (Keras float32 NHWC)
-        if L.op == "softmax" or (L.op == "dense" and L.attrs.get("activation") in (None, "linear", "softmax")):
+        if L.op == "softmax" or (L.op == "dense" and len(L.out_shape) == 1
+                                 and L.attrs.get("activation") in (None, "linear", "softmax")):
             return torch.float32          # logits / probabilities; a Dense(relu, ...) feeds the next GEMM in bf16
         return torch.bfloat16
 
@@ -196,7 +197,7 @@ class SliceExecutor:
                                                     ((0, 0), (0, 0)), dev)
             elif st.kind == "dwconv":
                 p = st.p
-                k = weights[f"{p['conv']}/depthwise_kernel"][..., 0]          # (kh, kw, C), multiplier 1
+                k = depthwise_kernel(weights, p["conv"])                      # (kh, kw, C), multiplier 1
                 bn = None
                 eps = 1e-3
                 if p["bn"]:
@@ -217,6 +218,8 @@ class SliceExecutor:
                 if L.op == "rescale":
                     sc = np.broadcast_to(np.asarray(L.attrs.get("scale", 1.0), np.float64), (c,))
                     sh = np.broadcast_to(np.asarray(L.attrs.get("offset", 0.0), np.float64), (c,))
+                elif L.op == "layerscale":
+                    sc, sh = weights[f"{L.name}/gamma"].astype(np.float64), np.zeros(c)
                 else:
                     mu = weights[f"{L.name}/mean"].astype(np.float64)
                     sd = np.maximum(np.sqrt(weights[f"{L.name}/variance"].astype(np.float64)), 1e-7)
@@ -234,6 +237,8 @@ class SliceExecutor:
                 s = gm / np.sqrt(var + eps)
                 self.packed[i] = (torch.tensor(s, dtype=torch.float32, device=dev),
                                   torch.tensor(bt - mu * s, dtype=torch.float32, device=dev))
+            elif st.kind == "layernorm":
+                self.packed[i] = self._pack_layernorm(weights, st, self.shape_of(st.out)[-1])
 
     def _pack_weights_f32(self, weights: Dict[str, np.ndarray]) -> None:
         dev = self.device
@@ -271,9 +276,11 @@ class SliceExecutor:
                 sc = gm / np.sqrt(var + eps)
                 self.packed[i] = (torch.tensor(sc, dtype=torch.float32, device=dev),
                                   torch.tensor(bt - mu * sc, dtype=torch.float32, device=dev))
+            elif st.kind == "layernorm":
+                self.packed[i] = self._pack_layernorm(weights, st, self.shape_of(st.out)[-1])
             elif st.kind == "dwconv":
                 p = st.p
-                k = weights[f"{p['conv']}/depthwise_kernel"][..., 0]          # (kh, kw, C), multiplier 1
+                k = depthwise_kernel(weights, p["conv"])                      # (kh, kw, C), multiplier 1
                 bn = None
                 eps = 1e-3
                 if p["bn"]:
@@ -288,6 +295,8 @@ class SliceExecutor:
                 if L.op == "rescale":
                     sc = np.broadcast_to(np.asarray(L.attrs.get("scale", 1.0), np.float64), (c,))
                     sh = np.broadcast_to(np.asarray(L.attrs.get("offset", 0.0), np.float64), (c,))
+                elif L.op == "layerscale":
+                    sc, sh = weights[f"{L.name}/gamma"].astype(np.float64), np.zeros(c)
                 else:
                     mu = weights[f"{L.name}/mean"].astype(np.float64)
                     sd = np.maximum(np.sqrt(weights[f"{L.name}/variance"].astype(np.float64)), 1e-7)
@@ -295,15 +304,27 @@ class SliceExecutor:
                 self.packed[i] = (torch.tensor(np.ascontiguousarray(sc), dtype=torch.float32, device=dev),
                                   torch.tensor(np.ascontiguousarray(sh), dtype=torch.float32, device=dev))
 
+    def _pack_layernorm(self, weights: Dict[str, np.ndarray], st: Step, cp: int):
+        """(gamma, beta) fp32 [cp] of a layernorm step, with Keras' defaults for scale=False / center=False;
+        the bf16 layout's padding channels get gamma = beta = 0, which makes them come out as zeros."""
+        name = st.p["layer"]
+        c = self.g.layers[name].out_shape[-1]
+        gm, bt = np.zeros(cp, np.float32), np.zeros(cp, np.float32)
+        gm[:c] = weights.get(f"{name}/gamma", np.ones(c, np.float32))
+        bt[:c] = weights.get(f"{name}/beta", np.zeros(c, np.float32))
+        return torch.tensor(gm, device=self.device), torch.tensor(bt, device=self.device)
+
     def _folded(self, weights: Dict[str, np.ndarray], p: Dict):
-        """BN-folded (kernel HWIO, bias) of a conv step's parameters."""
+        """BN-folded (kernel HWIO, bias) of a conv step's parameters; a folded LayerScale
+        (p["scale"]) scales kernel and bias per output channel as BN's scale does."""
         cname = p["conv"]
         bn = None
         eps = 1e-3
         if p["bn"]:
             bn = bn_params(weights, p["bn"])
             eps = self.g.layers[p["bn"]].attrs.get("epsilon", 1e-3)
-        return conv_ops.fold_bn(weights[f"{cname}/kernel"], weights.get(f"{cname}/bias"), bn, eps)
+        return conv_ops.fold_bn(conv_kernel(weights, p), weights.get(f"{cname}/bias"), bn, eps,
+                                scale=weights[f"{p['scale']}/gamma"] if p.get("scale") else None)
 
     # ----------------------------------------------------------- buffers
     def _alloc(self) -> None:
@@ -853,6 +874,10 @@ class SliceExecutor:
                 w, bias = self.packed[i]
                 E.dwconv(b[st.ins[0]], w, bias, b[st.out], st.p["stride"], st.p["pads"], act=st.p["relu"],
                          stream=stream)
+            elif k == "layernorm":
+                gm, bt = self.packed[i]
+                E.layernorm(b[st.ins[0]], gm, bt, b[st.out], self.g.layers[st.p["layer"]].out_shape[-1], st.p["eps"],
+                            stream=stream)
             elif k == "act":
                 E.act(b[st.ins[0]], b[st.out], st.p["mode"], st.p["alpha"], stream=stream)
             elif k == "binary":
@@ -978,6 +1003,9 @@ class SliceExecutor:
             w, bias = self.packed[i]
             E.dwconv_f32(b[st.ins[0]], w, bias, b[st.out], st.p["stride"], st.p["pads"], act=st.p["relu"],
                          stream=stream)
+        elif k == "layernorm":
+            gm, bt = self.packed[i]
+            E.layernorm_f32(b[st.ins[0]], gm, bt, b[st.out], st.p["eps"], stream=stream)
         elif k == "gconv":
             conv_ops.gconv_forward_f32(b[st.ins[0]], self.packed[i], b[st.out], relu=st.p["relu"], stream=stream)
         elif k == "avgpool":

@@ -8,10 +8,15 @@ kernels:
 
 * ``conv``     Conv2D [+BN folded] [+Add residual] [+ReLU / ReLU6, or the
                Conv2D's own activation='relu']; a preceding ZeroPadding2D or
-               'same' padding (any stride, TF placement) becomes explicit pads
+               'same' padding (any stride, TF placement) becomes explicit pads.
+               A Dense on an (H, W, C) tensor is a 1x1 conv step, and a
+               LayerScale directly after either folds in where BN's scale goes
+               (elsewhere it is an ``affine`` step)
 * ``maxpool``  [ZeroPadding2D +] MaxPooling2D ('same' padding excluded from the max)
 * ``avgpool``  AveragePooling2D (padding excluded from the mean)
-* ``dwconv``   DepthwiseConv2D [+BN folded] [+ReLU/ReLU6], explicit pads
+* ``dwconv``   DepthwiseConv2D, or Conv2D(groups=C) with one channel per group,
+               [+BN folded] [+ReLU/ReLU6], explicit pads
+* ``layernorm`` LayerNormalization over the last axis; nothing fuses into it
 * ``gconv``    Conv2D(groups > 1) [+BN folded] [+ReLU/ReLU6], explicit pads; no
                residual fusion, and a kind of its own so that no pass written
                for dense convs (pair, siblings, stem, bottleneck) ever sees it
@@ -141,7 +146,14 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                 done.add(n)
                 continue
             steps.append(Step("pad", n, [R(L.inputs[0])], [n], {"pad": a["pad"]}))
-        elif L.op in ("conv", "dwconv"):
+        elif L.op in ("conv", "dwconv") or (L.op == "dense" and len(g.layers[L.inputs[0]].out_shape) == 3):
+            if L.op == "dense":
+                # Dense on (H, W, C) is a 1x1 conv: it gets the pointwise kernels, the tuning table and
+                # the conv epilogue; the weight packers reshape its (cin, units) kernel (p["dense"])
+                if a.get("activation") == "softmax":
+                    raise NotImplementedError(f"Dense(activation='softmax') on a rank-3 tensor ({n})")
+                a = {"filters": a["units"], "kernel": (1, 1), "stride": 1, "padding": "valid",
+                     "activation": a.get("activation"), "use_bias": a.get("use_bias", True)}
             src = L.inputs[0]
             pads = ((0, 0), (0, 0))
             cover = [n]
@@ -155,15 +167,24 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
             res = None
             out = n
             post_act = 0                        # an activation the MFMA epilogue does not take (swish, ...)
-            grouped = L.op == "conv" and a.get("groups", 1) > 1
+            is_conv = L.op in ("conv", "dense")
+            # Conv2D(groups=C) with one channel per group is a depthwise conv (ConvNeXt's 7x7)
+            depthwise = L.op == "dwconv" or (L.op == "conv" and a.get("groups", 1) > 1 and a["groups"] == a["filters"]
+                                             == g.layers[L.inputs[0]].out_shape[-1])
+            grouped = L.op == "conv" and a.get("groups", 1) > 1 and not depthwise
+            scale = None                        # a LayerScale folded like BN's scale
             if own_act(n, L):
                 relu = own_act(n, L)            # Conv2D(activation=...): nothing after it fuses
-                if L.op == "conv" and relu > 2:
+                if not depthwise and relu > 2:
                     post_act, relu = relu, 0
             else:
                 c1 = single(n)
-                if c1 is not None and g.layers[c1].op == "bn":
-                    bn = c1
+                if c1 is not None and (g.layers[c1].op == "bn" or (g.layers[c1].op == "layerscale" and is_conv
+                                                                   and not depthwise and not grouped)):
+                    if g.layers[c1].op == "bn":
+                        bn = c1
+                    else:
+                        scale = c1
                     cover.append(c1)
                     out = c1
                     c2 = single(c1)
@@ -172,11 +193,11 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                            and single(c2) is not None and g.layers[single(c2)].op == "add"):
                         cover.append(c2)            # drop-connect Dropout between the BN and the residual Add
                         feed, c2 = c2, single(c2)
-                    if act_mode(c2) and (L.op == "dwconv" or act_mode(c2) <= 2):
+                    if act_mode(c2) and (depthwise or act_mode(c2) <= 2):
                         relu = act_mode(c2)
                         cover.append(c2)
                         out = c2
-                    elif (L.op == "conv" and not grouped and c2 is not None and g.layers[c2].op == "add"
+                    elif (is_conv and not depthwise and not grouped and c2 is not None and g.layers[c2].op == "add"
                           and len(g.layers[c2].inputs) == 2):
                         other = [i for i in g.layers[c2].inputs if i != feed]
                         if len(other) == 1 and alias.get(other[0], other[0]) in produced:
@@ -188,12 +209,12 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                                 relu = act_mode(c3)
                                 cover.append(c3)
                                 out = c3
-                elif act_mode(c1) and (L.op == "dwconv" or act_mode(c1) <= 2):
+                elif act_mode(c1) and (depthwise or act_mode(c1) <= 2):
                     relu = act_mode(c1)
                     cover.append(c1)
                     out = c1
             kernel = tuple(_pair(a["kernel"]))
-            if L.op == "dwconv":
+            if depthwise:
                 steps.append(Step("dwconv", out, [R(src)], cover,
                                   {"conv": n, "bn": bn, "relu": relu, "pads": pads, "stride": a.get("stride", 1),
                                    "kernel": kernel}))
@@ -210,6 +231,10 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                                   {"conv": n, "bn": bn, "relu": relu, "residual": res, "pads": pads,
                                    "stride": a.get("stride", 1), "kernel": kernel,
                                    "filters": a["filters"], "packed_input": src in packed}))
+                if scale:
+                    steps[-1].p["scale"] = scale
+                if L.op == "dense":
+                    steps[-1].p["dense"] = True
                 if post_act:
                     steps.append(Step("act", out, [cv_out], [], {"mode": post_act, "alpha": 0.3}))
             done.update(cover)
@@ -271,8 +296,13 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                 out = c
             steps.append(Step("binary", out, [R(i) for i in L.inputs], cover, {"fn": a["fn"], "act": mode}))
             done.update(cover)
-        elif L.op in ("rescale", "normalization"):
+        elif L.op in ("rescale", "normalization", "layerscale"):
+            # a LayerScale that did not fold into its conv (a cut exposes the conv, or none precedes it)
             steps.append(Step("affine", n, [R(L.inputs[0])], [n], {"layer": n}))
+            done.add(n)
+        elif L.op == "layernorm":
+            steps.append(Step("layernorm", n, [R(L.inputs[0])], [n],
+                              {"layer": n, "eps": float(a.get("epsilon", 1e-3))}))
             done.add(n)
         elif L.op == "gmp":
             steps.append(Step("gmp", n, [R(L.inputs[0])], [n]))
@@ -464,11 +494,13 @@ def merge_siblings(steps: List[Step]) -> List[Step]:
         if i in taken:
             continue
         p = st.p
-        if st.kind == "conv" and not p.get("residual") and p.get("kernel") == (1, 1) and not p.get("packed_input"):
+        if (st.kind == "conv" and not p.get("residual") and p.get("kernel") == (1, 1) and not p.get("packed_input")
+                and not p.get("dense")):
             for j in range(i + 1, min(i + 4, len(steps))):
                 sj = steps[j]
                 q = sj.p
                 if (j not in taken and sj.kind == "conv" and sj.ins[0] == st.ins[0] and not q.get("residual")
+                        and not q.get("dense")
                         and q.get("kernel") == (1, 1) and q["stride"] == p["stride"] and q["pads"] == p["pads"]
                         and p["filters"] % 256 == 0 and q["filters"] % 8 == 0):
                     # nothing between them may consume the first sibling's output before

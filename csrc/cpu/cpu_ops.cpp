@@ -361,6 +361,32 @@ void affine(const Arr<float>& x, const Arr<float>& scale, const Arr<float>& shif
     for (int c = 0; c < C; ++c) yp[r * C + c] = act_f(xp[r * C + c] * sp[c] + hp[c], act, alpha);
 }
 
+// Keras LayerNormalization over the last axis: y = (x - mu) * rsqrt(var + eps) * gamma[c] + beta[c], with the
+// row's mean and its biased variance from the centred values (two passes, never E[x^2] - mu^2)
+void layernorm(const Arr<float>& x, const Arr<float>& gamma, const Arr<float>& beta, Arr<float>& y, float eps) {
+  const int C = x.shape(x.ndim() - 1);
+  const long rows = x.size() / C;
+  need(gamma.size() == C && beta.size() == C && y.size() == x.size(), "layernorm shapes");
+  const float *xp = cptr(x), *gp = cptr(gamma), *bp = cptr(beta);
+  float* yp = mptr(y);
+  py::gil_scoped_release nogil;
+#pragma omp parallel for schedule(static)
+  for (long r = 0; r < rows; ++r) {
+    const float* xr = xp + r * C;
+    float* yr = yp + r * C;
+    double s = 0.0;
+    for (int c = 0; c < C; ++c) s += xr[c];
+    const double mu = s / C;
+    double q = 0.0;
+    for (int c = 0; c < C; ++c) {
+      const double d = xr[c] - mu;
+      q += d * d;
+    }
+    const double rstd = 1.0 / std::sqrt(q / C + (double)eps);
+    for (int c = 0; c < C; ++c) yr[c] = (float)((xr[c] - mu) * rstd) * gp[c] + bp[c];
+  }
+}
+
 // y = act(x)
 void activation(const Arr<float>& x, Arr<float>& y, int act, float alpha) {
   need(y.size() == x.size(), "act shapes");
@@ -479,6 +505,7 @@ PYBIND11_MODULE(_cpu, m) {
   m.def("global_pool", &global_pool, py::arg("x"), py::arg("y"), py::arg("kind") = 0);
   m.def("affine", &affine, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("y"), py::arg("act") = 0,
         py::arg("alpha") = 0.3f);
+  m.def("layernorm", &layernorm, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("y"), py::arg("eps"));
   m.def("activation", &activation, py::arg("x"), py::arg("y"), py::arg("act"), py::arg("alpha") = 0.3f);
   m.def("binary", &binary, py::arg("a"), py::arg("b"), py::arg("y"), py::arg("op"), py::arg("act") = 0,
         py::arg("alpha") = 0.3f);

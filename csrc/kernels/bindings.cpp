@@ -386,6 +386,15 @@ PYBIND11_MODULE(_C, m) {
     check(adapt::dwconv_f32(P<const float>(x), P<const float>(w), P<const float>(b), P<float>(y), B, H, W, C, OH, OW,
                             KH, KW, Sd, pt, pl, act, alpha, S(s)), "dwconv_f32");
   });
+  m.def("layernorm_f32", [](u64 x, u64 gamma, u64 beta, u64 y, int rows, int C, float eps, u64 s) {
+    check(adapt::layernorm_f32(P<const float>(x), P<const float>(gamma), P<const float>(beta), P<float>(y), rows, C,
+                               eps, S(s)), "layernorm_f32");
+  });
+  m.def("layernorm", [](u64 x, u64 gamma, u64 beta, u64 y, int rows, int Cp, int C, float eps, u64 s) {
+    check(adapt::layernorm(P<const bf16>(x), P<const float>(gamma), P<const float>(beta), P<bf16>(y), rows, Cp, C,
+                           eps, S(s)), "layernorm");
+  });
+  m.def("layernorm_lanes", &adapt::layernorm_lanes);
   m.def("gconv_f32_mfma_ok", &adapt::gconv_f32_mfma_ok);
   m.def("gconv_f32_forward", [](u64 x, u64 w, u64 b, u64 y, int B, int H, int W, int Cin, int OH, int OW, int Cout,
                                 int G, int KH, int KW, int Sd, int pt, int pl, int act, bool mfma, u64 s) {

@@ -225,6 +225,13 @@ hipError_t pad_f32(const float* x, float* y, int B, int H, int W, int C, int OH,
                    hipStream_t s);
 hipError_t dwconv_f32(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int C, int OH,
                       int OW, int KH, int KW, int S, int pad_t, int pad_l, int act, float alpha, hipStream_t s);
+// LayerNormalization over the last axis (layernorm.hip): x / y [rows][C] fp32, or [rows][Cp] bf16 with channels
+// C..Cp-1 layout padding (kept out of the statistics, written as zeros; gamma / beta then hold Cp floats)
+hipError_t layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, int rows, int C, float eps,
+                         hipStream_t s);
+hipError_t layernorm(const bf16* x, const float* gamma, const float* beta, bf16* y, int rows, int Cp, int C, float eps,
+                     hipStream_t s);
+int layernorm_lanes(int nvec);   // lanes per row for `nvec` 16-byte vectors per row; 0 = the looped path
 hipError_t avgpool_f32(const float* x, float* y, int B, int H, int W, int C, int OH, int OW, int KH, int KW, int S,
                        int pad_t, int pad_l, hipStream_t s);
 hipError_t concat_f32(const float* x, int Cx, float* y, int Cy, int off, size_t pixels, hipStream_t s);

@@ -44,6 +44,10 @@ OPS = (
     "normalization",  # Keras Normalization(axis=-1): weights mean, variance, count
     "layernorm",  # Keras LayerNormalization over the last axis: attrs epsilon; center / scale only when False
     "layerscale",  # ConvNeXt LayerScale: y = x * gamma (per channel); attrs init_values
+    "deconv",     # Keras Conv2DTranspose: filters, kernel=(kh,kw), stride, padding('valid'|'same'), use_bias,
+                  # activation; kernel (kh, kw, filters, cin) (Keras HWOI), no output_padding, no dilation
+    "upsample",   # Keras UpSampling2D: size=(sh,sw), interpolation ('nearest' | 'bilinear', half-pixel centres)
+    "crop",       # Keras Cropping2D: crop=((t,b),(l,r))
 )
 
 # activations the runtime executes (fused into conv / dense / eltwise epilogues,
@@ -77,6 +81,8 @@ def conv_kernel(weights, p: Dict):
     """HWIO kernel of a conv step's layer `p["conv"]`; a Dense on (H, W, C) (p["dense"]) keeps the Keras
     (cin, units) shape in the weights and is a 1x1 kernel here."""
     k = weights[f"{p['conv']}/kernel"]
+    if p.get("deconv"):         # Conv2DTranspose keeps Keras' (kh, kw, filters, cin); packers and BN folding want
+        return k.transpose(0, 1, 3, 2)      # the output channels last: (kh, kw, cin, filters)
     return k.reshape((1, 1) + tuple(k.shape)) if p.get("dense") else k
 
 
@@ -89,6 +95,16 @@ def same_pads(size: int, k: int, s: int) -> Tuple[int, int]:
 
 def _pair(v) -> Tuple[int, int]:
     return (v, v) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def deconv_out_len(size: int, k: int, s: int, padding: str) -> int:
+    """Keras `deconv_output_length` (no output_padding): 'same' size*s, 'valid' size*s + max(k - s, 0)."""
+    return size * s if padding == "same" else size * s + max(k - s, 0)
+
+
+def deconv_pad_before(k: int, s: int, padding: str) -> int:
+    """Where a Conv2DTranspose's output starts in the full scatter frame of length (size-1)*s + k."""
+    return max(k - s, 0) // 2 if padding == "same" else 0
 
 
 @dataclass
@@ -111,6 +127,12 @@ class Layer:
             cin = in_shapes[0][-1]
             # grouped (Keras layout): output channel o belongs to group o // (filters // groups)
             out = [(f"{self.name}/kernel", (kh, kw, cin // self.attrs.get("groups", 1), self.attrs["filters"]))]
+            if self.attrs.get("use_bias", True):
+                out.append((f"{self.name}/bias", (self.attrs["filters"],)))
+            return out
+        if self.op == "deconv":
+            kh, kw = self.attrs["kernel"]
+            out = [(f"{self.name}/kernel", (kh, kw, self.attrs["filters"], in_shapes[0][-1]))]    # Keras HWOI
             if self.attrs.get("use_bias", True):
                 out.append((f"{self.name}/bias", (self.attrs["filters"],)))
             return out
@@ -155,6 +177,10 @@ class Layer:
             kh, kw = self.attrs["kernel"]
             oh, ow, co = self.out_shape
             return oh * ow * co * kh * kw
+        if self.op == "deconv":                 # every input pixel meets every tap once
+            kh, kw = self.attrs["kernel"]
+            h, w, cin = in_shapes[0]
+            return h * w * kh * kw * cin * self.attrs["filters"]
         if self.op == "dense":
             px = 1
             for d in in_shapes[0][:-1]:         # a Dense on (H, W, C) is a GEMM per pixel
@@ -169,7 +195,7 @@ class Layer:
     @staticmethod
     def from_json(d: Dict) -> "Layer":
         attrs = dict(d.get("attrs", {}))
-        for k in ("kernel", "pad", "pool"):
+        for k in ("kernel", "pad", "pool", "size", "crop"):
             if k in attrs and isinstance(attrs[k], list):
                 attrs[k] = _tuplify(attrs[k])
         return Layer(d["name"], d["op"], list(d["inputs"]), attrs, tuple(d.get("out_shape", ())))
@@ -212,6 +238,14 @@ class Graph:
             if not isinstance(gr, int) or gr < 1 or cin % gr or layer.attrs["filters"] % gr:
                 raise ValueError(f"conv {layer.name!r}: groups={gr} must divide the input channels ({cin}) "
                                  f"and filters ({layer.attrs['filters']})")
+        if layer.op == "upsample":
+            sz = layer.attrs.get("size")
+            if (not isinstance(sz, tuple) or len(sz) != 2 or any(not isinstance(v, int) or v < 1 for v in sz)
+                    or layer.attrs.get("interpolation", "nearest") not in ("nearest", "bilinear")):
+                raise ValueError(f"upsample {layer.name!r}: size must be two positive ints and interpolation "
+                                 f"'nearest' or 'bilinear' (got {sz}, {layer.attrs.get('interpolation')!r})")
+        if layer.op == "crop" and layer.out_shape:
+            self._infer_shape(layer)                # an empty result is refused even with a given shape
         layer.out_shape = tuple(layer.out_shape) or self._infer_shape(layer)
         self.layers[layer.name] = layer
         self.order.append(layer.name)
@@ -237,6 +271,21 @@ class Graph:
             if a.get("padding", "valid") == "same":
                 return (-(-h // s), -(-w // s), co)
             return ((h - kh) // s + 1, (w - kw) // s + 1, co)
+        if layer.op == "deconv":
+            h, w, _ = ins[0]
+            kh, kw = a["kernel"]
+            s, pad = a.get("stride", 1), a.get("padding", "valid")
+            return (deconv_out_len(h, kh, s, pad), deconv_out_len(w, kw, s, pad), a["filters"])
+        if layer.op == "upsample":
+            h, w, c = ins[0]
+            sh, sw = a["size"]
+            return (h * sh, w * sw, c)
+        if layer.op == "crop":
+            (t, b), (l, r) = a["crop"]
+            h, w, c = ins[0]
+            if min(t, b, l, r) < 0 or h - t - b < 1 or w - l - r < 1:
+                raise ValueError(f"crop {layer.name!r}: {a['crop']} leaves nothing of {ins[0]}")
+            return (h - t - b, w - l - r, c)
         if layer.op in ("bn", "relu", "softmax", "identity", "act", "rescale", "normalization", "layernorm",
                         "layerscale"):
             return ins[0]

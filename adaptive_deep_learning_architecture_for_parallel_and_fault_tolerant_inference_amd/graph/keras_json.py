@@ -141,6 +141,27 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
         if int(cfg.get("depth_multiplier", 1)) != 1:
             raise NotImplementedError(f"{name}: depth_multiplier != 1")
         return Layer(name, "dwconv", inputs, a)
+    if cls == "Conv2DTranspose":
+        if cfg.get("output_padding") is not None:
+            raise NotImplementedError(f"{name}: Conv2DTranspose with output_padding={cfg['output_padding']}")
+        if _pair(cfg.get("dilation_rate", 1)) != (1, 1):
+            raise NotImplementedError(f"{name}: dilated transposed convolution "
+                                      f"(dilation_rate={cfg['dilation_rate']})")
+        a = {"filters": int(cfg["filters"]), "kernel": _pair(cfg["kernel_size"]), "stride": _stride(cfg, name),
+             "padding": cfg.get("padding", "valid"), "use_bias": bool(cfg.get("use_bias", True))}
+        act = _activation(cfg.get("activation", "linear"), name)
+        if act == "softmax":
+            raise NotImplementedError(f"{name}: softmax on a convolution")
+        if act:
+            a["activation"] = act
+        return Layer(name, "deconv", inputs, a)
+    if cls == "UpSampling2D":
+        interp = cfg.get("interpolation", "nearest")
+        if interp not in ("nearest", "bilinear"):
+            raise NotImplementedError(f"{name}: UpSampling2D interpolation {interp!r}")
+        return Layer(name, "upsample", inputs, {"size": _pair(cfg.get("size", 2)), "interpolation": interp})
+    if cls == "Cropping2D":
+        return Layer(name, "crop", inputs, {"crop": _padding2d(cfg.get("cropping", 0))})
     if cls == "BatchNormalization":
         axis = cfg.get("axis", -1)
         axis = axis[0] if isinstance(axis, list) else axis
@@ -277,6 +298,18 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
             cfg.update(filters=a["filters"], groups=a.get("groups", 1))
         else:
             cfg.update(depth_multiplier=1)
+    elif L.op == "deconv":
+        cls = "Conv2DTranspose"
+        cfg.update(filters=a["filters"], kernel_size=list(_pair(a["kernel"])), strides=[a.get("stride", 1)] * 2,
+                   padding=a.get("padding", "valid"), data_format="channels_last", dilation_rate=[1, 1],
+                   output_padding=None, activation=a.get("activation") or "linear",
+                   use_bias=a.get("use_bias", True))
+    elif L.op == "upsample":
+        cls = "UpSampling2D"
+        cfg.update(size=list(a["size"]), data_format="channels_last", interpolation=a.get("interpolation", "nearest"))
+    elif L.op == "crop":
+        cls = "Cropping2D"
+        cfg.update(cropping=[list(p) for p in a["crop"]], data_format="channels_last")
     elif L.op == "bn":
         cls = "BatchNormalization"
         cfg.update(axis=[3], momentum=0.99, epsilon=a.get("epsilon", 1e-3), center=a.get("center", True),

@@ -129,6 +129,8 @@ def layer_costs(g: Graph, batch: int = 32, hw: Optional[HwModel] = None) -> Dict
             byts = g.tensor_bytes(n, hw.act_bytes) * batch   # residual read inside the conv epilogue
             out[n] = byts / hw.hbm_bw
             continue
+        # deconv: its true MACs (input pixels x taps x cin x filters, the phase form multiplies no stuffed
+        # zeros) against its bytes; upsample / crop have no MACs and cost their input + output traffic
         t = max(2.0 * macs / hw.mfma_flops, byts / hw.hbm_bw) + hw.launch_s
         out[n] = t
     return out
@@ -213,8 +215,10 @@ def default_candidates(g: Graph, fine: bool = True) -> List[str]:
             return nxt != "relu"
         if L.op == "bn":
             return nxt not in ("relu", "add")
-        if L.op in ("conv", "dwconv"):
+        if L.op in ("conv", "dwconv", "deconv"):
             return L.attrs.get("activation") == "relu"
+        if L.op == "upsample":                  # a step of its own: nothing fuses into or after it
+            return True
         return False
     pts = prefix_points(g) if fine else articulation_points(g)
     return [n for n in pts if group_end(n)]

@@ -118,6 +118,12 @@ def init_weights(g: Graph, seed: int = 0, layers: Optional[List[str]] = None) ->
             out[specs[0][0]] = (rng.standard_normal((kh, kw, cin, cout)) * std).astype(np.float32)
             if len(specs) > 1:
                 out[specs[1][0]] = (rng.standard_normal(cout) * 0.01).astype(np.float32)
+        elif L.op == "deconv":                     # Keras HWOI; fan-in kh * kw * cin
+            kh, kw, cout, cin = specs[0][1]
+            std = np.sqrt(2.0 / (kh * kw * cin))
+            out[specs[0][0]] = (rng.standard_normal((kh, kw, cout, cin)) * std).astype(np.float32)
+            if len(specs) > 1:
+                out[specs[1][0]] = (rng.standard_normal(cout) * 0.01).astype(np.float32)
         elif L.op == "dwconv":
             kh, kw, cin, mult = specs[0][1]
             std = np.sqrt(2.0 / (kh * kw))

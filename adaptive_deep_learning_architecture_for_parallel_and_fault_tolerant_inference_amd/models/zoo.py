@@ -20,6 +20,11 @@ Parameter totals (Keras, include_top, 1000 classes; checked by tests):
 VGG16 138,357,544; VGG19 143,667,240; MobileNetV2 3,538,984; DenseNet121 8,062,504;
 EfficientNetB0 5,330,571; InceptionV3 23,851,784; ResNeXt50 25,097,128; ResNeXt101 44,315,560;
 ConvNeXt Tiny 28,589,128, Small 50,223,688, Base 88,591,464, Large 197,767,336, XLarge 350,196,968.
+
+Not from `keras.applications` (models whose output is a map, not a class vector):
+
+* U-Net (`unet`, `unet_bilinear`, test size `unet_tiny`): Conv2DTranspose or UpSampling2D decoders, skip
+  Concatenates; 31,031,745 parameters at base 64, depth 4, one class, RGB input.
 """
 from __future__ import annotations
 
@@ -400,7 +405,60 @@ def build_convnext(name: str = "convnext_tiny", classes: int = 1000, input_shape
     return g
 
 
+# ------------------------------------------------------------------- U-Net
+# name -> (base, depth, default input, up); tiny: same naming / structure, for fast tests
+UNET = {
+    "unet": (64, 4, (256, 256, 3), "transpose"),
+    "unet_bilinear": (64, 4, (256, 256, 3), "bilinear"),
+    "unet_tiny": (16, 2, (32, 32, 3), "transpose"),
+}
+
+
+def build_unet(name: str = "unet", classes: int = 1, input_shape=None, base: int = None, depth: int = None,
+               up: str = None) -> Graph:
+    """U-Net (Ronneberger et al. 2015) as it is usually written in Keras, with 'same' convolutions so the
+    skips need no cropping: encoder level i is two 3x3 ReLU convs of base * 2^i filters and a 2x2 max-pool,
+    the bottleneck two convs of base * 2^depth, each decoder level Conv2DTranspose(base * 2^i, 2, strides=2)
+    -> Concatenate([skip, up]) -> two 3x3 ReLU convs, the head a 1x1 sigmoid conv.  up="bilinear" /
+    "nearest" replaces the transposed conv by UpSampling2D(2) and a 2x2 'same' Conv2D of the same filters
+    (the same parameter total).  H and W must be multiples of 2^depth."""
+    dbase, ddepth, dshape, dup = UNET.get(name, UNET["unet"])
+    base, depth, up = base or dbase, ddepth if depth is None else depth, up or dup
+    shape = tuple(input_shape or dshape)
+    if up not in ("transpose", "bilinear", "nearest"):
+        raise ValueError(f"build_unet: up={up!r} (transpose, bilinear or nearest)")
+    if shape[0] % (1 << depth) or shape[1] % (1 << depth):
+        raise ValueError(f"build_unet: input {shape} is not a multiple of {1 << depth} in H and W")
+    g = Graph(name)
+    x = g.add(Layer("input_1", "input", [], {"shape": shape}))
+
+    def double(x: str, nm: str, f: int) -> str:
+        x = _conv(g, x, f"{nm}_conv1", f, 3, padding="same", activation="relu")
+        return _conv(g, x, f"{nm}_conv2", f, 3, padding="same", activation="relu")
+
+    skips = []
+    for i in range(depth):
+        x = double(x, f"enc{i + 1}", base << i)
+        skips.append(x)
+        x = g.add(Layer(f"enc{i + 1}_pool", "maxpool", [x], {"pool": 2, "stride": 2, "padding": "valid"}))
+    x = double(x, "bottleneck", base << depth)
+    for i in reversed(range(depth)):
+        nm, f = f"dec{i + 1}", base << i
+        if up == "transpose":
+            x = g.add(Layer(f"{nm}_up", "deconv", [x], {"filters": f, "kernel": (2, 2), "stride": 2,
+                                                       "padding": "same", "use_bias": True}))
+        else:
+            x = g.add(Layer(f"{nm}_upsample", "upsample", [x], {"size": (2, 2), "interpolation": up}))
+            x = _conv(g, x, f"{nm}_up", f, 2, padding="same")
+        x = g.add(Layer(f"{nm}_concat", "concat", [skips[i], x]))
+        x = double(x, nm, f)
+    x = _conv(g, x, "head", classes, 1, activation="sigmoid")
+    g.output_names = [x]
+    return g
+
+
 BUILDERS: Dict[str, Callable[..., Graph]] = {
+    **{n: (lambda n: lambda **kw: build_unet(n, **kw))(n) for n in UNET},
     **{n: (lambda n: lambda **kw: build_convnext(n, **kw))(n) for n in CONVNEXT},
     "vgg16": lambda **kw: build_vgg("vgg16", **kw),
     "vgg19": lambda **kw: build_vgg("vgg19", **kw),

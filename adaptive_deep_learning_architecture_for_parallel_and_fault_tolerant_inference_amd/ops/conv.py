@@ -1307,3 +1307,135 @@ def gconv_forward_f32(x: torch.Tensor, pg: PackedGconv, out: torch.Tensor, relu:
                                 pg.groups, pg.kh, pg.kw, pg.stride, pg.pad_t, pg.pad_l, int(relu),
                                 pg.path == "mfma", stream_handle(stream))
     return out
+
+
+# ------------------------------------------------------------------ transposed convolution
+DECONV_MAX_SLOTS = 256                # tap slots of one phase, ceil(kh / s) * ceil(kw / s): the halo of a 1 x 1 tile
+
+
+def deconv_path(cin: int, cout: int, kh: int, kw: int, s: int) -> str:
+    """Which kernel of csrc/kernels/deconv_f32.hip runs an fp32 Conv2DTranspose: "mfma" when Cin % 16 == 0
+    and Cout % 16 == 0 (every kernel size, stride and padding), "generic" for every other legal shape.
+    A static shape rule (no device needed); the launcher re-checks it."""
+    if min(cin, cout, kh, kw, s) < 1:
+        raise ValueError(f"transposed conv: cin {cin}, cout {cout}, kernel {kh}x{kw}, stride {s} must be >= 1")
+    ok = cin % 16 == 0 and cout % 16 == 0 and (-(-kh // s)) * (-(-kw // s)) <= DECONV_MAX_SLOTS
+    return "mfma" if ok else "generic"
+
+
+@dataclass
+class PackedDeconv:
+    """Device-resident weights of one (BN-folded) transposed conv, packed for `path`."""
+    w: torch.Tensor          # mfma: [s*s][Cout/16][slots][Cin/16][64 lanes][4] fp32; generic: [kh][kw][Cin][Cout] fp32
+    bias: torch.Tensor       # [Cout] fp32
+    kh: int
+    kw: int
+    cin: int
+    cout: int
+    stride: int
+    pad_t: int               # where the output starts in the full scatter frame
+    pad_l: int
+    path: str                # "mfma" | "generic" (fp32), "bf16" (the generic kernel on bf16 activations)
+
+
+def deconv_fragments_np(kernel: np.ndarray, s: int) -> np.ndarray:
+    """Transposed-conv kernel (kh, kw, Cin, Cout) -> the MFMA path's weights, per phase.
+
+    Phase (py, px) of the output (frame coordinate mod s) has the taps (py + s a, px + s b); tap slot
+    (a, b) holds that tap, slots past the kernel stay zero (the kernel never reads them).  Per phase, N tile
+    of 16 output channels, slot and 16-channel K chunk one A fragment set of v_mfma_f32_16x16x4_f32, as
+    `gconv_fragments_np`: lane (fr = output channel, fq) holds, for k-step e = 0..3, the weight of input
+    channel 4 fq + e of the chunk."""
+    kh, kw, cin, cout = kernel.shape
+    ta, tb = -(-kh // s), -(-kw // s)
+    k = np.asarray(kernel, np.float32)
+    dense = np.zeros((s, s, ta, tb, cin, cout), np.float32)
+    for py in range(s):
+        for px in range(s):
+            sub = k[py::s, px::s]                                   # taps of this phase, (<= ta, <= tb, cin, cout)
+            dense[py, px, :sub.shape[0], :sub.shape[1]] = sub
+    # [phase][slot][chunk][fq][e][tile][o] -> [phase][tile][slot][chunk][fq][o][e]: lane = 16 fq + o
+    d = dense.reshape(s * s, ta * tb, cin // 16, 4, 4, cout // 16, 16).transpose(0, 5, 1, 2, 3, 6, 4)
+    return np.ascontiguousarray(d).reshape(s * s, cout // 16, ta * tb, cin // 16, 64, 4)
+
+
+def pack_deconv_f32(kernel: np.ndarray, bias: np.ndarray, stride: int, padding, device) -> PackedDeconv:
+    """kernel: (kh, kw, Cin, Cout), i.e. Keras' Conv2DTranspose kernel with its last two axes swapped
+    (graph/ir.py `conv_kernel`), BN already folded.  padding: 'valid' | 'same', or the (top, left) start of
+    the output in the full frame as runtime/plan.py resolves it."""
+    from ..graph.ir import deconv_pad_before
+    kh, kw, cin, cout = kernel.shape
+    s = int(stride)
+    path = deconv_path(cin, cout, kh, kw, s)
+    pt, pl = ((deconv_pad_before(kh, s, padding), deconv_pad_before(kw, s, padding)) if isinstance(padding, str)
+              else (int(padding[0]), int(padding[1])))
+    w = deconv_fragments_np(kernel, s) if path == "mfma" else np.ascontiguousarray(kernel, np.float32)
+    return PackedDeconv(w=torch.from_numpy(w).to(device=device).contiguous(),
+                        bias=torch.from_numpy(np.ascontiguousarray(bias, np.float32)).to(device),
+                        kh=kh, kw=kw, cin=cin, cout=cout, stride=s, pad_t=pt, pad_l=pl, path=path)
+
+
+def pack_deconv_bf16(kernel: np.ndarray, bias: np.ndarray, stride: int, padding, device) -> PackedDeconv:
+    """bf16 execution: the generic kernel's fp32 weights (kh, kw, Cin, Cout) and bias; the activations'
+    padding channels are skipped by the kernel, so nothing is padded here."""
+    from ..graph.ir import deconv_pad_before
+    kh, kw, cin, cout = kernel.shape
+    s = int(stride)
+    deconv_path(cin, cout, kh, kw, s)
+    pt, pl = ((deconv_pad_before(kh, s, padding), deconv_pad_before(kw, s, padding)) if isinstance(padding, str)
+              else (int(padding[0]), int(padding[1])))
+    return PackedDeconv(w=torch.from_numpy(np.ascontiguousarray(kernel, np.float32)).to(device),
+                        bias=torch.from_numpy(np.ascontiguousarray(bias, np.float32)).to(device),
+                        kh=kh, kw=kw, cin=cin, cout=cout, stride=s, pad_t=pt, pad_l=pl, path="bf16")
+
+
+def _deconv_args(x, pd: PackedDeconv, out, relu, dtype, what):
+    for t, nm in ((x, "x"), (out, "out")):
+        if t.dtype != dtype or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"{what}: {nm} must be a contiguous {dtype} device tensor")
+    if x.dim() != 4 or out.dim() != 4 or x.shape[0] != out.shape[0]:
+        raise ValueError(f"{what}: x {tuple(x.shape)} / out {tuple(out.shape)} must be [B,H,W,C]")
+    B, H, W, _ = x.shape
+    _, OH, OW, _ = out.shape
+    # the output window must lie in the frame extended to whole strides: 'valid' / 'same' both do
+    if (OH < 1 or OW < 1 or pd.pad_t < 0 or pd.pad_l < 0 or pd.pad_t + OH > H * pd.stride + pd.kh
+            or pd.pad_l + OW > W * pd.stride + pd.kw):
+        raise ValueError(f"{what}: output {(OH, OW)} from {(H, W)}, kernel {pd.kh}x{pd.kw}, stride {pd.stride}, "
+                         f"start {(pd.pad_t, pd.pad_l)}")
+    if int(relu) not in (0, 1, 2):
+        raise ValueError(f"{what}: activation must be 0 (none), 1 (ReLU) or 2 (ReLU6)")
+    if pd.w.device != x.device or pd.bias.numel() != pd.cout or pd.w.dtype != torch.float32:
+        raise ValueError(f"{what}: weights on another device / bias size")
+    return B, H, W, OH, OW
+
+
+def deconv_forward_f32(x: torch.Tensor, pd: PackedDeconv, out: torch.Tensor, relu: int = 0, stream=None) -> torch.Tensor:
+    """Transposed conv: x [B,H,W,Cin] fp32 -> out [B,OH,OW,Cout] fp32 = act(deconv(x) + bias), act 0 / 1 (ReLU) /
+    2 (ReLU6).  One launch on `stream`, no workspace; the path is the one the weights were packed for."""
+    B, H, W, OH, OW = _deconv_args(x, pd, out, relu, torch.float32, "transposed conv")
+    if x.shape[3] != pd.cin or out.shape[3] != pd.cout:
+        raise ValueError(f"transposed conv expects [B,H,W,{pd.cin}] -> [B,OH,OW,{pd.cout}], got {tuple(x.shape)} -> "
+                         f"{tuple(out.shape)}")
+    if pd.path not in ("mfma", "generic"):
+        raise ValueError(f"transposed conv: weights packed for {pd.path!r} cannot run on fp32 activations")
+    if pd.path == "generic" and tuple(pd.w.shape) != (pd.kh, pd.kw, pd.cin, pd.cout):
+        raise ValueError(f"transposed conv: weights of shape {tuple(pd.w.shape)} are not the generic path's "
+                         f"{(pd.kh, pd.kw, pd.cin, pd.cout)}")
+    kernels().deconv_f32_forward(ptr(x), ptr(pd.w), ptr(pd.bias), ptr(out), B, H, W, pd.cin, OH, OW, pd.cout,
+                                 pd.kh, pd.kw, pd.stride, pd.pad_t, pd.pad_l, int(relu), pd.path == "mfma",
+                                 stream_handle(stream))
+    return out
+
+
+def deconv_forward_bf16(x: torch.Tensor, pd: PackedDeconv, out: torch.Tensor, relu: int = 0, stream=None) -> torch.Tensor:
+    """Transposed conv on bf16 NHWC activations whose channels are padded to 8: x [B,H,W,Cip] -> out
+    [B,OH,OW,Cop], fp32 weights and accumulation (the bounds-checked kernel, not MFMA); padding channels of
+    `x` are never read and those of `out` are written as zeros."""
+    B, H, W, OH, OW = _deconv_args(x, pd, out, relu, torch.bfloat16, "transposed conv (bf16)")
+    cip, cop = x.shape[3], out.shape[3]
+    if pd.path != "bf16" or cip < pd.cin or cop < pd.cout or tuple(pd.w.shape) != (pd.kh, pd.kw, pd.cin, pd.cout):
+        raise ValueError(f"transposed conv (bf16): weights {tuple(pd.w.shape)} [{pd.path}] against rows of "
+                         f"{cip} -> {cop} channels")
+    kernels().deconv_bf16_forward(ptr(x), ptr(pd.w), ptr(pd.bias), ptr(out), B, H, W, pd.cin, cip, OH, OW, pd.cout,
+                                  cop, pd.kh, pd.kw, pd.stride, pd.pad_t, pd.pad_l, int(relu), stream_handle(stream))
+    return out

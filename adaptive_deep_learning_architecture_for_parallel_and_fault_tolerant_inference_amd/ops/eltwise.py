@@ -390,6 +390,53 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: tor
     return out
 
 
+def _resize_args(x: torch.Tensor, out: torch.Tensor, dtype, what: str, C):
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{what}: fp32 or bf16 tensors, got {dtype}")
+    _chk(x, dtype, "x"); _chk(out, dtype, "out")
+    if x.dim() != 4 or out.dim() != 4 or x.shape[0] != out.shape[0] or x.shape[3] != out.shape[3]:
+        raise ValueError(f"{what}: bad shapes x{tuple(x.shape)} out{tuple(out.shape)}")
+    Cp = x.shape[3]
+    if dtype == torch.bfloat16 and (Cp % 8 or C is None or not 0 < int(C) <= Cp):
+        raise ValueError(f"{what}: bf16 rows are padded to 8 channels and need the real count (Cp={Cp}, C={C})")
+    if max(x.numel(), out.numel()) >= 2 ** 31 or x.numel() == 0:
+        raise ValueError(f"{what}: tensors must hold 1 .. 2^31 - 1 elements")
+    return Cp
+
+
+def upsample(x: torch.Tensor, out: torch.Tensor, size, bilinear: bool = False, C: Optional[int] = None,
+             stream=None) -> torch.Tensor:
+    """Keras UpSampling2D (csrc/kernels/resize.hip): x [B,H,W,C] -> out [B,H*sh,W*sw,C], fp32 or bf16 (rows of
+    Cp stored channels, `C` real ones; the padding is written as zeros).  Nearest is a bit-exact copy;
+    bilinear uses half-pixel centres (tf.image.resize)."""
+    sh, sw = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    Cp = _resize_args(x, out, x.dtype, "upsample", C)
+    B, H, W, _ = x.shape
+    if sh < 1 or sw < 1 or tuple(out.shape[1:3]) != (H * sh, W * sw):
+        raise ValueError(f"upsample: size {(sh, sw)} takes {tuple(x.shape)} to {(B, H * sh, W * sw, Cp)}, "
+                         f"got {tuple(out.shape)}")
+    if x.dtype == torch.float32:
+        kernels().upsample_f32(ptr(x), ptr(out), B, H, W, Cp, sh, sw, bool(bilinear), stream_handle(stream))
+    else:
+        kernels().upsample_bf16(ptr(x), ptr(out), B, H, W, Cp, int(C), sh, sw, bool(bilinear), stream_handle(stream))
+    return out
+
+
+def crop(x: torch.Tensor, out: torch.Tensor, top: int, left: int, C: Optional[int] = None, stream=None) -> torch.Tensor:
+    """Keras Cropping2D: out [B,OH,OW,C] = x[:, top:top+OH, left:left+OW, :], a bit-exact copy; fp32 or bf16
+    (bf16 as in `upsample`)."""
+    Cp = _resize_args(x, out, x.dtype, "crop", C)
+    B, H, W, _ = x.shape
+    OH, OW = out.shape[1:3]
+    if top < 0 or left < 0 or OH < 1 or OW < 1 or top + OH > H or left + OW > W:
+        raise ValueError(f"crop: window ({top}, {left}) + {(OH, OW)} is not inside {(H, W)}")
+    if x.dtype == torch.float32:
+        kernels().crop_f32(ptr(x), ptr(out), B, H, W, Cp, OH, OW, int(top), int(left), stream_handle(stream))
+    else:
+        kernels().crop_bf16(ptr(x), ptr(out), B, H, W, Cp, int(C), OH, OW, int(top), int(left), stream_handle(stream))
+    return out
+
+
 def avgpool_f32(x: torch.Tensor, out: torch.Tensor, k, s: int, pads=((0, 0), (0, 0)), stream=None) -> torch.Tensor:
     _chk(x, torch.float32, "x"); _chk(out, torch.float32, "out")
     kh, kw = (k, k) if isinstance(k, int) else k

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ..graph.ir import Graph, _pair, same_pads
+from ..graph.ir import Graph, _pair, deconv_out_len, deconv_pad_before, same_pads
 
 
 def _same(x: torch.Tensor, kh: int, kw: int, s: int, value: float = 0.0) -> torch.Tensor:
@@ -56,6 +56,33 @@ def _act(y: torch.Tensor, act, alpha: float = 0.3) -> torch.Tensor:
     raise ValueError(f"unsupported activation {act!r}")
 
 
+def deconv_nhwc(x: torch.Tensor, kernel: torch.Tensor, bias, stride: int, padding: str) -> torch.Tensor:
+    """Keras Conv2DTranspose (no output_padding, no dilation) on NHWC x with the Keras kernel
+    (kh, kw, filters, cin): the full scatter F[i*s + t] += x[i] * w[t] (no kernel flip), of which the output is
+    `deconv_out_len` elements from `deconv_pad_before`; positions past the end of F (k < s) are zero before
+    the bias."""
+    kh, kw = kernel.shape[:2]
+    full = F.conv_transpose2d(x.permute(0, 3, 1, 2), kernel.permute(3, 2, 0, 1), None, stride=stride)
+    oh, ow = deconv_out_len(x.shape[1], kh, stride, padding), deconv_out_len(x.shape[2], kw, stride, padding)
+    pt, pl = deconv_pad_before(kh, stride, padding), deconv_pad_before(kw, stride, padding)
+    full = F.pad(full, (0, max(pl + ow - full.shape[3], 0), 0, max(pt + oh - full.shape[2], 0)))
+    y = full[:, :, pt:pt + oh, pl:pl + ow].permute(0, 2, 3, 1)
+    return y if bias is None else y + bias
+
+
+def upsample_nhwc(x: torch.Tensor, size, interpolation: str) -> torch.Tensor:
+    """Keras UpSampling2D on NHWC x: 'nearest' repeats pixels, 'bilinear' is tf.image.resize's half-pixel
+    centres (`align_corners=False`)."""
+    sh, sw = size
+    if interpolation == "nearest":
+        return x.repeat_interleave(sh, dim=1).repeat_interleave(sw, dim=2)
+    if interpolation != "bilinear":
+        raise ValueError(f"unsupported interpolation {interpolation!r}")
+    y = F.interpolate(x.permute(0, 3, 1, 2), size=(x.shape[1] * sh, x.shape[2] * sw), mode="bilinear",
+                      align_corners=False)
+    return y.permute(0, 2, 3, 1)
+
+
 class ReferenceExecutor:
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], device="cpu", dtype=torch.float32):
         self.g = g
@@ -95,6 +122,15 @@ class ReferenceExecutor:
                 x = _same(x, *a["kernel"], s)
             y = F.conv2d(x, k, bias, stride=s, groups=c)
             return _act(y.permute(0, 2, 3, 1), a.get("activation"))
+        if L.op == "deconv":
+            bias = self.w.get(f"{L.name}/bias")
+            y = deconv_nhwc(ins[0], self.w[f"{L.name}/kernel"], bias, a.get("stride", 1), a.get("padding", "valid"))
+            return _act(y, a.get("activation"), a.get("alpha", 0.3))
+        if L.op == "upsample":
+            return upsample_nhwc(ins[0], a["size"], a.get("interpolation", "nearest"))
+        if L.op == "crop":
+            (t, b), (l, r) = a["crop"]
+            return ins[0][:, t:ins[0].shape[1] - b, l:ins[0].shape[2] - r, :]
         if L.op == "bn":
             m_, v_ = self.w[f"{L.name}/moving_mean"], self.w[f"{L.name}/moving_variance"]
             g_ = self.w.get(f"{L.name}/gamma", 1.0)         # scale=False / center=False defaults

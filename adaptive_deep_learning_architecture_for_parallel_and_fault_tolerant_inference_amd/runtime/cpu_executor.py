@@ -55,7 +55,7 @@ class CpuExecutor:
     """Runs one (sub)graph on the host CPU with the native `_cpu` ops (fp32)."""
 
     KINDS = ("conv", "gconv", "dwconv", "maxpool", "avgpool", "bn", "add", "relu", "act", "binary", "affine", "gmp", "copy",
-             "concat", "gap", "dense", "softmax", "pad", "layernorm")
+             "concat", "gap", "dense", "softmax", "pad", "layernorm", "deconv", "upsample", "crop")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], outputs: Optional[Sequence[str]] = None):
         self.g = g
@@ -90,6 +90,9 @@ class CpuExecutor:
                 k, b = self._folded(weights, st.p)
                 self.packed[i] = (_pad_cout(k, cob), np.ascontiguousarray(b, np.float32))
             elif st.kind == "gconv":                # Keras' grouped layout (kh, kw, cin / groups, cout) as it is
+                k, b = self._folded(weights, st.p)
+                self.packed[i] = (np.ascontiguousarray(k, np.float32), np.ascontiguousarray(b, np.float32))
+            elif st.kind == "deconv":               # (kh, kw, cin, filters): conv_kernel turns Keras' HWOI round
                 k, b = self._folded(weights, st.p)
                 self.packed[i] = (np.ascontiguousarray(k, np.float32), np.ascontiguousarray(b, np.float32))
             elif st.kind == "dense":
@@ -152,6 +155,13 @@ class CpuExecutor:
             w, b = self.packed[i]
             (pt, _), (pl, _) = p["pads"]
             m.gconv2d(ins[0], w, b, y, int(p["stride"]), int(pt), int(pl), int(p["groups"]), int(p["relu"]), 0.3)
+        elif k == "deconv":
+            w, b = self.packed[i]
+            m.deconv2d(ins[0], w, b, y, int(p["stride"]), int(p["pads"][0]), int(p["pads"][1]), int(p["relu"]), 0.3)
+        elif k == "upsample":
+            m.upsample2d(ins[0], y, int(p["size"][0]), int(p["size"][1]), bool(p["bilinear"]))
+        elif k == "crop":
+            m.crop2d(ins[0], y, int(p["crop"][0][0]), int(p["crop"][1][0]))
         elif k == "dwconv":
             w, b = self.packed[i]
             (pt, _), (pl, _) = p["pads"]

@@ -78,7 +78,8 @@ class SliceExecutor:
     """Runs one (sub)graph for a fixed batch on one device with our HIP kernels."""
 
     FP32_KINDS = ("conv", "pair", "dense", "maxpool", "gap", "softmax", "add", "bn", "relu", "pad", "copy",
-                  "dwconv", "avgpool", "concat", "act", "binary", "affine", "stem_f32", "gconv", "layernorm")
+                  "dwconv", "avgpool", "concat", "act", "binary", "affine", "stem_f32", "gconv", "layernorm",
+                  "deconv", "upsample", "crop")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], batch: int, device="cuda",
                  outputs: Optional[Sequence[str]] = None, tune: bool = False, num_sets: int = 1,
@@ -239,6 +240,9 @@ class SliceExecutor:
                                   torch.tensor(bt - mu * s, dtype=torch.float32, device=dev))
             elif st.kind == "layernorm":
                 self.packed[i] = self._pack_layernorm(weights, st, self.shape_of(st.out)[-1])
+            elif st.kind == "deconv":            # the bounds-checked kernel on bf16 activations (no bf16 MFMA path)
+                kf, bf = self._folded(weights, st.p)      # (kh, kw, cin, filters): BN scales the last axis
+                self.packed[i] = conv_ops.pack_deconv_bf16(kf, bf, st.p["stride"], st.p["pads"], dev)
 
     def _pack_weights_f32(self, weights: Dict[str, np.ndarray]) -> None:
         dev = self.device
@@ -258,6 +262,9 @@ class SliceExecutor:
             elif st.kind == "gconv":
                 kf, bf = self._folded(weights, st.p)      # BN scales the last (output channel) axis
                 self.packed[i] = conv_ops.pack_gconv_f32(kf, bf, st.p["groups"], st.p["stride"], st.p["pads"], dev)
+            elif st.kind == "deconv":
+                kf, bf = self._folded(weights, st.p)      # (kh, kw, cin, filters): BN scales the last axis
+                self.packed[i] = conv_ops.pack_deconv_f32(kf, bf, st.p["stride"], st.p["pads"], dev)
             elif st.kind == "pair":
                 k3, b3 = self._folded(weights, st.p["c3"])
                 k1, b1 = self._folded(weights, st.p["c1"])
@@ -874,6 +881,14 @@ class SliceExecutor:
                 w, bias = self.packed[i]
                 E.dwconv(b[st.ins[0]], w, bias, b[st.out], st.p["stride"], st.p["pads"], act=st.p["relu"],
                          stream=stream)
+            elif k == "deconv":
+                conv_ops.deconv_forward_bf16(b[st.ins[0]], self.packed[i], b[st.out], relu=st.p["relu"], stream=stream)
+            elif k == "upsample":
+                E.upsample(b[st.ins[0]], b[st.out], st.p["size"], st.p["bilinear"],
+                           C=self.g.layers[st.out.split("#")[0]].out_shape[-1], stream=stream)
+            elif k == "crop":
+                E.crop(b[st.ins[0]], b[st.out], st.p["crop"][0][0], st.p["crop"][1][0],
+                       C=self.g.layers[st.out.split("#")[0]].out_shape[-1], stream=stream)
             elif k == "layernorm":
                 gm, bt = self.packed[i]
                 E.layernorm(b[st.ins[0]], gm, bt, b[st.out], self.g.layers[st.p["layer"]].out_shape[-1], st.p["eps"],
@@ -1006,6 +1021,12 @@ class SliceExecutor:
         elif k == "layernorm":
             gm, bt = self.packed[i]
             E.layernorm_f32(b[st.ins[0]], gm, bt, b[st.out], st.p["eps"], stream=stream)
+        elif k == "deconv":
+            conv_ops.deconv_forward_f32(b[st.ins[0]], self.packed[i], b[st.out], relu=st.p["relu"], stream=stream)
+        elif k == "upsample":
+            E.upsample(b[st.ins[0]], b[st.out], st.p["size"], st.p["bilinear"], stream=stream)
+        elif k == "crop":
+            E.crop(b[st.ins[0]], b[st.out], st.p["crop"][0][0], st.p["crop"][1][0], stream=stream)
         elif k == "gconv":
             conv_ops.gconv_forward_f32(b[st.ins[0]], self.packed[i], b[st.out], relu=st.p["relu"], stream=stream)
         elif k == "avgpool":

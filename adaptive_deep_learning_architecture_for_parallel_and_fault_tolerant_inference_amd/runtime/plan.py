@@ -20,6 +20,11 @@ kernels:
 * ``gconv``    Conv2D(groups > 1) [+BN folded] [+ReLU/ReLU6], explicit pads; no
                residual fusion, and a kind of its own so that no pass written
                for dense convs (pair, siblings, stem, bottleneck) ever sees it
+* ``deconv``   Conv2DTranspose [+BN folded] [+ReLU/ReLU6]; `pads` is where the output
+               starts in the full scatter frame (top, left).  A kind of its own: no
+               residual, pair, sibling or bottleneck pass ever sees it
+* ``upsample`` UpSampling2D (nearest / bilinear); not folded into a following conv
+* ``crop``     Cropping2D
 * ``concat``   Concatenate along channels (one copy launch per input)
 * ``copy``     a Flatten/Dropout that the slice emits under its own name
                (otherwise they alias their input: Dropout everywhere,
@@ -43,7 +48,7 @@ import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Set
 
-from ..graph.ir import ACT_MODE, Graph, _pair, same_pads
+from ..graph.ir import ACT_MODE, Graph, _pair, deconv_pad_before, same_pads
 
 
 @dataclass
@@ -238,6 +243,40 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                 if post_act:
                     steps.append(Step("act", out, [cv_out], [], {"mode": post_act, "alpha": 0.3}))
             done.update(cover)
+        elif L.op == "deconv":
+            kh, kw = _pair(a["kernel"])
+            s, padding = a.get("stride", 1), a.get("padding", "valid")
+            cover, out, bn, relu, post_act = [n], n, None, 0, 0
+            if own_act(n, L):
+                relu = own_act(n, L)
+                if relu > 2:
+                    post_act, relu = relu, 0
+            else:
+                c1 = single(n)
+                if c1 is not None and g.layers[c1].op == "bn":
+                    bn = c1
+                    cover.append(c1)
+                    out = c1
+                    c1 = single(c1)
+                if 0 < act_mode(c1) <= 2:
+                    relu = act_mode(c1)
+                    cover.append(c1)
+                    out = c1
+            cv_out = out if not post_act else n + "#preact"
+            steps.append(Step("deconv", cv_out, [R(L.inputs[0])], cover,
+                              {"conv": n, "deconv": True, "bn": bn, "relu": relu, "stride": s,
+                               "kernel": (kh, kw), "filters": a["filters"],
+                               "pads": (deconv_pad_before(kh, s, padding), deconv_pad_before(kw, s, padding))}))
+            if post_act:
+                steps.append(Step("act", out, [cv_out], [], {"mode": post_act, "alpha": 0.3}))
+            done.update(cover)
+        elif L.op == "upsample":
+            steps.append(Step("upsample", n, [R(L.inputs[0])], [n],
+                              {"size": tuple(a["size"]), "bilinear": a.get("interpolation", "nearest") == "bilinear"}))
+            done.add(n)
+        elif L.op == "crop":
+            steps.append(Step("crop", n, [R(L.inputs[0])], [n], {"crop": a["crop"]}))
+            done.add(n)
         elif L.op in ("maxpool", "avgpool"):
             src = L.inputs[0]
             pads = ((0, 0), (0, 0))

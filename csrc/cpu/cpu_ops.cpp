@@ -232,6 +232,117 @@ void gconv2d(const Arr<float>& x, const Arr<float>& w, const Arr<float>& bias, A
         gconv_row(xp, wp, bp, yp, n, oh, g, H, W, C, OH, OW, CO, groups, KH, KW, stride, pad_t, pad_l, act, alpha);
 }
 
+// ------------------------------------------------------------------ transposed conv
+// Keras Conv2DTranspose in gather form: output (oy, ox) sits at f = o + pad in the
+// full scatter frame F[i * S + t] += x[i] * w[t]; its taps are the t == f (mod S)
+// with i = (f - t) / S inside the map.  Every output element is written once; one
+// with no tap (KH < S) is act(bias).  A task owns one output row.
+// x [N,H,W,C]; w [KH,KW,C,CO] (output channels last); bias [CO]; y [N,OH,OW,CO]
+ADAPT_CLONES
+void deconv_row(const float* __restrict x, const float* __restrict w, const float* __restrict b, float* __restrict y,
+                int n, int oy, int H, int W, int C, int OH, int OW, int CO, int KH, int KW, int S, int PT, int PL,
+                int act, float alpha) {
+  std::vector<float> accv(CO);
+  float* a = accv.data();
+  const int fy = oy + PT;
+  for (int ox = 0; ox < OW; ++ox) {
+    std::copy(b, b + CO, a);
+    const int fx = ox + PL;
+    for (int ty = fy % S; ty < KH; ty += S) {
+      const int iy = (fy - ty) / S;
+      if (fy < ty || iy >= H) continue;
+      for (int tx = fx % S; tx < KW; tx += S) {
+        const int ix = (fx - tx) / S;
+        if (fx < tx || ix >= W) continue;
+        const float* xv = x + (((size_t)n * H + iy) * W + ix) * C;
+        const float* wr = w + (size_t)(ty * KW + tx) * C * CO;
+        for (int ci = 0; ci < C; ++ci) {
+          const float xc = xv[ci];
+          const float* wv = wr + (size_t)ci * CO;
+#pragma omp simd
+          for (int j = 0; j < CO; ++j) a[j] += xc * wv[j];
+        }
+      }
+    }
+    float* yo = y + (((size_t)n * OH + oy) * OW + ox) * CO;
+    for (int j = 0; j < CO; ++j) yo[j] = act_f(a[j], act, alpha);
+  }
+}
+
+void deconv2d(const Arr<float>& x, const Arr<float>& w, const Arr<float>& bias, Arr<float>& y, int stride, int pad_t,
+              int pad_l, int act, float alpha) {
+  need(x.ndim() == 4 && w.ndim() == 4 && y.ndim() == 4 && bias.ndim() == 1, "deconv2d ranks");
+  const int N = x.shape(0), H = x.shape(1), W = x.shape(2), C = x.shape(3), OH = y.shape(1), OW = y.shape(2),
+            CO = y.shape(3), KH = w.shape(0), KW = w.shape(1);
+  need(w.shape(2) == C && w.shape(3) == CO && y.shape(0) == N && bias.shape(0) == CO && stride >= 1 && pad_t >= 0 &&
+           pad_l >= 0 && N >= 1 && H >= 1 && W >= 1 && OH >= 1 && OW >= 1,
+       "deconv2d shapes");
+  const float *xp = cptr(x), *wp = cptr(w), *bp = cptr(bias);
+  float* yp = mptr(y);
+  py::gil_scoped_release nogil;
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int n = 0; n < N; ++n)
+    for (int oy = 0; oy < OH; ++oy)
+      deconv_row(xp, wp, bp, yp, n, oy, H, W, C, OH, OW, CO, KH, KW, stride, pad_t, pad_l, act, alpha);
+}
+
+// ------------------------------------------------------------------ upsample / crop
+// Keras UpSampling2D: y [N,H*SH,W*SW,C].  Nearest repeats pixels; bilinear is
+// tf.image.resize with half-pixel centres: f = max((o + 0.5) / s - 0.5, 0),
+// i0 = floor(f), i1 = min(i0 + 1, size - 1), weight f - i0.
+void upsample2d(const Arr<float>& x, Arr<float>& y, int sh, int sw, bool bilinear) {
+  need(x.ndim() == 4 && y.ndim() == 4 && sh >= 1 && sw >= 1, "upsample2d ranks");
+  const int N = x.shape(0), H = x.shape(1), W = x.shape(2), C = x.shape(3);
+  const int OH = H * sh, OW = W * sw;
+  need(y.shape(0) == N && y.shape(1) == OH && y.shape(2) == OW && y.shape(3) == C, "upsample2d shapes");
+  const float* xp = cptr(x);
+  float* yp = mptr(y);
+  py::gil_scoped_release nogil;
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int n = 0; n < N; ++n)
+    for (int oy = 0; oy < OH; ++oy) {
+      float* yr = yp + ((size_t)n * OH + oy) * OW * C;
+      if (!bilinear) {
+        const float* xr = xp + ((size_t)n * H + oy / sh) * W * C;
+        for (int ox = 0; ox < OW; ++ox) std::memcpy(yr + (size_t)ox * C, xr + (size_t)(ox / sw) * C, sizeof(float) * C);
+        continue;
+      }
+      const float fy = std::max((oy + 0.5f) / sh - 0.5f, 0.f);
+      const int y0 = (int)fy, y1 = std::min(y0 + 1, H - 1);
+      const float wy = fy - y0;
+      const float* r0 = xp + ((size_t)n * H + y0) * W * C;
+      const float* r1 = xp + ((size_t)n * H + y1) * W * C;
+      for (int ox = 0; ox < OW; ++ox) {
+        const float fx = std::max((ox + 0.5f) / sw - 0.5f, 0.f);
+        const int x0 = (int)fx, x1 = std::min(x0 + 1, W - 1);
+        const float wx = fx - x0;
+        const float *a = r0 + (size_t)x0 * C, *b = r0 + (size_t)x1 * C, *c = r1 + (size_t)x0 * C,
+                    *d = r1 + (size_t)x1 * C;
+        float* yo = yr + (size_t)ox * C;
+#pragma omp simd
+        for (int j = 0; j < C; ++j) {
+          const float top = a[j] + (b[j] - a[j]) * wx, bot = c[j] + (d[j] - c[j]) * wx;
+          yo[j] = top + (bot - top) * wy;
+        }
+      }
+    }
+}
+
+// Keras Cropping2D: y [N,H-t-b,W-l-r,C] = x[:, t:H-b, l:W-r, :]
+void crop2d(const Arr<float>& x, Arr<float>& y, int t, int l) {
+  need(x.ndim() == 4 && y.ndim() == 4 && t >= 0 && l >= 0, "crop2d ranks");
+  const int N = x.shape(0), H = x.shape(1), W = x.shape(2), C = x.shape(3), OH = y.shape(1), OW = y.shape(2);
+  need(y.shape(0) == N && y.shape(3) == C && OH >= 1 && OW >= 1 && t + OH <= H && l + OW <= W, "crop2d shapes");
+  const float* xp = cptr(x);
+  float* yp = mptr(y);
+  py::gil_scoped_release nogil;
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int n = 0; n < N; ++n)
+    for (int h = 0; h < OH; ++h)
+      std::memcpy(yp + ((size_t)n * OH + h) * OW * C, xp + (((size_t)n * H + h + t) * W + l) * C,
+                  sizeof(float) * OW * C);
+}
+
 // ------------------------------------------------------------------ depthwise
 // x [N,H,W,C]; w [KH,KW,C]; bias [C]; y [N,OH,OW,C]
 ADAPT_CLONES
@@ -498,6 +609,10 @@ PYBIND11_MODULE(_cpu, m) {
         py::arg("residual") = py::none());
   m.def("gconv2d", &gconv2d, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("stride"),
         py::arg("pad_t"), py::arg("pad_l"), py::arg("groups"), py::arg("act") = 0, py::arg("alpha") = 0.3f);
+  m.def("deconv2d", &deconv2d, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("stride"),
+        py::arg("pad_t"), py::arg("pad_l"), py::arg("act") = 0, py::arg("alpha") = 0.3f);
+  m.def("upsample2d", &upsample2d, py::arg("x"), py::arg("y"), py::arg("sh"), py::arg("sw"), py::arg("bilinear"));
+  m.def("crop2d", &crop2d, py::arg("x"), py::arg("y"), py::arg("t"), py::arg("l"));
   m.def("dwconv2d", &dwconv2d, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("stride"),
         py::arg("pad_t"), py::arg("pad_l"), py::arg("act") = 0, py::arg("alpha") = 0.3f);
   m.def("pool2d", &pool2d, py::arg("x"), py::arg("y"), py::arg("kind"), py::arg("kh"), py::arg("kw"),

@@ -395,6 +395,32 @@ PYBIND11_MODULE(_C, m) {
                            eps, S(s)), "layernorm");
   });
   m.def("layernorm_lanes", &adapt::layernorm_lanes);
+  m.def("deconv_f32_mfma_ok", &adapt::deconv_f32_mfma_ok);
+  m.def("deconv_f32_forward", [](u64 x, u64 w, u64 b, u64 y, int B, int H, int W, int Cin, int OH, int OW, int Cout,
+                                 int KH, int KW, int Sd, int pt, int pl, int act, bool mfma, u64 s) {
+    adapt::DeconvF32Params p{P<const float>(x), P<const float>(w), P<const float>(b), P<float>(y), B, H, W, Cin, OH,
+                             OW, Cout, KH, KW, Sd, pt, pl, act};
+    check(adapt::deconv_f32_forward(p, mfma, S(s)), "deconv_f32_forward");
+  });
+  m.def("deconv_bf16_forward", [](u64 x, u64 w, u64 b, u64 y, int B, int H, int W, int Cin, int Cip, int OH, int OW,
+                                  int Cout, int Cop, int KH, int KW, int Sd, int pt, int pl, int act, u64 s) {
+    adapt::DeconvF32Params p{nullptr, nullptr, nullptr, nullptr, B, H, W, Cin, OH, OW, Cout, KH, KW, Sd, pt, pl, act};
+    check(adapt::deconv_bf16_forward(P<const bf16>(x), P<const float>(w), P<const float>(b), P<bf16>(y), p, Cip, Cop,
+                                     S(s)), "deconv_bf16_forward");
+  });
+  m.def("upsample_f32", [](u64 x, u64 y, int B, int H, int W, int C, int SH, int SW, bool bilinear, u64 s) {
+    check(adapt::upsample_f32(P<const float>(x), P<float>(y), B, H, W, C, SH, SW, bilinear, S(s)), "upsample_f32");
+  });
+  m.def("upsample_bf16", [](u64 x, u64 y, int B, int H, int W, int Cp, int C, int SH, int SW, bool bilinear, u64 s) {
+    check(adapt::upsample_bf16(P<const bf16>(x), P<bf16>(y), B, H, W, Cp, C, SH, SW, bilinear, S(s)),
+          "upsample_bf16");
+  });
+  m.def("crop_f32", [](u64 x, u64 y, int B, int H, int W, int C, int OH, int OW, int T, int L, u64 s) {
+    check(adapt::crop_f32(P<const float>(x), P<float>(y), B, H, W, C, OH, OW, T, L, S(s)), "crop_f32");
+  });
+  m.def("crop_bf16", [](u64 x, u64 y, int B, int H, int W, int Cp, int C, int OH, int OW, int T, int L, u64 s) {
+    check(adapt::crop_bf16(P<const bf16>(x), P<bf16>(y), B, H, W, Cp, C, OH, OW, T, L, S(s)), "crop_bf16");
+  });
   m.def("gconv_f32_mfma_ok", &adapt::gconv_f32_mfma_ok);
   m.def("gconv_f32_forward", [](u64 x, u64 w, u64 b, u64 y, int B, int H, int W, int Cin, int OH, int OW, int Cout,
                                 int G, int KH, int KW, int Sd, int pt, int pl, int act, bool mfma, u64 s) {

@@ -345,6 +345,32 @@ struct GconvF32Params {
   float* out;          // [B][OH][OW][Cout]
   int B, H, W, Cin, OH, OW, Cout, G, KH, KW, S, PT, PL, act;
 };
+// transposed convolution, NHWC (deconv_f32.hip): out = act(deconv(x) + bias), Keras Conv2DTranspose.
+// (PT, PL): where the output starts in the full scatter frame F[i*S + t] += x[i] * w[t]
+struct DeconvF32Params {
+  const float* x;      // [B][H][W][Cin]
+  const float* w;      // MFMA path: fragment-packed [S*S][Cout/16][ceil(KH/S)*ceil(KW/S)][Cin/16][64 lanes][4];
+                       // generic: [KH][KW][Cin][Cout]
+  const float* bias;   // [Cout]
+  float* out;          // [B][OH][OW][Cout]
+  int B, H, W, Cin, OH, OW, Cout, KH, KW, S, PT, PL, act;
+};
+bool deconv_f32_mfma_ok(int Cin, int Cout, int KH, int KW, int S);     // shape rule of the MFMA path
+// mfma: which path to launch (the caller packed w for it); an ineligible shape is an error, never a fall-through
+hipError_t deconv_f32_forward(const DeconvF32Params& p, bool mfma, hipStream_t s);
+// bf16 in / out with rows of Cip / Cop channels (padded to 8; padding is never read and written as zeros), the
+// generic path's fp32 weights [KH][KW][Cin][Cout] and bias; p.x / p.w / p.bias / p.out are not used
+hipError_t deconv_bf16_forward(const bf16* x, const float* w, const float* bias, bf16* out, const DeconvF32Params& p,
+                               int Cip, int Cop, hipStream_t s);
+// UpSampling2D (nearest / bilinear with half-pixel centres) and Cropping2D (resize.hip); bf16 rows are Cp wide
+// with channels C..Cp-1 written as zeros
+hipError_t upsample_f32(const float* x, float* y, int B, int H, int W, int C, int SH, int SW, int bilinear,
+                        hipStream_t s);
+hipError_t upsample_bf16(const bf16* x, bf16* y, int B, int H, int W, int Cp, int C, int SH, int SW, int bilinear,
+                         hipStream_t s);
+hipError_t crop_f32(const float* x, float* y, int B, int H, int W, int C, int OH, int OW, int T, int L, hipStream_t s);
+hipError_t crop_bf16(const bf16* x, bf16* y, int B, int H, int W, int Cp, int C, int OH, int OW, int T, int L,
+                     hipStream_t s);
 bool gconv_f32_mfma_ok(int Cin, int Cout, int G);     // shape rule of the MFMA path
 // mfma: which path to launch (the caller packed w for it); an ineligible shape is an error, never a fall-through
 hipError_t gconv_f32_forward(const GconvF32Params& p, bool mfma, hipStream_t s);

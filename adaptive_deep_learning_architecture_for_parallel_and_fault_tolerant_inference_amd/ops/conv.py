@@ -12,8 +12,9 @@ from __future__ import annotations
 
 import math
 import os
+from collections import namedtuple
 from dataclasses import dataclass
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -59,23 +60,6 @@ def halo_rows(cfg: int, pc: "PackedConv", H: int, W: int) -> int:
 _CFG_EFF = {0: 1.0, 4: 0.97, 1: 0.86, 2: 0.86, 3: 0.66, 5: 0.42}
 
 
-def cfg_supported(cfg: int, pc: "PackedConv", pure: bool) -> bool:
-    """v2 configs walk K tap-major in 64-channel slices: they need Cin % 64 == 0;
-    v3 (halo) configs take 3x3/s1/p1 convs only (the row count is checked at launch);
-    pointwise configs (PW_CFGS) take 1x1 stride-1 convs of the shapes pw_wide.hip has."""
-    if cfg in PW_CFGS:
-        return pure and pw_supported(pc)
-    if cfg in PS_CFGS:
-        return pure and ps_supported(pc, cfg)
-    if cfg in RR3_CFGS:
-        return rr3_supported(pc)
-    if cfg in CS3_CFGS:
-        return cs3_supported(pc)
-    if cfg in V1_CFGS:
-        return True
-    if cfg in HALO_PATCH:
-        return (pc.kh, pc.kw, pc.stride, pc.pad_t, pc.pad_l) == (3, 3, 1, 1, 1) and pc.cin % 64 == 0
-    return pc.cin % 64 == 0
 NUM_CUS = 256
 
 
@@ -185,16 +169,62 @@ def sk_plan(M: int, N: int, Kpad: int, cfg: int, mult: int = 1):
     return tiles, g, it, g * 2 * bm * bn
 
 
-def workspace_elems(M: int, N: int, Kpad: int, cfg: int, ksplit: int) -> int:
-    """fp32 workspace a launch needs: split-K slabs or stream-K partial slots (none for the sliced pointwise
-    configs, whose `ksplit` is a grid size)."""
-    if cfg in PS_CFGS:
-        return 0
-    if ksplit > 1:
-        return ksplit * M * N
-    if ksplit < 0:
-        return sk_plan(M, N, Kpad, cfg, -ksplit)[3]
-    return 0
+class ConvFamily(NamedTuple):
+    """The launch contract of one kernel family behind `conv_forward` / `conv_forward_f32`.  Everything that has
+    to agree about a config id (the entry points, the executor's scratch sizing, the tuners, the benches and the
+    guard-band tests) reads it from the family's record; `bf16_family` / `f32_family` find the record of an id."""
+    cfgs: tuple          # the family's config ids (fp32: in the order the tuner walks them; bf16: _BF16_TUNE_ORDER)
+    supported: Callable  # (cfg, pc, residual) -> bool: the family's kernel `cfg` takes this conv
+    units: Callable      # (cfg, B, H, W, pc) -> (tiles, K chunks) of a whole-K launch
+    ksplits: Callable    # (cfg, B, H, W, pc) -> the `ksplit` values the tuner tries, in its order
+    scratch: Callable    # (cfg, ksplit, B, H, W, pc) -> (fp32 workspace elements, int32 arrival counters), exact
+    launch: Callable     # (ConvCall) -> None: the family's own shape rules and its kernels() call
+
+
+# A checked call on its way to `ConvFamily.launch`: `ws` / `ctr` are device pointers (0: none needed)
+ConvCall = namedtuple("ConvCall", "x pc out residual relu out2 relu2 cfg ks B H W OH OW ws ctr stream")
+
+
+def _family_table(families) -> dict:
+    table = {cfg: fam for fam in families for cfg in fam.cfgs}
+    assert len(table) == sum(len(fam.cfgs) for fam in families), "a config id in two families"
+    return table
+
+
+def _out_mn(B: int, H: int, W: int, pc: "PackedConv"):
+    OH, OW = pc.out_hw(H, W)
+    return B * OH * OW, pc.cout
+
+
+class _FlatConv(NamedTuple):
+    """Stand-in conv for callers that know a launch only as a GEMM (M x N outputs, Kpad): the output "map"
+    it reports is what they passed, so the families' `scratch` sizes it as the real conv."""
+    cout: int
+    Kpad: int
+    oh: int
+    ow: int
+    cin: int = 0
+
+    def out_hw(self, h: int, w: int):
+        return self.oh, self.ow
+
+
+def _scratch_ptrs(need, workspace: Optional[torch.Tensor], counters: Optional[torch.Tensor], device):
+    """The one place a launch's scratch is checked against `ConvFamily.scratch`: (workspace pointer, counter
+    pointer), 0 where the launch needs none.  A missing workspace is allocated; counters must come zeroed."""
+    nws, nctr = need
+    ws_ptr = ctr_ptr = 0
+    if nws:
+        if workspace is None:
+            workspace = torch.empty(nws, dtype=torch.float32, device=device)
+        if workspace.numel() < nws or workspace.dtype != torch.float32:
+            raise ValueError(f"this config and ksplit need an fp32 workspace of {nws} elements")
+        ws_ptr = ptr(workspace)
+    if nctr:
+        if counters is None or counters.numel() < nctr or counters.dtype != torch.int32:
+            raise ValueError(f"this config and ksplit need {nctr} int32 arrival counters (zeroed)")
+        ctr_ptr = ptr(counters)
+    return ws_ptr, ctr_ptr
 
 
 def conv_forward(x: torch.Tensor, pc: PackedConv, out: torch.Tensor, residual: Optional[torch.Tensor] = None,
@@ -205,7 +235,7 @@ def conv_forward(x: torch.Tensor, pc: PackedConv, out: torch.Tensor, residual: O
     """x: [B,H,W,Cin] bf16 NHWC; out: [B,OH,OW,Cout] bf16 (or fp32 [M][Cout] for GEMM use).
 
     ksplit > 1: split-K (fp32 slabs + reduce launch); ksplit < 0: stream-K over
-    -ksplit x 256 blocks (v2 configs; needs `counters`, int32 zeros, one per tile).
+    -ksplit x 256 blocks (v2 configs; `counters`: int32 zeros, one per tile).  `bf16_scratch` sizes both.
     Dual output (``pc.n_split > 0``, two sibling convs packed along N): channels
     [0, n_split) go to `out` (ReLU `relu`), the rest to `out2` (ReLU `relu2`)."""
     if x.dim() == 2:
@@ -237,62 +267,16 @@ def conv_forward(x: torch.Tensor, pc: PackedConv, out: torch.Tensor, residual: O
         raise ValueError("residual must be bf16 with the output's shape")
     if cfg is None:
         cfg, ksplit = choose_cfg(M, N, pc.Kpad)
-    if cfg in RR3_CFGS:                    # register-resident-filter 3x3 (conv3x3_rr.hip)
-        if ksplit != 1 or ns or out_f32 or residual is not None or (H, W) != (28, 28) or OH != H or OW != W:
-            raise ValueError(f"3x3 config {cfg}: 28x28 stride-1 bf16 output, no residual / split-K")
-        rr3_forward(x, pc, out.view(x.shape[0], OH, OW, N), relu=int(relu), kg=RR3_CFGS[cfg], stream=stream)
-        return out
-    if cfg in CS3_CFGS:                    # channel-split register-resident 3x3 (conv3x3_cs.hip)
-        if ksplit != 1 or ns or out_f32 or residual is not None or OH != H or OW != W:
-            raise ValueError(f"3x3 config {cfg}: stride-1 bf16 output, no residual / split-K")
-        cs3_forward(x, pc, out.view(x.shape[0], OH, OW, N), relu=int(relu), stream=stream)
-        return out
-    if cfg in PS_CFGS:                     # channel-sliced persistent pointwise kernel (pw_slice.hip)
-        # no split-K: `ksplit` 1 / 2 is the grid, one or two blocks per CU (PS_GRIDS)
-        if ksplit not in PS_GRIDS or ns or out_f32 or OH != H or OW != W:
-            raise ValueError(f"pointwise config {cfg}: single bf16 output, ksplit 1 / 2 = blocks per CU")
-        return ps_forward(x.reshape(M, C), pc, out.view(M, N), None if residual is None else residual.view(M, N),
-                          relu=int(relu), cfg=cfg, blocks=NUM_CUS * ksplit, stream=stream)
-    if cfg in PW_CFGS:                     # persistent pointwise kernel (pw_wide.hip)
-        if ksplit != 1 or ns or out_f32 or OH != H or OW != W:
-            raise ValueError(f"pointwise config {cfg}: single bf16 output, no split-K")
-        return pw_forward(x.reshape(M, C), pc, out.view(M, N), None if residual is None else residual.view(M, N),
-                          relu=int(relu), cfg=cfg, blocks=NUM_CUS, stream=stream)
-    bm, bn = CFG_TILES[cfg]
-    if pc.w.shape[0] < math.ceil(N / bn) * bn:
-        raise ValueError("packed weights not padded to the tile's N")
-    if ns and ns % 8:
-        raise ValueError("dual-output split must be a multiple of 8 channels")
-    pure = pc.kh == 1 and pc.kw == 1 and pc.stride == 1 and pc.pad_t == 0 and pc.pad_l == 0 and OH == H and OW == W
-    if not cfg_supported(cfg, pc, pure):
-        raise ValueError(f"tile config {cfg} does not support this conv (Cin {pc.cin}, {pc.kh}x{pc.kw}/s{pc.stride})")
-    if ksplit == 0 or (ksplit < 0 and cfg in V1_CFGS) or (ksplit != 1 and cfg in HALO_PATCH):
-        raise ValueError(f"ksplit {ksplit} not supported by tile config {cfg}")
-    th = 0
-    if cfg in HALO_PATCH:
-        th = halo_rows(cfg, pc, H, W)
-        if th < 1:
-            raise ValueError(f"halo config {cfg} cannot tile a {H}x{W} 3x3 conv")
-    ws_ptr = ctr_ptr = 0
-    sk_iters = 0
-    need = workspace_elems(M, N, pc.Kpad, cfg, ksplit)
-    if need:
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.float32, device=x.device)
-        if workspace.numel() < need or workspace.dtype != torch.float32:
-            raise ValueError(f"ksplit {ksplit} needs an fp32 workspace of {need} elements")
-        ws_ptr = ptr(workspace)
-    if ksplit < 0:
-        tiles, _, sk_iters, _ = sk_plan(M, N, pc.Kpad, cfg, -ksplit)
-        if counters is None:
-            counters = torch.zeros(tiles, dtype=torch.int32, device=x.device)
-        if counters.numel() < tiles or counters.dtype != torch.int32:
-            raise ValueError(f"stream-K needs {tiles} int32 tile counters")
-        ctr_ptr = ptr(counters)
-    kernels().conv_forward(ptr(x), ptr(pc.w), ptr(pc.bias), ptr(residual), ptr(out), ws_ptr, ctr_ptr, sk_iters, th,
-                           B, H, W, C, OH, OW, N, pc.kh, pc.kw, pc.stride, pc.pad_t, pc.pad_l,
-                           pc.K, pc.Kpad, ns or N, int(relu), int(ksplit), int(cfg), bool(out_f32),
-                           stream_handle(stream), ptr(out2), int(ns), int(relu2))
+    cfg, ksplit = int(cfg), int(ksplit)
+    family = bf16_family(cfg)
+    if not family.supported(cfg, pc, residual is not None):
+        raise ValueError(f"config {cfg} does not support this conv (Cin {pc.cin}, {pc.kh}x{pc.kw}/s{pc.stride})")
+    need = family.scratch(cfg, ksplit, B, H, W, pc)
+    if need[1] and counters is None:
+        counters = torch.zeros(need[1], dtype=torch.int32, device=x.device)
+    ws_ptr, ctr_ptr = _scratch_ptrs(need, workspace, counters, x.device)
+    family.launch(ConvCall(x, pc, out, residual, int(relu), out2, int(relu2), cfg, ksplit, B, H, W, OH, OW,
+                           ws_ptr, ctr_ptr, stream))
     return out
 
 
@@ -439,20 +423,6 @@ def f32_sk_plan(M: int, N: int, Kpad: int, cfg: int, mult: int = 1):
     return tiles, g, it, g * 2 * bm * bn
 
 
-def workspace_elems_f32(M: int, N: int, Kpad: int, cfg: int, ksplit: int) -> int:
-    """fp32 workspace a launch needs: split-K slabs or stream-K partial slots
-    (Winograd ksplit < 0: -ksplit slabs, the fixup fused into the kernel)."""
-    if ksplit > 1:
-        return ksplit * M * N
-    if ksplit < 0:
-        if cfg in F32S_CFGS:
-            return f32s_ws_elems(cfg)
-        if cfg in WINO_F32_CFGS or cfg in WINO_F32_ABLATE:
-            return (4 if ksplit <= WINO_SK_BASE else -ksplit) * M * N    # stream-K: <= 4 partials per unit
-        return f32_sk_plan(M, N, Kpad, cfg, -ksplit)[3]
-    return 0
-
-
 def wino_sk_plan(cfg: int, B: int, H: int, W: int, N: int, C: int, ksplit: int):
     """(grid, iterations per block, most partials of one unit) of a stream-K Winograd launch."""
     return tuple(kernels().conv_wino_sk_plan(wino_blocks(cfg, B, H, W, N), C // 16, WINO_SK_BASE - ksplit))
@@ -471,22 +441,8 @@ def wino_sk_feasible(cfg: int, B: int, H: int, W: int, N: int, C: int, ksplit: i
 def wino_blocks(cfg: int, B: int, H: int, W: int, N: int) -> int:
     """Blocks per split of a Winograd launch (tile groups x channel groups): the fused split-K
     arrival counters it needs."""
-    nwm, fn = {**WINO_F32_CFGS, **WINO_F32_ABLATE}[cfg]
+    nwm, fn = _WINO_GEOM[cfg]
     return math.ceil(B * ((H + 1) // 2) * ((W + 1) // 2) / (16 * nwm)) * (N // (16 * fn))
-
-
-def f32_counter_elems(cfg: int, ksplit: int, B: int, H: int, W: int, OH: int, OW: int, N: int, Kpad: int) -> int:
-    """int32 arrival counters an fp32 launch needs: stream-K tiles (v2 GEMM configs) or fused
-    Winograd split-K blocks; 0 for plain launches."""
-    if ksplit >= 0:
-        return 0
-    if cfg in F32S_CFGS:
-        return f32s_tiles(cfg, B * OH * OW, N)
-    if cfg in WINO4S_F32_CFGS:
-        return int(kernels().wino4s_blocks(cfg, B, H, W, N))
-    if cfg in WINO_F32_CFGS or cfg in WINO_F32_ABLATE:
-        return wino_blocks(cfg, B, H, W, N)
-    return f32_sk_plan(B * OH * OW, N, Kpad, cfg, -ksplit)[0]
 
 
 # fp32 Winograd F(2x2, 3x3) configs (csrc/kernels/conv_wino_f32.hip ADAPT_WINO_CFGS): id -> (waves of 16
@@ -533,6 +489,7 @@ def wino_map_ok(cfg: int, H: int, W: int) -> bool:
 
 # cfg 80 with ablation switches (conv_wino_f32.hip ABL = id - 90): tools/conv_bench_f32.py only, never tuned
 WINO_F32_ABLATE = {90 + a: (4, 2) for a in (1, 2, 4, 5, 8, 9)}
+_WINO_GEOM = {**WINO_F32_CFGS, **WINO_F32_ABLATE}
 # B^T (input), G (weights) and A^T (output) of F(2x2, 3x3) (Lavin & Gray 2016)
 WINO_BT = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], np.float64)
 WINO_G = np.array([[1, 0, 0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0, 0, 1]], np.float64)
@@ -687,28 +644,6 @@ def pack_pw_f32(kernel_hwio: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(w.transpose(3, 0, 1, 4, 2).reshape(N // 16, K // 16, 64, 4).astype(np.float32))
 
 
-def f32_cfg_supported(cfg: int, cin: int, cout: int, pc: Optional["PackedConv"] = None,
-                      residual: bool = False) -> bool:
-    """Whether fp32 tile config `cfg` runs a conv with `cin` input / `cout` output channels
-    (Winograd configs also need the conv itself: 3x3 / s1 / p1 with its transformed weights;
-    the pointwise configs a 1x1 / s1 conv with its fragment-packed weights).  `residual`: the conv has a
-    fused residual input, which the F(4x4) split configs do not take."""
-    if cfg in PW_F32_CFGS:
-        return (pc is not None and pc.pwf is not None and PW_F32_CFGS[cfg] in PW_F32_BMS[pc.cin]
-                and pw_f32_shape_ok(pc, PW_F32_CFGS[cfg]))
-    if cfg in WINO4S_F32_CFGS:
-        return (not residual and pc is not None and pc.wino4s is not None and wino4s_supported(pc)
-                and bool(kernels().wino4s_ok(cfg, cin, cout, 1)))
-    if cfg in F32S_CFGS:
-        return pc is not None and f32s_supported(pc)
-    if cfg in WINO_F32_CFGS or cfg in WINO_F32_ABLATE:
-        fn = {**WINO_F32_CFGS, **WINO_F32_ABLATE}[cfg][1]
-        return pc is not None and pc.wino is not None and wino_supported(pc) and cout % (16 * fn) == 0
-    if cfg in F32G_CFGS:
-        return cin % F32_BK == 0 and cout % 4 == 0
-    return cfg in F32_TILES
-
-
 def pack_conv_f32(kernel_hwio: np.ndarray, bias: np.ndarray, stride: int, pads, device,
                   row_align: int = 256) -> PackedConv:
     """[Npad][Kpad] fp32 weights, k = (kh, kw, ci) with ci innermost; no channel padding."""
@@ -757,15 +692,255 @@ def choose_cfg_f32(M: int, N: int, Kpad: int, occupancy: int = 2):
     return best[1], best[2]
 
 
+# ---- fp32 kernel families: one ConvFamily record each
+_SPLITS_F32 = (1, 2, 4, 8, 16)
+
+
+def _f32_tile_units(cfg: int, B: int, H: int, W: int, pc: "PackedConv"):
+    M, N = _out_mn(B, H, W, pc)
+    bm, bn = F32_TILES[cfg]
+    return math.ceil(M / bm) * math.ceil(N / bn), pc.Kpad // F32_BK
+
+
+def _f32_tile_scratch(cfg: int, ks: int, B: int, H: int, W: int, pc: "PackedConv"):
+    """Split-K slabs, or stream-K partial slots and one arrival counter per tile."""
+    M, N = _out_mn(B, H, W, pc)
+    if ks > 1:
+        return ks * M * N, 0
+    if ks < 0:
+        tiles, _, _, ws = f32_sk_plan(M, N, pc.Kpad, cfg, -ks)
+        return ws, tiles
+    return 0, 0
+
+
+def _f32_tile_launch(c: ConvCall) -> None:
+    pc, N = c.pc, c.pc.cout
+    bn = F32_TILES[c.cfg][1]
+    if pc.w.shape[0] < math.ceil(N / bn) * bn or pc.Kpad % F32_BK:
+        raise ValueError("packed fp32 weights not padded to the tile")
+    kernels().conv_f32_forward(ptr(c.x), ptr(pc.w), ptr(pc.bias), ptr(c.residual), ptr(c.out), c.ws, c.B, c.H, c.W,
+                               pc.cin, c.OH, c.OW, N, pc.kh, pc.kw, pc.stride, pc.pad_t, pc.pad_l, pc.K, pc.Kpad,
+                               c.relu, c.ks, c.cfg, stream_handle(c.stream), c.ctr, ptr(c.out2), int(pc.n_split),
+                               c.relu2)
+
+
+def _f32_v1_launch(c: ConvCall) -> None:
+    if c.ks < 0:
+        raise ValueError("fp32 stream-K runs on the v2 configs only")
+    _f32_tile_launch(c)
+
+
+def _wino_supported(cfg: int, pc: "PackedConv", residual: bool) -> bool:
+    return pc.wino is not None and wino_supported(pc) and pc.cout % (16 * _WINO_GEOM[cfg][1]) == 0
+
+
+def _wino_units(cfg: int, B: int, H: int, W: int, pc: "PackedConv"):
+    return wino_blocks(cfg, B, H, W, pc.cout), pc.cin // 16
+
+
+def _wino_ksplits(cfg: int, B: int, H: int, W: int, pc: "PackedConv"):
+    if cfg in WINO_PU_CFGS:                  # persistent: whole K in one launch
+        return (1,)
+    if cfg in WINO_SK_CFGS:                  # stream-K twins: 1 or 2 x 256 blocks only
+        return (WINO_SK_BASE - 1, WINO_SK_BASE - 2)
+    return _SPLITS_F32 + (-2, -4)            # split-K over 16-channel chunks; fused split-K (<= 4 splits)
+
+
+def _wino_scratch(cfg: int, ks: int, B: int, H: int, W: int, pc: "PackedConv"):
+    """ksplit > 1: slabs; <= -2: -ksplit slabs, the fixup fused into the kernel; stream-K: <= 4 partials per
+    unit.  Every ksplit < 0 needs one arrival counter per block."""
+    M, N = _out_mn(B, H, W, pc)
+    slabs = 0 if ks == 1 else 4 if ks <= WINO_SK_BASE else abs(ks)
+    if slabs * M * N * 4 > 0x7fffffff:
+        raise ValueError("Winograd split-K slabs beyond 2 GiB")
+    return slabs * M * N, wino_blocks(cfg, B, H, W, N) if ks < 0 else 0
+
+
+def _wino_launch(c: ConvCall) -> None:
+    # ksplit > 1: slabs + splitk_reduce_f32; ksplit <= -2: -ksplit slabs, the last split of
+    # each block adds them in split order inside the kernel
+    # ksplit <= -100 (stream-K configs only): (-ksplit - 100) x 256 blocks over the (unit, chunk) space
+    cfg, ks, pc, C, N = c.cfg, c.ks, c.pc, c.pc.cin, c.pc.cout
+    sk = ks <= WINO_SK_BASE
+    if (c.OH, c.OW) != (c.H, c.W) or c.x.dim() != 4 or ks == -1 or not wino_map_ok(cfg, c.H, c.W) \
+            or sk != (cfg in WINO_SK_CFGS):
+        raise ValueError(f"Winograd config {cfg}: 3x3/s1/p1 conv on a 4-D input (v2 configs: rows of >= 4 tiles), "
+                         f"split-K >= 1 or fused split-K <= -2; stream-K configs {sorted(WINO_SK_CFGS)} take "
+                         f"ksplit <= {WINO_SK_BASE}")
+    if not sk and (abs(ks) > (C // 16) or ks < -4):
+        raise ValueError(f"Winograd split-K {ks} exceeds the {C // 16} channel chunks (fused: <= 4 splits)")
+    if cfg in WINO_PU_CFGS and ks != 1:
+        raise ValueError(f"persistent Winograd config {cfg} runs whole K only (ksplit 1)")
+    if sk and wino_sk_plan(cfg, c.B, c.H, c.W, N, C, ks)[2] > 4:
+        raise ValueError("Winograd stream-K would cut a unit into more than 4 partials")
+    kernels().conv_f32_forward(ptr(c.x), ptr(pc.wino), ptr(pc.bias), ptr(c.residual), ptr(c.out), c.ws, c.B, c.H,
+                               c.W, C, c.OH, c.OW, N, 3, 3, 1, 1, 1, pc.K, pc.Kpad, c.relu, ks, cfg,
+                               stream_handle(c.stream), c.ctr)
+
+
+def _wino4s_supported(cfg: int, pc: "PackedConv", residual: bool) -> bool:
+    return (not residual and pc.wino4s is not None and wino4s_supported(pc)
+            and bool(kernels().wino4s_ok(cfg, pc.cin, pc.cout, 1)))
+
+
+def _wino4s_units(cfg: int, B: int, H: int, W: int, pc: "PackedConv"):
+    return int(kernels().wino4s_blocks(cfg, B, H, W, pc.cout)), pc.cin // 16
+
+
+def _wino4s_ksplits(cfg: int, B: int, H: int, W: int, pc: "PackedConv"):
+    if cfg in WINO4S_ROW_CFGS:               # row split: whole K only
+        return (1,)
+    return _SPLITS_F32 + tuple(-k for k in wino4s_splits(pc.cin) if k > 1)     # split-K, fused fixup
+
+
+def _wino4s_scratch(cfg: int, ks: int, B: int, H: int, W: int, pc: "PackedConv"):
+    """V and the split-K partials (or the row split's half-transformed rows), whatever the split; the fused
+    split-K fixup (ksplit < 0) needs one arrival counter per (tile, channel) block."""
+    return (wino4s_ws_elems(B, H, W, pc.cin, pc.cout, ks, cfg),
+            _wino4s_units(cfg, B, H, W, pc)[0] if ks < 0 else 0)
+
+
+def _wino4s_launch(c: ConvCall) -> None:
+    # Winograd F(4x4, 3x3): input transform -> V (workspace), pure-MFMA GEMM with the output transform in
+    # its epilogue, and for ksplit > 1 the split-K reduce (bias / ReLU there)
+    cfg, ks, pc, C, N = c.cfg, c.ks, c.pc, c.pc.cin, c.pc.cout
+    if ((c.OH, c.OW) != (c.H, c.W) or c.x.dim() != 4 or not kernels().wino4s_ok(cfg, C, N, ks)
+            or not kernels().wino4s_range_ok(cfg, c.B, c.H, c.W, C, N, ks)):
+        raise ValueError(f"Winograd F(4x4) split config {cfg}: 3x3/s1/p1 conv on a 4-D input, N % (16 x WN) == 0, "
+                         f"|ksplit| in {wino4s_splits(C)} (fused: <= -2; row-split configs "
+                         f"{min(WINO4S_ROW_CFGS)}+: ksplit 1), V / U / slabs / rows below 2 GiB")
+    kernels().wino4s_forward(ptr(c.x), ptr(pc.wino4s), ptr(pc.bias), ptr(c.out), c.ws, c.B, c.H, c.W, C, N,
+                             c.relu, ks, cfg, stream_handle(c.stream), c.ctr)
+
+
+def _pw_f32_supported(cfg: int, pc: "PackedConv", residual: bool) -> bool:
+    return (pc.pwf is not None and PW_F32_CFGS[cfg] in PW_F32_BMS[pc.cin]
+            and pw_f32_shape_ok(pc, PW_F32_CFGS[cfg]))
+
+
+def _pw_f32_launch(c: ConvCall) -> None:
+    cfg, pc, N, ns = c.cfg, c.pc, c.pc.cout, int(c.pc.n_split)
+    M = c.B * c.OH * c.OW
+    if c.ks != 1 or c.x.dim() != 4:
+        raise ValueError(f"pointwise fp32 config {cfg}: 4-D input, ksplit 1")
+    if cfg in PW_F32_TAIL and not kernels().pw_f32_tail_plan(M, pc.cin, N, ns, PW_F32_CFGS[cfg])[0]:
+        raise ValueError(f"pointwise fp32 config {cfg}: no partial last tile round to split")
+    kernels().pw_f32_forward(ptr(c.x), ptr(pc.pwf), ptr(pc.bias), ptr(c.residual), ptr(c.out), M, pc.cin, N, c.relu,
+                             PW_F32_CFGS[cfg], stream_handle(c.stream), c.B, c.H, c.W, c.OH, c.OW, pc.stride,
+                             ptr(c.out2), ns, c.relu2)
+
+
+def _f32s_units(cfg: int, B: int, H: int, W: int, pc: "PackedConv"):
+    return f32s_tiles(cfg, *_out_mn(B, H, W, pc)), pc.cin // 32
+
+
+def _f32s_scratch(cfg: int, ks: int, B: int, H: int, W: int, pc: "PackedConv"):
+    return (f32s_ws_elems(cfg), _f32s_units(cfg, B, H, W, pc)[0]) if ks < 0 else (0, 0)
+
+
+def _f32s_launch(c: ConvCall) -> None:
+    # big-tile 1x1 GEMM: whole K per tile (ksplit 1) or stream-K over 256 blocks (ksplit -1)
+    pc = c.pc
+    if c.x.dim() != 4 or c.ks not in (1, -1):
+        raise ValueError(f"fp32 1x1 GEMM config {c.cfg}: 4-D input, ksplit 1 or -1")
+    kernels().conv_f32_forward(ptr(c.x), ptr(pc.w), ptr(pc.bias), ptr(c.residual), ptr(c.out), c.ws, c.B, c.H, c.W,
+                               pc.cin, c.OH, c.OW, pc.cout, 1, 1, pc.stride, 0, 0, pc.K, pc.Kpad, c.relu, c.ks, c.cfg,
+                               stream_handle(c.stream), c.ctr, ptr(c.out2), int(pc.n_split), c.relu2)
+
+
+F32_V1 = ConvFamily(tuple(c for c in F32_TILES if c not in F32G_CFGS), lambda cfg, pc, residual: True,
+                    _f32_tile_units, lambda cfg, B, H, W, pc: _SPLITS_F32, _f32_tile_scratch, _f32_v1_launch)
+F32_V2 = ConvFamily(tuple(c for c in F32_TILES if c in F32G_CFGS),
+                    lambda cfg, pc, residual: pc.cin % F32_BK == 0 and pc.cout % 4 == 0,
+                    _f32_tile_units, lambda cfg, B, H, W, pc: _SPLITS_F32 + (-1, -2), _f32_tile_scratch,
+                    _f32_tile_launch)
+F32_WINO = ConvFamily(tuple(_WINO_GEOM), _wino_supported, _wino_units, _wino_ksplits, _wino_scratch, _wino_launch)
+F32_WINO4S = ConvFamily(tuple(WINO4S_F32_CFGS), _wino4s_supported, _wino4s_units, _wino4s_ksplits, _wino4s_scratch,
+                        _wino4s_launch)
+# persistent / streaming pointwise: whole K, one launch, no scratch
+F32_PW = ConvFamily(tuple(PW_F32_CFGS), _pw_f32_supported, lambda cfg, B, H, W, pc: (0, 1),
+                    lambda cfg, B, H, W, pc: (1,), lambda cfg, ks, B, H, W, pc: (0, 0), _pw_f32_launch)
+F32_GEMM_S = ConvFamily(tuple(F32S_CFGS), lambda cfg, pc, residual: f32s_supported(pc), _f32s_units,
+                        lambda cfg, B, H, W, pc: (1, -1), _f32s_scratch, _f32s_launch)
+F32_FAMILIES = (F32_V1, F32_V2, F32_WINO, F32_WINO4S, F32_PW, F32_GEMM_S)
+_F32_FAMILY_OF = _family_table(F32_FAMILIES)
+# ablation and measurement builds, and the configs measured behind their rivals: launchable, never tuned
+_F32_NEVER_TUNED = frozenset(WINO_F32_ABLATE) | WINO_MEASURE_CFGS | F32_UNTUNED
+
+
+class _Channels(NamedTuple):
+    cin: int
+    cout: int
+
+
+def f32_family(cfg: int) -> ConvFamily:
+    try:
+        return _F32_FAMILY_OF[cfg]
+    except KeyError:
+        raise ValueError(f"unknown fp32 tile config {cfg}") from None
+
+
+def f32_cfg_supported(cfg: int, cin: int, cout: int, pc: Optional["PackedConv"] = None,
+                      residual: bool = False) -> bool:
+    """Whether fp32 config `cfg` runs a conv with `cin` input / `cout` output channels.  Only the plain tile
+    families can tell from the channel counts alone; every other family needs the conv `pc` itself (its shape
+    and its packed weights).  `residual`: the conv has a fused residual input, which the F(4x4) split configs
+    do not take."""
+    family = _F32_FAMILY_OF.get(cfg)
+    if family is None:
+        return False
+    if pc is None:
+        return family in (F32_V1, F32_V2) and family.supported(cfg, _Channels(cin, cout), residual)
+    return family.supported(cfg, pc, residual)
+
+
+def f32_scratch(cfg: int, ks: int, B: int, H: int, W: int, pc: "PackedConv"):
+    """(fp32 workspace elements, int32 arrival counters) of one fp32 launch: exactly what config `cfg` at
+    split `ks` needs on a B x H x W input of conv `pc`."""
+    return f32_family(cfg).scratch(cfg, ks, B, H, W, pc)
+
+
+def f32_candidates(B: int, H: int, W: int, pc: "PackedConv", residual: bool = False):
+    """The (cfg, ksplit) pairs the fp32 tuner times, in its order: every family's `ksplits`, with split-K /
+    stream-K only where the tiles alone leave CUs idle."""
+    for family in F32_FAMILIES:
+        for cfg in family.cfgs:
+            if cfg in _F32_NEVER_TUNED or not family.supported(cfg, pc, residual):
+                continue
+            tiles, kts = family.units(cfg, B, H, W, pc)
+            for ks in family.ksplits(cfg, B, H, W, pc):
+                if ks > 1 and (kts // ks < 2 or tiles >= 2 * NUM_CUS):
+                    continue
+                if ks < 0 and tiles >= 4 * NUM_CUS:
+                    continue
+                if family is F32_WINO and WINO_SK_BASE < ks < 0 and (kts // -ks < 2 or tiles >= 2 * NUM_CUS):
+                    continue                 # F(2x2)'s fused split-K is a split-K: pruned like one
+                yield cfg, ks
+
+
+# The sizing helpers from before the family records, for callers that hold a launch as (M, N, Kpad) and not as a
+# conv: the same `scratch` / `units`, asked through a stand-in conv.  New code calls f32_scratch.
+def workspace_elems_f32(M: int, N: int, Kpad: int, cfg: int, ksplit: int) -> int:
+    family = f32_family(cfg)
+    if family is F32_WINO4S:
+        raise ValueError("the F(4x4) workspace depends on the map: f32_scratch or wino4s_ws_elems")
+    return family.scratch(cfg, ksplit, 1, 1, M, _FlatConv(N, Kpad, 1, M))[0]
+
+
+def f32_counter_elems(cfg: int, ksplit: int, B: int, H: int, W: int, OH: int, OW: int, N: int, Kpad: int) -> int:
+    """One arrival counter per whole-K unit (tile or block) of a ksplit < 0 launch."""
+    return f32_family(cfg).units(cfg, B, H, W, _FlatConv(N, Kpad, OH, OW))[0] if ksplit < 0 else 0
+
+
 def conv_forward_f32(x: torch.Tensor, pc: PackedConv, out: torch.Tensor, residual: Optional[torch.Tensor] = None,
                      relu: int = 0, cfg: Optional[int] = None, ksplit: int = 1,
                      workspace: Optional[torch.Tensor] = None, stream=None,
                      counters: Optional[torch.Tensor] = None, out2: Optional[torch.Tensor] = None,
                      relu2: int = 0) -> torch.Tensor:
     """fp32 conv / GEMM: x [B,H,W,Cin] (or [M,K]) fp32 -> out [B,OH,OW,Cout] fp32, with
-    act(conv + bias (+ residual)) fused.  ksplit > 1: split-K, needs `workspace`
-    (ksplit*M*N fp32); ksplit < 0 (v2 configs): stream-K over -ksplit x 256 blocks,
-    needs `workspace` (workspace_elems_f32) and `counters` (int32 zeros, one per tile).
+    act(conv + bias (+ residual)) fused.  ksplit > 1: split-K; ksplit < 0: stream-K or a fused split-K fixup,
+    as the config's family defines it.  `f32_scratch` gives the `workspace` floats (allocated when absent) and
+    the `counters` (int32 zeros; every launch leaves them zero) such a launch needs.
     Dual output (``pc.n_split > 0``, two sibling 1x1 convs packed along N, no residual):
     channels [0, n_split) go to `out` (activation `relu`), the rest to `out2` (`relu2`)."""
     if x.dim() == 2:
@@ -799,121 +974,15 @@ def conv_forward_f32(x: torch.Tensor, pc: PackedConv, out: torch.Tensor, residua
         raise ValueError("conv epilogue activation must be 0 (none), 1 (ReLU) or 2 (ReLU6)")
     if cfg is None:
         cfg, ksplit = choose_cfg_f32(M, N, pc.Kpad)
-    if cfg in PW_F32_CFGS:
-        if not f32_cfg_supported(cfg, C, N, pc) or int(ksplit or 1) != 1 or x.dim() != 4:
-            raise ValueError(f"pointwise fp32 config {cfg}: 1x1 / s1-2 conv, K in {sorted(PW_F32_FPW)}, "
-                             f"N (and the dual-output split) a multiple of the slice, ksplit 1")
-        if cfg in PW_F32_TAIL and not kernels().pw_f32_tail_plan(M, C, N, int(ns), PW_F32_CFGS[cfg])[0]:
-            raise ValueError(f"pointwise fp32 config {cfg}: no partial last tile round to split")
-        kernels().pw_f32_forward(ptr(x), ptr(pc.pwf), ptr(pc.bias), ptr(residual), ptr(out), M, C, N, int(relu),
-                                 PW_F32_CFGS[cfg], stream_handle(stream), B, H, W, OH, OW, pc.stride, ptr(out2),
-                                 int(ns), int(relu2))
-        return out
-    if cfg in F32S_CFGS:
-        # big-tile 1x1 GEMM: whole K per tile (ksplit 1) or stream-K over 256 blocks (ksplit -1)
-        ksplit = int(ksplit) or 1
-        if not f32_cfg_supported(cfg, C, N, pc) or x.dim() != 4 or ksplit not in (1, -1):
-            raise ValueError(f"fp32 1x1 GEMM config {cfg}: 1x1 / pad 0 / stride 1-2 conv, Cin % 32 == 0, "
-                             f"N % 16 == 0, ksplit 1 or -1")
-        ws_ptr = ctr_ptr = 0
-        if ksplit < 0:
-            need = f32s_ws_elems(cfg)
-            if workspace is None:
-                workspace = torch.empty(need, dtype=torch.float32, device=x.device)
-            if workspace.numel() < need or workspace.dtype != torch.float32:
-                raise ValueError(f"fp32 1x1 GEMM stream-K needs an fp32 workspace of {need} elements")
-            nt = f32s_tiles(cfg, M, N)
-            if counters is None or counters.numel() < nt or counters.dtype != torch.int32:
-                raise ValueError(f"fp32 1x1 GEMM stream-K needs {nt} int32 tile counters (zeroed)")
-            ws_ptr, ctr_ptr = ptr(workspace), ptr(counters)
-        kernels().conv_f32_forward(ptr(x), ptr(pc.w), ptr(pc.bias), ptr(residual), ptr(out), ws_ptr, B, H, W,
-                                   C, OH, OW, N, 1, 1, pc.stride, 0, 0, pc.K, pc.Kpad, int(relu), ksplit, int(cfg),
-                                   stream_handle(stream), ctr_ptr, ptr(out2), int(ns), int(relu2))
-        return out
-    if cfg in WINO4S_F32_CFGS:
-        # Winograd F(4x4, 3x3): input transform -> V (workspace), pure-MFMA GEMM with the output transform in
-        # its epilogue, and for ksplit > 1 the split-K reduce (bias / ReLU there)
-        ksplit = int(ksplit) or 1
-        if (not f32_cfg_supported(cfg, C, N, pc, residual is not None) or (OH, OW) != (H, W) or x.dim() != 4
-                or not kernels().wino4s_ok(cfg, C, N, ksplit)
-                or not kernels().wino4s_range_ok(cfg, B, H, W, C, N, ksplit)):
-            raise ValueError(f"Winograd F(4x4) split config {cfg}: 3x3/s1/p1 conv with wino4s weights, C % 16 == 0, "
-                             f"N % (16 x WN) == 0, no residual, |ksplit| in {wino4s_splits(C)} (fused: <= -2; "
-                             f"row-split configs {min(WINO4S_ROW_CFGS)}+: ksplit 1), V / U / slabs / rows below 2 GiB")
-        need = wino4s_ws_elems(B, H, W, C, N, ksplit, cfg)
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.float32, device=x.device)
-        if workspace.numel() < need or workspace.dtype != torch.float32:
-            raise ValueError(f"Winograd F(4x4) split needs an fp32 workspace of {need} elements")
-        ctr_ptr = 0
-        if ksplit < 0:                       # fused split-K fixup: one arrival counter per (tile, channel) block
-            nb = int(kernels().wino4s_blocks(cfg, B, H, W, N))
-            if counters is None or counters.numel() < nb or counters.dtype != torch.int32:
-                raise ValueError(f"Winograd F(4x4) fused split-K needs {nb} int32 arrival counters (zeroed)")
-            ctr_ptr = ptr(counters)
-        kernels().wino4s_forward(ptr(x), ptr(pc.wino4s), ptr(pc.bias), ptr(out), ptr(workspace), B, H, W, C, N,
-                                 int(relu), ksplit, int(cfg), stream_handle(stream), ctr_ptr)
-        return out
-    if cfg in WINO_F32_CFGS or cfg in WINO_F32_ABLATE:
-        # ksplit > 1: slabs + splitk_reduce_f32; ksplit <= -2: -ksplit slabs, the last split of
-        # each block adds them in split order inside the kernel (needs `counters`)
-        # ksplit <= -100 (stream-K configs only): (-ksplit - 100) x 256 blocks over the (unit, chunk) space
-        ksplit = int(ksplit) or 1
-        sk = ksplit <= WINO_SK_BASE
-        if not f32_cfg_supported(cfg, C, N, pc) or (OH, OW) != (H, W) or x.dim() != 4 or ksplit == -1 \
-                or not wino_map_ok(cfg, H, W) or sk != (cfg in WINO_SK_CFGS):
-            raise ValueError(f"Winograd config {cfg}: 3x3/s1/p1 conv with transformed weights, C % 16 == 0, "
-                             f"N % 16 * fragments == 0, split-K >= 1 or fused split-K <= -2; stream-K configs "
-                             f"{sorted(WINO_SK_CFGS)} take ksplit <= {WINO_SK_BASE}")
-        if not sk and (abs(ksplit) > (C // 16) or ksplit < -4):
-            raise ValueError(f"Winograd split-K {ksplit} exceeds the {C // 16} channel chunks (fused: <= 4 splits)")
-        if cfg in WINO_PU_CFGS and ksplit != 1:
-            raise ValueError(f"persistent Winograd config {cfg} runs whole K only (ksplit 1)")
-        if sk and wino_sk_plan(cfg, B, H, W, N, C, ksplit)[2] > 4:
-            raise ValueError("Winograd stream-K would cut a unit into more than 4 partials")
-        ws_ptr = ctr_ptr = 0
-        if ksplit != 1:
-            need = workspace_elems_f32(M, N, pc.Kpad, cfg, ksplit)
-            if need * 4 > 0x7fffffff:
-                raise ValueError("Winograd split-K slabs beyond 2 GiB")
-            if workspace is None:
-                workspace = torch.empty(need, dtype=torch.float32, device=x.device)
-            if workspace.numel() < need or workspace.dtype != torch.float32:
-                raise ValueError(f"Winograd split-K {ksplit} needs an fp32 workspace of {need} elements")
-            ws_ptr = ptr(workspace)
-        if ksplit < 0:
-            nb = wino_blocks(cfg, B, H, W, N)
-            if counters is None or counters.numel() < nb or counters.dtype != torch.int32:
-                raise ValueError(f"Winograd fused split-K / stream-K needs {nb} int32 arrival counters (zeroed)")
-            ctr_ptr = ptr(counters)
-        kernels().conv_f32_forward(ptr(x), ptr(pc.wino), ptr(pc.bias), ptr(residual), ptr(out), ws_ptr, B, H, W, C,
-                                   OH, OW, N, 3, 3, 1, 1, 1, pc.K, pc.Kpad, int(relu), ksplit, int(cfg),
-                                   stream_handle(stream), ctr_ptr)
-        return out
-    if cfg not in F32_TILES:
-        raise ValueError(f"unknown fp32 tile config {cfg}")
-    bm, bn = F32_TILES[cfg]
-    if pc.w.shape[0] < math.ceil(N / bn) * bn or pc.Kpad % F32_BK:
-        raise ValueError("packed fp32 weights not padded to the tile")
-    ws_ptr = ctr_ptr = 0
-    ksplit = int(ksplit) or 1
-    if ksplit < 0:
-        if cfg not in F32G_CFGS:
-            raise ValueError("fp32 stream-K runs on the v2 configs only")
-        tiles = f32_sk_plan(M, N, pc.Kpad, cfg, -ksplit)[0]
-        if counters is None or counters.numel() < tiles or counters.dtype != torch.int32:
-            raise ValueError(f"fp32 stream-K needs {tiles} int32 tile counters")
-        ctr_ptr = ptr(counters)
-    if ksplit != 1:
-        need = workspace_elems_f32(M, N, pc.Kpad, cfg, ksplit)
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.float32, device=x.device)
-        if workspace.numel() < need or workspace.dtype != torch.float32:
-            raise ValueError(f"ksplit {ksplit} needs an fp32 workspace of {need} elements")
-        ws_ptr = ptr(workspace)
-    kernels().conv_f32_forward(ptr(x), ptr(pc.w), ptr(pc.bias), ptr(residual), ptr(out), ws_ptr, B, H, W, C, OH, OW,
-                               N, pc.kh, pc.kw, pc.stride, pc.pad_t, pc.pad_l, pc.K, pc.Kpad, int(relu),
-                               ksplit, int(cfg), stream_handle(stream), ctr_ptr, ptr(out2), int(ns), int(relu2))
+    cfg, ksplit = int(cfg), int(ksplit) or 1
+    family = f32_family(cfg)
+    if not family.supported(cfg, pc, residual is not None):
+        raise ValueError(f"fp32 config {cfg} does not take this conv ({pc.kh}x{pc.kw}/s{pc.stride}, {C} -> {N} "
+                         f"channels{', fused residual' if residual is not None else ''}) as it is packed")
+    need = family.scratch(cfg, ksplit, B, H, W, pc)
+    ws_ptr, ctr_ptr = _scratch_ptrs(need, workspace, counters, x.device)
+    family.launch(ConvCall(x, pc, out, residual, int(relu), out2, int(relu2), cfg, ksplit, B, H, W, OH, OW,
+                           ws_ptr, ctr_ptr, stream))
     return out
 
 
@@ -1029,6 +1098,157 @@ def cs3_forward(x: torch.Tensor, pc: "PackedConv", out: torch.Tensor, relu: int 
     kernels().conv3x3_cs_forward(ptr(x), ptr(pw_fragments(pc)), ptr(pc.bias), ptr(out), B, H, W, C, int(relu),
                                  stream_handle(stream))
     return out
+
+
+# ------------------------------------------------------- bf16 kernel families
+def _tile_units(cfg: int, B: int, H: int, W: int, pc: "PackedConv"):
+    M, N = _out_mn(B, H, W, pc)
+    bm, bn = CFG_TILES[cfg]
+    return math.ceil(M / bm) * math.ceil(N / bn), pc.Kpad // BK
+
+
+def _tile_scratch(cfg: int, ks: int, B: int, H: int, W: int, pc: "PackedConv"):
+    """Split-K slabs, or stream-K partial slots and one arrival counter per tile."""
+    M, N = _out_mn(B, H, W, pc)
+    if ks > 1:
+        return ks * M * N, 0
+    if ks < 0:
+        tiles, _, _, ws = sk_plan(M, N, pc.Kpad, cfg, -ks)
+        return ws, tiles
+    return 0, 0
+
+
+def _no_scratch(cfg, ks, B, H, W, pc):
+    return 0, 0
+
+
+def _tile_launch(c: ConvCall, th: int = 0) -> None:
+    pc, N, ns = c.pc, c.pc.cout, c.pc.n_split
+    if pc.w.shape[0] < math.ceil(N / CFG_TILES[c.cfg][1]) * CFG_TILES[c.cfg][1]:
+        raise ValueError("packed weights not padded to the tile's N")
+    if ns and ns % 8:
+        raise ValueError("dual-output split must be a multiple of 8 channels")
+    if c.ks == 0:
+        raise ValueError(f"ksplit 0 not supported by tile config {c.cfg}")
+    sk_iters = sk_plan(c.B * c.OH * c.OW, N, pc.Kpad, c.cfg, -c.ks)[2] if c.ks < 0 else 0
+    kernels().conv_forward(ptr(c.x), ptr(pc.w), ptr(pc.bias), ptr(c.residual), ptr(c.out), c.ws, c.ctr, sk_iters, th,
+                           c.B, c.H, c.W, pc.cin, c.OH, c.OW, N, pc.kh, pc.kw, pc.stride, pc.pad_t, pc.pad_l,
+                           pc.K, pc.Kpad, ns or N, c.relu, c.ks, c.cfg, c.out.dtype == torch.float32,
+                           stream_handle(c.stream), ptr(c.out2), int(ns), c.relu2)
+
+
+def _v1_launch(c: ConvCall) -> None:
+    if c.ks < 0:
+        raise ValueError(f"ksplit {c.ks} not supported by tile config {c.cfg} (stream-K: v2 configs)")
+    _tile_launch(c)
+
+
+def _halo_supported(cfg: int, pc: "PackedConv", residual: bool) -> bool:
+    return (pc.kh, pc.kw, pc.stride, pc.pad_t, pc.pad_l) == (3, 3, 1, 1, 1) and pc.cin % 64 == 0
+
+
+def _halo_launch(c: ConvCall) -> None:
+    th = halo_rows(c.cfg, c.pc, c.H, c.W)
+    if c.ks != 1 or th < 1:
+        raise ValueError(f"halo config {c.cfg} cannot tile a {c.H}x{c.W} 3x3 conv (whole K only)")
+    _tile_launch(c, th)
+
+
+def _resident_ok(c: ConvCall, what: str, grids=(1,)):
+    """The register-resident kernels write one bf16 output of the input's size; `ksplit` is not a K split."""
+    if c.ks not in grids or c.pc.n_split or c.out.dtype == torch.float32 or (c.OH, c.OW) != (c.H, c.W):
+        raise ValueError(f"{what} config {c.cfg}: single stride-1 bf16 output, ksplit in {grids}")
+    M = c.B * c.OH * c.OW
+    return c.x.reshape(M, c.pc.cin), c.out.view(M, c.pc.cout), None if c.residual is None else \
+        c.residual.view(M, c.pc.cout)
+
+
+def _pw_launch(c: ConvCall) -> None:
+    x, out, res = _resident_ok(c, "pointwise")
+    pw_forward(x, c.pc, out, res, relu=c.relu, cfg=c.cfg, blocks=NUM_CUS, stream=c.stream)
+
+
+def _ps_launch(c: ConvCall) -> None:
+    # no split-K: `ksplit` 1 / 2 is the grid, one or two blocks per CU (PS_GRIDS)
+    x, out, res = _resident_ok(c, "sliced pointwise", PS_GRIDS)
+    ps_forward(x, c.pc, out, res, relu=c.relu, cfg=c.cfg, blocks=NUM_CUS * c.ks, stream=c.stream)
+
+
+def _rr3_launch(c: ConvCall) -> None:
+    _resident_ok(c, "3x3")
+    if c.residual is not None or (c.H, c.W) != (28, 28):
+        raise ValueError(f"3x3 config {c.cfg}: 28x28 maps, no residual")
+    rr3_forward(c.x, c.pc, c.out.view(c.B, c.OH, c.OW, c.pc.cout), relu=c.relu, kg=RR3_CFGS[c.cfg], stream=c.stream)
+
+
+def _cs3_launch(c: ConvCall) -> None:
+    _resident_ok(c, "3x3")
+    if c.residual is not None:
+        raise ValueError(f"3x3 config {c.cfg}: no residual")
+    cs3_forward(c.x, c.pc, c.out.view(c.B, c.OH, c.OW, c.pc.cout), relu=c.relu, stream=c.stream)
+
+
+_RING_KSPLITS = (1, 2, 3, 4, 6, 8, -1, -2)
+BF16_V1 = ConvFamily(V1_CFGS, lambda cfg, pc, residual: True, _tile_units,
+                     lambda cfg, B, H, W, pc: (1, 2, 3, 4, 6, 8), _tile_scratch, _v1_launch)
+# v2 configs walk K tap-major in 64-channel slices: they need Cin % 64 == 0
+BF16_RING = ConvFamily(tuple(c for c in CFG_TILES if c not in V1_CFGS and c not in HALO_PATCH),
+                       lambda cfg, pc, residual: pc.cin % 64 == 0, _tile_units,
+                       lambda cfg, B, H, W, pc: _RING_KSPLITS, _tile_scratch, _tile_launch)
+# v3 (halo) configs take 3x3/s1/p1 convs, whole K only: the tuner offers them the ring's splits all the same
+# (the launch turns them down), and `scratch` answers for those as a tile config would
+BF16_HALO = ConvFamily(tuple(HALO_PATCH), _halo_supported, _tile_units,
+                       lambda cfg, B, H, W, pc: _RING_KSPLITS, _tile_scratch, _halo_launch)
+_RESIDENT_UNITS = lambda cfg, B, H, W, pc: (0, pc.Kpad // BK)      # noqa: E731  (persistent grids: no tiles)
+BF16_PW_WIDE = ConvFamily(tuple(PW_CFGS), lambda cfg, pc, residual: pw_supported(pc), _RESIDENT_UNITS,
+                          lambda cfg, B, H, W, pc: (1,), _no_scratch, _pw_launch)
+BF16_PW_SLICE = ConvFamily(tuple(PS_CFGS), lambda cfg, pc, residual: ps_supported(pc, cfg), _RESIDENT_UNITS,
+                           lambda cfg, B, H, W, pc: PS_GRIDS, _no_scratch, _ps_launch)
+BF16_RR3 = ConvFamily(tuple(RR3_CFGS), lambda cfg, pc, residual: rr3_supported(pc), _RESIDENT_UNITS,
+                      lambda cfg, B, H, W, pc: (1,), _no_scratch, _rr3_launch)
+BF16_CS3 = ConvFamily(tuple(CS3_CFGS), lambda cfg, pc, residual: cs3_supported(pc), _RESIDENT_UNITS,
+                      lambda cfg, B, H, W, pc: (1,), _no_scratch, _cs3_launch)
+BF16_FAMILIES = (BF16_V1, BF16_RING, BF16_HALO, BF16_PW_WIDE, BF16_PW_SLICE, BF16_RR3, BF16_CS3)
+_BF16_FAMILY_OF = _family_table(BF16_FAMILIES)
+# the tuner's walk: the tile table in id order (ring ids lie on both sides of the halo ids), then the resident kernels
+_BF16_TUNE_ORDER = tuple(CFG_TILES) + BF16_PW_WIDE.cfgs + BF16_PW_SLICE.cfgs + BF16_RR3.cfgs + BF16_CS3.cfgs
+
+
+def bf16_family(cfg: int) -> ConvFamily:
+    try:
+        return _BF16_FAMILY_OF[cfg]
+    except KeyError:
+        raise ValueError(f"unknown bf16 conv config {cfg}") from None
+
+
+def cfg_supported(cfg: int, pc: "PackedConv", pure: bool = True) -> bool:
+    """Whether bf16 config `cfg` takes this conv (the halo configs' row count is checked at launch).  `pure`
+    (a 1x1 / s1 / p0 conv) is what the pointwise families ask of `pc` themselves."""
+    family = _BF16_FAMILY_OF.get(cfg)
+    return family is not None and family.supported(cfg, pc, False)
+
+
+def bf16_scratch(cfg: int, ks: int, B: int, H: int, W: int, pc: "PackedConv"):
+    """(fp32 workspace elements, int32 arrival counters) of one bf16 launch."""
+    return bf16_family(cfg).scratch(cfg, ks, B, H, W, pc)
+
+
+def workspace_elems(M: int, N: int, Kpad: int, cfg: int, ksplit: int) -> int:
+    """`bf16_scratch` workspace floats for callers that hold (M, N, Kpad) only (as workspace_elems_f32)."""
+    return bf16_family(cfg).scratch(cfg, ksplit, 1, 1, M, _FlatConv(N, Kpad, 1, M))[0]
+
+
+def bf16_candidates(B: int, H: int, W: int, pc: "PackedConv", residual: bool = False):
+    """The (cfg, ksplit) pairs the bf16 tuner times, in its order: split-K only where a split keeps two K tiles."""
+    for cfg in _BF16_TUNE_ORDER:
+        family = bf16_family(cfg)
+        if not family.supported(cfg, pc, residual):
+            continue
+        _, kts = family.units(cfg, B, H, W, pc)
+        for ks in family.ksplits(cfg, B, H, W, pc):
+            if ks > 1 and kts // ks < 2:
+                continue
+            yield cfg, ks
 
 
 # ------------------------------------------------------- fused bottleneck

@@ -20,7 +20,6 @@ allocator and the stream / graph API only.
 from __future__ import annotations
 
 import json
-import math
 import os
 import threading
 from collections import ChainMap
@@ -507,24 +506,12 @@ class SliceExecutor:
         return B, H, W, C, OH, OW, pc
 
     def _ensure_ws(self) -> None:
+        scratch = conv_ops.f32_scratch if self.fp32 else conv_ops.bf16_scratch
         need = ctr = 0
         for i, (cfg, ks) in self.cfg.items():
-            if self.fp32:
-                if cfg in conv_ops.WINO4S_F32_CFGS:        # V and the split-K partials, whatever the split
-                    B, H, W, C, OH, OW, pc = self._conv_geom(i)
-                    need = max(need, conv_ops.wino4s_ws_elems(B, H, W, C, pc.cout, ks, cfg))
-                    ctr = max(ctr, conv_ops.f32_counter_elems(cfg, ks, B, H, W, OH, OW, pc.cout, pc.Kpad))
-                    continue
-                if ks != 1:
-                    B, H, W, C, OH, OW, pc = self._conv_geom(i)
-                    need = max(need, conv_ops.workspace_elems_f32(B * OH * OW, pc.cout, pc.Kpad, cfg, ks))
-                    ctr = max(ctr, conv_ops.f32_counter_elems(cfg, ks, B, H, W, OH, OW, pc.cout, pc.Kpad))
-                continue
-            if ks != 1:
-                B, H, W, C, OH, OW, pc = self._conv_geom(i)
-                need = max(need, conv_ops.workspace_elems(B * OH * OW, pc.cout, pc.Kpad, cfg, ks))
-                if ks < 0:
-                    ctr = max(ctr, conv_ops.sk_plan(B * OH * OW, pc.cout, pc.Kpad, cfg, -ks)[0])
+            B, H, W, _, _, _, pc = self._conv_geom(i)
+            nws, nctr = scratch(cfg, ks, B, H, W, pc)
+            need, ctr = max(need, nws), max(ctr, nctr)
         if need and (self._ws is None or self._ws.numel() < need):
             self._ws = torch.empty(need, dtype=torch.float32, device=self.device)
             if self._side:                     # side-stream convs must not share scratch with the main stream
@@ -563,12 +550,13 @@ class SliceExecutor:
             self.autotune_f32() if self.fp32 else self.autotune(verbose=os.environ.get("ADAPT_TUNE_VERBOSE", "0") == "1")
 
     @staticmethod
-    def _time_graph(fn, reps: int) -> float:
-        """ms per call of `fn`, `reps` calls captured in one hipGraph (device time only)."""
+    def _time_graph(fn, reps: int, stream=None) -> float:
+        """ms per call of `fn`, `reps` calls captured in one hipGraph (device time only); `stream`: the
+        stream to capture on."""
         fn()
         torch.cuda.synchronize()
         gg = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gg):
+        with torch.cuda.graph(gg, stream=stream):
             for _ in range(reps):
                 fn()
         gg.replay()
@@ -580,104 +568,16 @@ class SliceExecutor:
         e.synchronize()
         return s.elapsed_time(e) / (3 * reps)
 
-    def autotune_f32(self, reps: int = 10, persist: bool = True, refine: int = 3,
-                     verbose: bool = False) -> Dict[str, List]:
-        """fp32 path: time every (tile cfg, split-K) of conv_f32.hip per conv
-        problem in isolation and keep the fastest ("f32|" keys in the table);
-        then (refine > 1) re-decide each problem among its `refine` best isolated
-        candidates by replaying the whole captured slice, as the bf16 tuner does
-        (round 5: the 98-row GEMM tile cfg 307 is 5 % slower than the ring kernel
-        in isolation and 10 us per batch faster in the model)."""
-        results: Dict[str, List] = {}
-        done: Dict[str, Tuple[int, int]] = {}
-        ranked: Dict[str, List[Tuple[float, int, int]]] = {}
-        prev = dict(load_tuning())
-        for i, st in enumerate(self.steps):
-            if st.kind not in ("conv", "dense") or i in self._dense_part:
-                continue
-            B, H, W, C, OH, OW, pc = self._conv_geom(i)
-            M, N = B * OH * OW, pc.cout
-            key = "f32|" + conv_key(B, H, W, C, pc)
-            if key in done:
-                self.cfg[i] = done[key]
-                continue
-            x = torch.randn(self.bufs(0)[st.ins[0]].shape, device=self.device)
-            ns = pc.n_split                       # merged sibling convs write two outputs
-            out = torch.empty(M * (ns or N), dtype=torch.float32, device=self.device)
-            out2 = torch.empty(M * (N - ns), dtype=torch.float32, device=self.device) if ns else None
-            ktiles = pc.Kpad // conv_ops.F32_BK
-            best = None
-            for cfg in (list(conv_ops.F32_TILES) + list(conv_ops.WINO_F32_CFGS) + list(conv_ops.WINO4S_F32_CFGS)
-                        + list(conv_ops.PW_F32_CFGS) + list(conv_ops.F32S_CFGS)):
-                if (not conv_ops.f32_cfg_supported(cfg, C, pc.cout, pc, len(st.ins) > 1)
-                        or cfg in conv_ops.WINO_MEASURE_CFGS
-                        or cfg in conv_ops.F32_UNTUNED):
-                    continue
-                if cfg in conv_ops.WINO4S_F32_CFGS:       # F(4x4) transform + GEMM: split-K, fused fixup
-                    sp = [k for k in conv_ops.wino4s_splits(C) if k > 1]
-                    tiles, kts, sks = int(conv_ops.kernels().wino4s_blocks(cfg, B, H, W, N)), C // 16, \
-                        tuple(-k for k in sp)
-                    if cfg in conv_ops.WINO4S_ROW_CFGS:   # row split: whole K only
-                        kts, sks = 1, ()
-                elif cfg in conv_ops.PW_F32_CFGS:            # persistent pointwise: whole K, one launch
-                    tiles, kts, sks = 0, 1, ()
-                elif cfg in conv_ops.F32S_CFGS:             # big-tile 1x1 GEMM: tiles, or stream-K over 256
-                    tiles, kts, sks = conv_ops.f32s_tiles(cfg, M, N), C // 32, (-1,)
-                elif cfg in conv_ops.WINO_F32_CFGS:         # Winograd F(2x2,3x3): split-K over 16-channel chunks
-                    nwm, fn = conv_ops.WINO_F32_CFGS[cfg]
-                    tiles = math.ceil(B * ((OH + 1) // 2) * ((OW + 1) // 2) / (16 * nwm)) * (N // (16 * fn))
-                    kts, sks = C // 16, (-2, -4)          # fused split-K (fixup in the kernel, <= 4 splits)
-                    if cfg in conv_ops.WINO_SK_CFGS:       # stream-K twins: 1 or 2 x 256 blocks only
-                        kts, sks = C // 16, (conv_ops.WINO_SK_BASE - 1, conv_ops.WINO_SK_BASE - 2)
-                    if cfg in conv_ops.WINO_PU_CFGS:       # persistent: whole K in one launch
-                        kts, sks = 1, ()
-                else:
-                    bm, bn = conv_ops.F32_TILES[cfg]
-                    tiles = math.ceil(M / bm) * math.ceil(N / bn)
-                    kts = ktiles
-                    sks = (-1, -2) if cfg in conv_ops.F32G_CFGS else ()
-                for ks in ((1,) if cfg in conv_ops.PW_F32_CFGS or cfg in conv_ops.F32S_CFGS else
-                           (1, 2, 4, 8, 16) if cfg not in conv_ops.WINO_SK_CFGS else ()) + sks:
-                    # split-K / stream-K only where the tiles alone leave CUs idle
-                    if ks > 1 and (kts // ks < 2 or tiles >= 2 * conv_ops.NUM_CUS):
-                        continue
-                    if ks < 0 and tiles >= 4 * conv_ops.NUM_CUS:
-                        continue
-                    if -100 < ks < 0 and cfg in conv_ops.WINO_F32_CFGS and (kts // -ks < 2 or tiles >= 2 * conv_ops.NUM_CUS):
-                        continue
-                    nws = (conv_ops.wino4s_ws_elems(B, H, W, C, N, ks, cfg) if cfg in conv_ops.WINO4S_F32_CFGS
-                           else conv_ops.workspace_elems_f32(M, N, pc.Kpad, cfg, ks))
-                    ws = torch.empty(nws, dtype=torch.float32, device=self.device) if nws else None
-                    nctr = conv_ops.f32_counter_elems(cfg, ks, B, H, W, OH, OW, N, pc.Kpad)
-                    ctr = torch.zeros(nctr, dtype=torch.int32, device=self.device) if nctr else None
-                    try:
-                        t = self._time_graph(lambda: conv_ops.conv_forward_f32(x, pc, out, cfg=cfg, ksplit=ks,
-                                                                               workspace=ws, counters=ctr,
-                                                                               out2=out2), reps)
-                    except (RuntimeError, ValueError):
-                        continue
-                    ranked.setdefault(key, []).append((t, cfg, ks))
-                    if best is None or t < best[0]:
-                        best = (t, cfg, ks)
-            if best:
-                results[key] = [best[1], best[2], round(best[0] * 1000, 2)]
-                done[key] = (best[1], best[2])
-                self.cfg[i] = (best[1], best[2])
-                if verbose:
-                    print(f"autotune {key}: cfg {best[1]} ksplit {best[2]} {best[0] * 1000:.2f} us", flush=True)
-        self._ensure_ws()
-        refine = int(os.environ.get("ADAPT_TUNE_REFINE", refine))
-        if refine > 1 and ranked:
-            self._refine_in_graph(ranked, results, refine, prev, verbose, prefix="f32|")
-        if persist:
-            save_tuning(results)
-        return results
-
-    def autotune(self, reps: int = 20, persist: bool = True, refine: int = 3, verbose: bool = False) -> Dict[str, List]:
-        """Time every (tile cfg, split-K) candidate per conv problem in isolation,
-        then (refine > 1) re-decide each problem among its `refine` best
-        candidates by replaying the WHOLE captured slice: isolated timings miss
-        how a kernel's tail and grid overlap with its neighbours."""
+    def _autotune(self, reps: int, persist: bool, refine: int, verbose: bool) -> Dict[str, List]:
+        """Both tuners: time every candidate (conv_ops.f32_candidates / bf16_candidates, in their order: the
+        first of equal timings is kept) of each distinct conv problem in isolation, with scratch of exactly
+        the contract's size, then refine in the whole captured slice."""
+        if self.fp32:
+            prefix, dtype, stream = "f32|", torch.float32, None
+            candidates, scratch, forward = conv_ops.f32_candidates, conv_ops.f32_scratch, conv_ops.conv_forward_f32
+        else:
+            prefix, dtype, stream = "", torch.bfloat16, self._capture_stream()
+            candidates, scratch, forward = conv_ops.bf16_candidates, conv_ops.bf16_scratch, conv_ops.conv_forward
         results: Dict[str, List] = {}
         done: Dict[str, Tuple[int, int]] = {}
         ranked: Dict[str, List[Tuple[float, int, int]]] = {}
@@ -687,58 +587,27 @@ class SliceExecutor:
                 continue
             B, H, W, C, OH, OW, pc = self._conv_geom(i)
             M, N = B * OH * OW, pc.cout
-            key = conv_key(B, H, W, C, pc)
+            key = prefix + conv_key(B, H, W, C, pc)
             if key in done:
                 self.cfg[i] = done[key]
                 continue
-            x = torch.randn(self.bufs(0)[st.ins[0]].shape, device=self.device).to(torch.bfloat16)
+            x = torch.randn(self.bufs(0)[st.ins[0]].shape, device=self.device).to(dtype)
             ns = pc.n_split                       # merged sibling convs write two outputs
-            out = torch.empty(M * (ns or N), dtype=torch.bfloat16, device=self.device)
-            extra = {"out2": torch.empty(M * (N - ns), dtype=torch.bfloat16, device=self.device)} if ns else {}
+            out = torch.empty(M * (ns or N), dtype=dtype, device=self.device)
+            out2 = torch.empty(M * (N - ns), dtype=dtype, device=self.device) if ns else None
             best = None
-            ktiles = pc.Kpad // conv_ops.BK
-            resident = (list(conv_ops.PW_CFGS) + list(conv_ops.PS_CFGS) + list(conv_ops.RR3_CFGS)
-                        + list(conv_ops.CS3_CFGS))
-            for cfg in list(conv_ops.CFG_TILES) + resident:
-                for ks in (1, 2, 3, 4, 6, 8, -1, -2):
-                    if cfg in conv_ops.PS_CFGS:              # ks = blocks per CU for the sliced pointwise
-                        if ks not in conv_ops.PS_GRIDS:
-                            continue
-                    elif cfg in resident and ks != 1:
-                        continue
-                    if ks > 1 and ktiles // ks < 2:
-                        continue
-                    if ks < 0 and cfg in conv_ops.V1_CFGS:
-                        continue
-                    try:
-                        need = conv_ops.workspace_elems(M, N, pc.Kpad, cfg, ks)
-                        ws = torch.empty(need, dtype=torch.float32, device=self.device) if need else None
-                        ctr = None
-                        if ks < 0:
-                            ctr = torch.zeros(conv_ops.sk_plan(M, N, pc.Kpad, cfg, -ks)[0], dtype=torch.int32,
-                                              device=self.device)
-                        conv_ops.conv_forward(x, pc, out, cfg=cfg, ksplit=ks, workspace=ws, counters=ctr, **extra)
-                        torch.cuda.synchronize(self.device)
-                        # time device work only: `reps` launches captured in one hipGraph
-                        gg = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(gg, stream=self._capture_stream()):
-                            for _ in range(reps):
-                                conv_ops.conv_forward(x, pc, out, cfg=cfg, ksplit=ks, workspace=ws, counters=ctr,
-                                                      **extra)
-                        gg.replay()
-                        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        s.record()
-                        for _ in range(3):
-                            gg.replay()
-                        e.record()
-                        e.synchronize()
-                        t = s.elapsed_time(e) / (3 * reps)
-                        del gg
-                    except (RuntimeError, ValueError):
-                        continue
-                    ranked.setdefault(key, []).append((t, cfg, ks))
-                    if best is None or t < best[0]:
-                        best = (t, cfg, ks)
+            for cfg, ks in candidates(B, H, W, pc, len(st.ins) > 1):
+                try:
+                    nws, nctr = scratch(cfg, ks, B, H, W, pc)
+                    ws = torch.empty(nws, dtype=torch.float32, device=self.device) if nws else None
+                    ctr = torch.zeros(nctr, dtype=torch.int32, device=self.device) if nctr else None
+                    t = self._time_graph(lambda: forward(x, pc, out, cfg=cfg, ksplit=ks, workspace=ws, counters=ctr,
+                                                         out2=out2), reps, stream)
+                except (RuntimeError, ValueError):
+                    continue
+                ranked.setdefault(key, []).append((t, cfg, ks))
+                if best is None or t < best[0]:
+                    best = (t, cfg, ks)
             if best:
                 results[key] = [best[1], best[2], round(best[0] * 1000, 2)]
                 done[key] = (best[1], best[2])
@@ -750,10 +619,27 @@ class SliceExecutor:
         # are re-timed inside the whole captured slice
         refine = int(os.environ.get("ADAPT_TUNE_REFINE", refine))
         if refine > 1 and ranked:
-            self._refine_in_graph(ranked, results, refine, prev, verbose)
+            self._refine_in_graph(ranked, results, refine, prev, verbose, prefix=prefix)
         if persist:
             save_tuning(results)
         return results
+
+    def autotune_f32(self, reps: int = 10, persist: bool = True, refine: int = 3,
+                     verbose: bool = False) -> Dict[str, List]:
+        """fp32 path: time every (config, split-K) candidate per conv
+        problem in isolation and keep the fastest ("f32|" keys in the table);
+        then (refine > 1) re-decide each problem among its `refine` best isolated
+        candidates by replaying the whole captured slice, as the bf16 tuner does
+        (round 5: the 98-row GEMM tile cfg 307 is 5 % slower than the ring kernel
+        in isolation and 10 us per batch faster in the model)."""
+        return self._autotune(reps, persist, refine, verbose)
+
+    def autotune(self, reps: int = 20, persist: bool = True, refine: int = 3, verbose: bool = False) -> Dict[str, List]:
+        """Time every (tile cfg, split-K) candidate per conv problem in isolation,
+        then (refine > 1) re-decide each problem among its `refine` best
+        candidates by replaying the WHOLE captured slice: isolated timings miss
+        how a kernel's tail and grid overlap with its neighbours."""
+        return self._autotune(reps, persist, refine, verbose)
 
     def _graph_time(self, rounds: int = 5, reps: int = 10) -> float:
         """Median ms per replay of the whole slice, freshly captured."""

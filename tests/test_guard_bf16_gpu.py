@@ -2,7 +2,7 @@
 
 Same harness and the same four assertions as tests/test_guard_f32_gpu.py: each launch runs once with NaN and once
 with +inf in the guards of everything it reads (uint8 inputs: 0xFF bytes), outputs pre-filled with NaN, scratch of
-exactly `workspace_elems` / `sk_plan` tiles / `dense_small_scratch` / `gap_scratch_elems`; all guards intact,
+exactly `bf16_scratch` (workspace floats, `sk_plan` tile counters) / `dense_small_scratch` / `gap_scratch_elems`; all guards intact,
 outputs finite and bit-identical between the two runs, stream-K counters back to zero, and the result within the
 family's existing budget of a float64 reference computed from the bf16-rounded inputs and weights.
 
@@ -143,11 +143,11 @@ def _guarded_conv(c, cfg, ksplit, relu2=1):
     specs = [((c.B, c.OH, c.OW, ns or c.Cout), BF16)] + ([((c.B, c.OH, c.OW, c.Cout - ns), BF16)] if ns else [])
 
     def launch(dev, outs, poison):
-        ws = _scratch(C.workspace_elems(c.M, c.Cout, c.Kpad, cfg, ksplit), poison)
+        nws, nctr = C.bf16_scratch(cfg, ksplit, c.B, c.H, c.W, c.pc[poison])
+        ws = _scratch(nws, poison)
         ctr = None
         if ksplit < 0:
-            ctr = G.guarded(C.sk_plan(c.M, c.Cout, c.Kpad, cfg, -ksplit)[0], torch.int32, "cuda", payload=0,
-                            name="counters")
+            ctr = G.guarded(nctr, torch.int32, "cuda", payload=0, name="counters")
         for _rep in range(2 if ctr is not None else 1):      # the second launch meets the first one's counters
             C.conv_forward(dev["x"], c.pc[poison], outs[0], dev.get("residual"), relu=c.relu, cfg=cfg, ksplit=ksplit,
                            workspace=ws, counters=ctr, out2=outs[1] if ns else None, relu2=relu2)
@@ -196,7 +196,7 @@ def _mode_ok(shape, ksplit):
 @pytest.mark.parametrize("shape,ksplit", [(s, k) for s in CONV_SHAPES for k in (1, 2, -1) if _mode_ok(s, k)])
 def test_guard_conv_bf16_tiles(shape, ksplit):
     """Every id in CFG_TILES (v1, the LDS-DMA v2 families incl. 62-70, the halo kernel); ksplit 2: split-K
-    slabs; -1: stream-K with exactly `workspace_elems` floats and `sk_plan` tile counters."""
+    slabs; -1: stream-K with exactly the `bf16_scratch` floats and `sk_plan` tile counters."""
     c = _conv_case(shape)
     ran = 0
     for cfg in sorted(C.CFG_TILES):

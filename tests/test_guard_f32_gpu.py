@@ -3,7 +3,7 @@
 Each (family, config, split mode, shape) is launched twice, once with NaN and once with +inf in the guards of
 everything it reads (activations, residuals, packed weights, biases, and the workspace, which is also written),
 with outputs pre-filled with NaN and scratch of exactly the size the project's contract functions promise
-(`workspace_elems_f32`, `f32_counter_elems`, `wino4s_ws_elems`, `f32s_ws_elems`, `dense_small_f32_scratch`,
+(`f32_scratch`: workspace floats and arrival counters of the config and split launched; `dense_small_f32_scratch`,
 `gap_scratch_elems`).  Asserted per launch:
 
 1. every guard of every buffer handed to the launch is intact, bit for bit;
@@ -131,12 +131,6 @@ def _conv_case(shape, n_split=0):
     return c
 
 
-def _ws_elems(c, cfg, ksplit):
-    if cfg in C.WINO4S_F32_CFGS:
-        return C.wino4s_ws_elems(c.B, c.H, c.W, c.Cin, c.Cout, ksplit)
-    return C.workspace_elems_f32(c.M, c.Cout, c.Kpad, cfg, ksplit)
-
-
 def _guarded_conv(c, cfg, ksplit, budget=2e-5, rel=_rel1, relu2=1):
     """One config / split mode on one case, under both poisons; the four assertions of the module docstring."""
     label = f"cfg {cfg} ksplit {ksplit} shape {c.shape}"
@@ -146,8 +140,8 @@ def _guarded_conv(c, cfg, ksplit, budget=2e-5, rel=_rel1, relu2=1):
         x, res, pc = c.dev[poison]
         out = _out((c.B, c.OH, c.OW, ns or c.Cout))
         out2 = _out((c.B, c.OH, c.OW, c.Cout - ns), "out2") if ns else None
-        ws = _scratch(_ws_elems(c, cfg, ksplit), poison)
-        ctr = _counters(C.f32_counter_elems(cfg, ksplit, c.B, c.H, c.W, c.OH, c.OW, c.Cout, c.Kpad))
+        nws, nctr = C.f32_scratch(cfg, ksplit, c.B, c.H, c.W, pc)
+        ws, ctr = _scratch(nws, poison), _counters(nctr)
         for _rep in range(2 if ctr is not None else 1):      # the second launch meets the first one's counters
             C.conv_forward_f32(x, pc, out, res, relu=c.relu, cfg=cfg, ksplit=ksplit, workspace=ws, counters=ctr,
                                out2=out2, relu2=relu2)

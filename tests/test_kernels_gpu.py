@@ -349,10 +349,10 @@ def test_conv_dual_output_matches_two_convs(ops, cfg, ks, shape):
     o0, o1 = torch.full_like(r0, 7.0), torch.full_like(r1, 7.0)
     ws = ctr = None
     if cfg is not None:
-        need = conv.workspace_elems(M, N0 + N1, pcd.Kpad, cfg, ks)
+        need, nctr = conv.bf16_scratch(cfg, ks, B, H, W, pcd)
         ws = torch.empty(max(need, 1), device=dev, dtype=torch.float32)
         if ks < 0:
-            ctr = torch.zeros(conv.sk_plan(M, N0 + N1, pcd.Kpad, cfg, -ks)[0], device=dev, dtype=torch.int32)
+            ctr = torch.zeros(nctr, device=dev, dtype=torch.int32)
     if cfg is not None and ks > 1 and pcd.Kpad // 64 // ks < 1:
         pytest.skip("K too short to split")
     conv.conv_forward(x, pcd, o0, relu=False, cfg=cfg, ksplit=ks, workspace=ws, counters=ctr, out2=o1, relu2=True)

@@ -84,7 +84,7 @@ def test_wino_f32_stream_k_v3_blocks_meet_two_units():
         grid, iters, smax = C.wino_sk_plan(cfg, B, H, W, Cout, Cin, -101)
         assert iters == 2 and (Cin // 16) % iters and C.wino_sk_feasible(cfg, B, H, W, Cout, Cin, -101)
         ctr = torch.zeros(C.wino_blocks(cfg, B, H, W, Cout), dtype=torch.int32, device="cuda")
-        ws = torch.empty(C.workspace_elems_f32(B * H * W, Cout, pc.Kpad, cfg, -101), device="cuda")
+        ws = torch.empty(C.f32_scratch(cfg, -101, B, H, W, pc)[0], device="cuda")
         for rep in range(2):
             out.fill_(float("nan"))
             C.conv_forward_f32(xd, pc, out, relu=1, cfg=cfg, ksplit=-101, workspace=ws, counters=ctr)

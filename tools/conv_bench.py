@@ -41,43 +41,40 @@ def bench(shape, only=None, reps=20, ks_list=(1, 2, 3, 4, 6, 8, -1, -2)):
     flop = 2.0 * M * N * pc.K
     byts = (x.numel() + M * N * (2 if has_res else 1)) * 2 + pc.w.numel() * 2
     rows = []
-    pure = k == 1 and s == 1 and p == 0
-    for cfg in (only or C.CFG_TILES):
-        if not C.cfg_supported(cfg, pc, pure):
+    if only:                  # named configs: every split their family knows
+        pairs = [(cfg, ks) for cfg in only if C.cfg_supported(cfg, pc)
+                 for ks in C.bf16_family(cfg).ksplits(cfg, B, H, W, pc)]
+    else:                     # what the tuner would time
+        pairs = list(C.bf16_candidates(B, H, W, pc, bool(has_res)))
+    for cfg, ks in pairs:
+        if ks not in ks_list:
             continue
-        for ks in ks_list:
-            if ks > 1 and pc.Kpad // 64 // ks < 2:
-                continue
-            if ks < 0 and cfg in C.V1_CFGS:
-                continue
-            if ks != 1 and cfg not in C.CFG_TILES:      # register-resident / persistent kernels: whole K only
-                continue
-            need = C.workspace_elems(M, N, pc.Kpad, cfg, ks) if cfg in C.CFG_TILES else 0
-            ws = torch.empty(need, device=dev, dtype=torch.float32) if need else None
-            ctr = torch.zeros(C.sk_plan(M, N, pc.Kpad, cfg, -ks)[0], device=dev, dtype=torch.int32) if ks < 0 else None
-            try:
-                C.conv_forward(x, pc, out, residual=res, relu=True, cfg=cfg, ksplit=ks, workspace=ws, counters=ctr)
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    for _ in range(reps):
-                        C.conv_forward(x, pc, out, residual=res, relu=True, cfg=cfg, ksplit=ks, workspace=ws,
-                                       counters=ctr)
+        need, nctr = C.bf16_scratch(cfg, ks, B, H, W, pc)
+        ws = torch.empty(need, device=dev, dtype=torch.float32) if need else None
+        ctr = torch.zeros(nctr, device=dev, dtype=torch.int32) if nctr else None
+        try:
+            C.conv_forward(x, pc, out, residual=res, relu=True, cfg=cfg, ksplit=ks, workspace=ws, counters=ctr)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for _ in range(reps):
+                    C.conv_forward(x, pc, out, residual=res, relu=True, cfg=cfg, ksplit=ks, workspace=ws,
+                                   counters=ctr)
+            g.replay()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
                 g.replay()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(5):
-                    g.replay()
-                e1.record()
-                e1.synchronize()
-                t = e0.elapsed_time(e1) / (5 * reps) * 1e3
-            except (RuntimeError, ValueError) as e:
-                print("skip", cfg, ks, e)
-                continue
-            bm, bn = C.CFG_TILES.get(cfg, (0, 0))
-            blocks = (C.sk_plan(M, N, pc.Kpad, cfg, -ks)[1] if ks < 0 else
-                      math.ceil(M / bm) * math.ceil(N / bn) * ks if bm else 0)
-            rows.append((t, cfg, ks, blocks))
+            e1.record()
+            e1.synchronize()
+            t = e0.elapsed_time(e1) / (5 * reps) * 1e3
+        except (RuntimeError, ValueError) as e:
+            print("skip", cfg, ks, e)
+            continue
+        bm, bn = C.CFG_TILES.get(cfg, (0, 0))
+        blocks = (C.sk_plan(M, N, pc.Kpad, cfg, -ks)[1] if ks < 0 else
+                  math.ceil(M / bm) * math.ceil(N / bn) * ks if bm else 0)
+        rows.append((t, cfg, ks, blocks))
     rows.sort()
     print(f"\n== B{B} {H}x{W}x{Cin} -> {Cout} k{k} s{s}  M={M} N={N} K={pc.K}  "
           f"{flop / 1e9:.2f} GFLOP {byts / 1e6:.1f} MB")

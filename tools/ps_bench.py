@@ -33,7 +33,7 @@ def bench_shape(M, K, N, has_res, rounds):
     for cfg in IGEMM:
         if C.cfg_supported(cfg, pc, True):
             for ks in (1, 2):
-                need = C.workspace_elems(M, N, pc.Kpad, cfg, ks)
+                need = C.bf16_scratch(cfg, ks, 1, 1, M, pc)[0]
                 ws = torch.empty(need, dtype=torch.float32, device="cuda") if need else None
                 variants[f"igemm cfg {cfg} ks {ks}"] = (
                     lambda c=cfg, k=ks, w=ws: C.conv_forward(x, pc, out, r, relu=1, cfg=c, ksplit=k, workspace=w))

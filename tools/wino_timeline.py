@@ -41,9 +41,8 @@ def main():
     pc = C.pack_conv_f32(kern, np.zeros(Cout, np.float32), 1, ((1, 1), (1, 1)), dev)
     M, N = B * H * W, Cout
     out = torch.empty(M * N, device=dev)
-    nws = C.workspace_elems_f32(M, N, pc.Kpad, a.cfg, a.ks)
+    nws, nctr = C.f32_scratch(a.cfg, a.ks, B, H, W, pc)
     ws = torch.empty(nws, device=dev) if nws else None
-    nctr = C.f32_counter_elems(a.cfg, a.ks, B, H, W, H, W, N, pc.Kpad)
     ctr = torch.zeros(nctr, device=dev, dtype=torch.int32) if nctr else None
     nw, fn = C.WINO_F32_CFGS[a.cfg]
     T = B * ((H + 1) // 2) * ((W + 1) // 2)

@@ -48,6 +48,9 @@ OPS = (
                   # activation; kernel (kh, kw, filters, cin) (Keras HWOI), no output_padding, no dilation
     "upsample",   # Keras UpSampling2D: size=(sh,sw), interpolation ('nearest' | 'bilinear', half-pixel centres)
     "crop",       # Keras Cropping2D: crop=((t,b),(l,r))
+    "mha",        # Keras MultiHeadAttention as self-attention over all positions: num_heads, key_dim, value_dim
+                  # (absent means key_dim), use_bias; input (H, W, C) or (T, C), output the same shape
+    "posembed",   # ViT class token + learned position embedding: attrs class_token; (H, W, C) -> (1, T + ct, C)
 )
 
 # activations the runtime executes (fused into conv / dense / eltwise epilogues,
@@ -80,10 +83,40 @@ def depthwise_kernel(weights, name: str):
 def conv_kernel(weights, p: Dict):
     """HWIO kernel of a conv step's layer `p["conv"]`; a Dense on (H, W, C) (p["dense"]) keeps the Keras
     (cin, units) shape in the weights and is a 1x1 kernel here."""
+    if p.get("mha"):
+        k = mha_projection(weights, p["conv"], p, p["mha"])[0]
+        return k.reshape((1, 1) + tuple(k.shape))
     k = weights[f"{p['conv']}/kernel"]
     if p.get("deconv"):         # Conv2DTranspose keeps Keras' (kh, kw, filters, cin); packers and BN folding want
         return k.transpose(0, 1, 3, 2)      # the output channels last: (kh, kw, cin, filters)
     return k.reshape((1, 1) + tuple(k.shape)) if p.get("dense") else k
+
+
+def conv_bias(weights, p: Dict):
+    """Bias of a conv step's layer `p["conv"]`, or None."""
+    if p.get("mha"):
+        return mha_projection(weights, p["conv"], p, p["mha"])[1]
+    return weights.get(f"{p['conv']}/bias")
+
+
+def mha_projection(weights, name: str, head: Dict, part: str):
+    """(kernel, bias or None) of the two GEMMs around the attention core of MultiHeadAttention layer `name`;
+    `head` holds heads, key_dim, value_dim.  part "qkv": the query / key / value projections side by side,
+    (C, h * (2 d + dv)) ordered [Q | K | V] and head-major inside each, with Keras' 1/sqrt(key_dim) query scale
+    folded into the Q columns and the Q bias.  part "out": the output projection (h * dv, C)."""
+    import numpy as np
+    h, d, dv = head["heads"], head["key_dim"], head["value_dim"]
+    if part == "out":
+        return (weights[f"{name}/attention_output/kernel"].reshape(h * dv, -1),
+                weights.get(f"{name}/attention_output/bias"))
+    scale = {"query": 1.0 / np.sqrt(np.float64(d)), "key": 1.0, "value": 1.0}
+    ks = [(weights[f"{name}/{q}/kernel"].astype(np.float64) * scale[q]).reshape(-1, h * w)
+          for q, w in (("query", d), ("key", d), ("value", dv))]
+    kernel = np.concatenate(ks, axis=1).astype(np.float32)
+    if f"{name}/query/bias" not in weights:
+        return kernel, None
+    bs = [(weights[f"{name}/{q}/bias"].astype(np.float64) * scale[q]).reshape(-1) for q in ("query", "key", "value")]
+    return kernel, np.concatenate(bs).astype(np.float32)
 
 
 def same_pads(size: int, k: int, s: int) -> Tuple[int, int]:
@@ -95,6 +128,14 @@ def same_pads(size: int, k: int, s: int) -> Tuple[int, int]:
 
 def _pair(v) -> Tuple[int, int]:
     return (v, v) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def _tokens(shape: Sequence[int]) -> int:
+    """Positions of a per-image (H, W, C) or (T, C) tensor: everything but the channel axis."""
+    t = 1
+    for d in shape[:-1]:
+        t *= d
+    return t
 
 
 def deconv_out_len(size: int, k: int, s: int, padding: str) -> int:
@@ -159,6 +200,21 @@ class Layer:
             return [(f"{self.name}/{n}", (c,)) for n, k in keep if k]
         if self.op == "layerscale":
             return [(f"{self.name}/gamma", (in_shapes[0][-1],))]
+        if self.op == "mha":
+            c, h, d = in_shapes[0][-1], self.attrs["num_heads"], self.attrs["key_dim"]
+            dv = self.attrs.get("value_dim") or d
+            out = []
+            for part, shp, bshp in (("query", (c, h, d), (h, d)), ("key", (c, h, d), (h, d)),
+                                    ("value", (c, h, dv), (h, dv)), ("attention_output", (h, dv, c), (c,))):
+                out.append((f"{self.name}/{part}/kernel", shp))
+                if self.attrs.get("use_bias", True):
+                    out.append((f"{self.name}/{part}/bias", bshp))
+            return out
+        if self.op == "posembed":
+            t, c = _tokens(in_shapes[0]), in_shapes[0][-1]
+            ct = 1 if self.attrs.get("class_token") else 0
+            return ([(f"{self.name}/class_token", (1, 1, c))] if ct else []) + [
+                (f"{self.name}/position_embedding", (t + ct, c))]
         if self.op == "dense":
             cin = in_shapes[0][-1]
             out = [(f"{self.name}/kernel", (cin, self.attrs["units"]))]
@@ -186,6 +242,11 @@ class Layer:
             for d in in_shapes[0][:-1]:         # a Dense on (H, W, C) is a GEMM per pixel
                 px *= d
             return px * in_shapes[0][-1] * self.attrs["units"]
+        if self.op == "mha":                    # projections, Q K^T and P V, output projection
+            t, c = _tokens(in_shapes[0]), in_shapes[0][-1]
+            h, d = self.attrs["num_heads"], self.attrs["key_dim"]
+            dv = self.attrs.get("value_dim") or d
+            return t * c * h * (2 * d + dv) + t * t * h * (d + dv) + t * h * dv * c
         return 0
 
     def to_json(self) -> Dict:
@@ -244,6 +305,17 @@ class Graph:
                     or layer.attrs.get("interpolation", "nearest") not in ("nearest", "bilinear")):
                 raise ValueError(f"upsample {layer.name!r}: size must be two positive ints and interpolation "
                                  f"'nearest' or 'bilinear' (got {sz}, {layer.attrs.get('interpolation')!r})")
+        if layer.op == "mha":
+            rank = len(self.layers[layer.inputs[0]].out_shape)
+            if (len(layer.inputs) != 1 or rank not in (2, 3) or int(layer.attrs.get("num_heads", 0)) < 1
+                    or int(layer.attrs.get("key_dim", 0)) < 1 or int(layer.attrs.get("value_dim") or 1) < 1):
+                raise ValueError(f"mha {layer.name!r}: needs one input of rank 2 or 3 (got rank {rank}), "
+                                 f"num_heads >= 1 and key_dim >= 1 (got {layer.attrs.get('num_heads')}, "
+                                 f"{layer.attrs.get('key_dim')})")
+        if layer.op == "posembed":
+            shp = self.layers[layer.inputs[0]].out_shape
+            if len(shp) != 3:
+                raise ValueError(f"posembed {layer.name!r}: needs an (H, W, C) or (1, T, C) input, got {shp}")
         if layer.op == "crop" and layer.out_shape:
             self._infer_shape(layer)                # an empty result is refused even with a given shape
         layer.out_shape = tuple(layer.out_shape) or self._infer_shape(layer)
@@ -287,8 +359,10 @@ class Graph:
                 raise ValueError(f"crop {layer.name!r}: {a['crop']} leaves nothing of {ins[0]}")
             return (h - t - b, w - l - r, c)
         if layer.op in ("bn", "relu", "softmax", "identity", "act", "rescale", "normalization", "layernorm",
-                        "layerscale"):
+                        "layerscale", "mha"):
             return ins[0]
+        if layer.op == "posembed":
+            return (1, _tokens(ins[0]) + (1 if a.get("class_token") else 0), ins[0][-1])
         if layer.op == "binary":
             return ins[0]
         if layer.op == "reshape":

@@ -57,6 +57,68 @@ def _inbound_names(layer: Dict[str, Any]) -> List[str]:
     return [entry[0] for entry in node]               # Keras 2: [[name, node, tensor, kwargs], ...]
 
 
+_MHA_ARGS = ("query", "value", "key", "attention_mask", "return_attention_scores", "training", "use_causal_mask")
+
+
+def _tensor_name(v):
+    """Layer name of a serialized tensor reference (Keras 2 ["name", node, tensor], Keras 3 __keras_tensor__),
+    None for anything else."""
+    if isinstance(v, dict) and v.get("class_name") == "__keras_tensor__":
+        return v["config"]["keras_history"][0]
+    if isinstance(v, (list, tuple)) and len(v) >= 3 and isinstance(v[0], str) and isinstance(v[1], int):
+        return v[0]
+    return None
+
+
+def _mha_input(layer: Dict[str, Any], name: str) -> str:
+    """The one tensor a MultiHeadAttention call attends over.  Keras 2 keeps `value` / `key` in the first
+    inbound entry's kwargs, Keras 3 in the node's "kwargs" (or all of them in "args"); the call must be plain
+    self-attention: query, value and key the same tensor, no mask, no scores returned."""
+    nodes = layer.get("inbound_nodes") or []
+    if len(nodes) != 1:
+        raise NotImplementedError(f"layer {name!r} is called {len(nodes)} times (one call per layer)")
+    node = nodes[0]
+    if isinstance(node, dict):                       # Keras 3
+        args, kwargs = list(node.get("args", [])), dict(node.get("kwargs", {}))
+    else:                                            # Keras 2
+        args, kwargs = [list(e[:3]) for e in node], {}
+        for e in node:
+            if len(e) > 3 and isinstance(e[3], dict):
+                kwargs.update(e[3])
+    call = dict(zip(_MHA_ARGS, args))
+    call.update(kwargs)
+    q, v = _tensor_name(call.get("query")), _tensor_name(call.get("value"))
+    k = _tensor_name(call.get("key")) if call.get("key") is not None else v
+    if q is None or v is None:
+        raise NotImplementedError(f"{name}: MultiHeadAttention call without a query and a value tensor")
+    if not q == v == k:
+        raise NotImplementedError(f"{name}: cross-attention (query {q!r}, value {v!r}, key {k!r}); only "
+                                  f"self-attention over one tensor is supported")
+    if call.get("attention_mask") is not None:
+        raise NotImplementedError(f"{name}: MultiHeadAttention with an attention_mask")
+    if call.get("use_causal_mask"):
+        raise NotImplementedError(f"{name}: MultiHeadAttention with use_causal_mask")
+    if call.get("return_attention_scores"):
+        raise NotImplementedError(f"{name}: MultiHeadAttention with return_attention_scores")
+    return q
+
+
+def _check_mha(cfg: Dict[str, Any], in_shape: Tuple[int, ...], name: str) -> None:
+    """What the config may ask for beyond the defaults: attention over all position axes, and an output as
+    wide as the input (`in_shape` is per image)."""
+    rank = len(in_shape) + 1                          # with the batch axis, as Keras counts
+    axes = cfg.get("attention_axes")
+    if axes is not None:
+        axes = [axes] if isinstance(axes, int) else list(axes)
+        if sorted(a + rank if a < 0 else a for a in axes) != list(range(1, rank - 1)):
+            raise NotImplementedError(f"{name}: MultiHeadAttention attention_axes={cfg['attention_axes']} (only all "
+                                      f"position axes)")
+    osh = cfg.get("output_shape")
+    if osh is not None and (list(osh) if isinstance(osh, (list, tuple)) else [osh]) != [in_shape[-1]]:
+        raise NotImplementedError(f"{name}: MultiHeadAttention output_shape={osh} (only the input's "
+                                  f"{in_shape[-1]} channels)")
+
+
 def _padding2d(p) -> Tuple[Tuple[int, int], Tuple[int, int]]:
     if isinstance(p, int):
         return ((p, p), (p, p))
@@ -179,6 +241,15 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
             if not cfg.get(k, True):
                 a[k] = False
         return Layer(name, "layernorm", inputs, a)
+    if cls == "MultiHeadAttention":
+        # the call (self-attention only) and attention_axes / output_shape are checked in from_keras_json
+        a = {"num_heads": int(cfg["num_heads"]), "key_dim": int(cfg["key_dim"]),
+             "use_bias": bool(cfg.get("use_bias", True))}
+        if cfg.get("value_dim") is not None and int(cfg["value_dim"]) != a["key_dim"]:
+            a["value_dim"] = int(cfg["value_dim"])
+        return Layer(name, "mha", inputs, a)
+    if cls == "ClassTokenPositionEmbedding":           # the project's own layer (graph/ir.py "posembed")
+        return Layer(name, "posembed", inputs, {"class_token": bool(cfg.get("class_token", True))})
     if cls == "LayerScale":
         return Layer(name, "layerscale", inputs, {"init_values": float(cfg.get("init_values", 1e-6))})
     if cls == "StochasticDepth":                       # drops whole residual branches in training only
@@ -264,7 +335,13 @@ def from_keras_json(s) -> Graph:
     g = Graph(cfg.get("name", "model"))
     for ld in cfg["layers"]:
         name = ld.get("name") or ld["config"]["name"]
-        for layer in _layers_from_keras(ld["class_name"], ld["config"], name, _inbound_names(ld)):
+        mha = ld["class_name"] == "MultiHeadAttention"
+        inputs = [_mha_input(ld, name)] if mha else _inbound_names(ld)
+        if mha:
+            if inputs[0] not in g.layers:
+                raise ValueError(f"layer {name!r} consumes unknown tensor {inputs[0]!r}")
+            _check_mha(ld["config"], g.layers[inputs[0]].out_shape, name)
+        for layer in _layers_from_keras(ld["class_name"], ld["config"], name, inputs):
             g.add(layer)
         if ld["class_name"] == "LayerNormalization":
             _check_last_axis(ld["config"].get("axis", -1), len(g.layers[name].out_shape) + 1, name)
@@ -318,6 +395,13 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
         cls = "LayerNormalization"
         cfg.update(axis=[-1], epsilon=a.get("epsilon", 1e-3), center=a.get("center", True),
                    scale=a.get("scale", True))
+    elif L.op == "mha":
+        cls = "MultiHeadAttention"
+        cfg.update(num_heads=a["num_heads"], key_dim=a["key_dim"], value_dim=a.get("value_dim") or a["key_dim"],
+                   dropout=0.0, use_bias=a.get("use_bias", True), output_shape=None, attention_axes=None)
+    elif L.op == "posembed":
+        cls = "ClassTokenPositionEmbedding"
+        cfg.update(class_token=bool(a.get("class_token")))
     elif L.op == "layerscale":
         cls = "LayerScale"
         cfg.update(init_values=a.get("init_values", 1e-6), projection_dim=L.out_shape[-1])
@@ -373,6 +457,8 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
     else:
         raise NotImplementedError(L.op)
     inbound = [[[i, 0, 0, {}] for i in L.inputs]] if L.inputs else []
+    if L.op == "mha":                                   # Keras 2: mha(x, x) keeps `value` in the entry's kwargs
+        inbound = [[[L.inputs[0], 0, 0, {"value": [L.inputs[0], 0, 0]}]]]
     return {"class_name": cls, "config": cfg, "name": L.name, "inbound_nodes": inbound}
 
 

@@ -146,6 +146,17 @@ def init_weights(g: Graph, seed: int = 0, layers: Optional[List[str]] = None) ->
                     "beta": (rng.standard_normal(c) * 0.05).astype(np.float32)}
             for wname, _ in specs:                 # scale=False / center=False drop gamma / beta
                 out[wname] = vals[wname.rsplit("/", 1)[1]]
+        elif L.op == "mha":
+            # projections: fan-in C (h * dv for the output projection), biases zero
+            for wname, shp in specs:
+                if wname.endswith("/bias"):
+                    out[wname] = np.zeros(shp, np.float32)
+                else:
+                    fan_in = shp[0] * shp[1] if "/attention_output/" in wname else shp[0]
+                    out[wname] = (rng.standard_normal(shp) * np.sqrt(1.0 / fan_in)).astype(np.float32)
+        elif L.op == "posembed":
+            for wname, shp in specs:               # class token and position embedding: N(0, 0.02)
+                out[wname] = (rng.standard_normal(shp) * 0.02).astype(np.float32)
         elif L.op == "layerscale":
             # O(1), not Keras' 1e-6: with that every residual branch would vanish from the output
             out[specs[0][0]] = rng.uniform(0.1, 0.3, specs[0][1][0]).astype(np.float32)

@@ -15,11 +15,13 @@ takes an arbitrary Keras JSON):
 * InceptionV3         (BatchNormalization(scale=False), asymmetric 1x7 / 7x1 kernels, multi-branch concats)
 * ResNeXt-50 / -101 (32x4d)  (Conv2D(groups=32) 3x3 in every block, ResNet layer names)
 * ConvNeXt-Tiny ... -XLarge  (LayerNormalization, Dense on (H, W, C), LayerScale, a 7x7 Conv2D(groups=C))
+* ViT-Ti / S / B / L at patch 16  (MultiHeadAttention as self-attention, class token + position embedding)
 
 Parameter totals (Keras, include_top, 1000 classes; checked by tests):
 VGG16 138,357,544; VGG19 143,667,240; MobileNetV2 3,538,984; DenseNet121 8,062,504;
 EfficientNetB0 5,330,571; InceptionV3 23,851,784; ResNeXt50 25,097,128; ResNeXt101 44,315,560;
-ConvNeXt Tiny 28,589,128, Small 50,223,688, Base 88,591,464, Large 197,767,336, XLarge 350,196,968.
+ConvNeXt Tiny 28,589,128, Small 50,223,688, Base 88,591,464, Large 197,767,336, XLarge 350,196,968;
+ViT (published sizes, patch 16) Ti 5,717,416, S 22,050,664, B 86,567,656, L 304,326,632.
 
 Not from `keras.applications` (models whose output is a map, not a class vector):
 
@@ -457,7 +459,55 @@ def build_unet(name: str = "unet", classes: int = 1, input_shape=None, base: int
     return g
 
 
+# --------------------------------------------------------------------- ViT
+# name -> (patch, width, depth, heads, mlp, default input); micro: same naming / structure, for fast tests
+VIT = {
+    "vit_ti16": (16, 192, 12, 3, 768, (224, 224, 3)),
+    "vit_s16": (16, 384, 12, 6, 1536, (224, 224, 3)),
+    "vit_b16": (16, 768, 12, 12, 3072, (224, 224, 3)),
+    "vit_l16": (16, 1024, 24, 16, 4096, (224, 224, 3)),
+    "vit_micro": (8, 64, 2, 2, 128, (32, 32, 3)),
+}
+VIT_EPS = 1e-6
+
+
+def build_vit(name: str = "vit_b16", classes: int = 1000, input_shape=None) -> Graph:
+    """Vision Transformer (Dosovitskiy et al. 2021; the published Ti / S / B / L at patch 16) as a flat pre-norm
+    graph: a p x p / p patch conv, the class token and position embedding, `depth` blocks of
+    LayerNormalization -> MultiHeadAttention -> Add and LayerNormalization -> Dense -> GELU -> Dense -> Add on a
+    (1, T, C) token map, a final LayerNormalization, the class token cropped out, and the Dense softmax head."""
+    patch, width, depth, heads, mlp, default_shape = VIT[name]
+    shape = tuple(input_shape or default_shape)
+    if len(shape) != 3 or shape[0] % patch or shape[1] % patch:
+        raise ValueError(f"{name}: input {shape} is not (H, W, C) with H and W multiples of the {patch}-pixel patch")
+    g = Graph(name)
+    x = g.add(Layer("input_1", "input", [], {"shape": shape}))
+    x = _conv(g, x, f"{name}_patch_embed", width, patch, stride=patch)
+    x = g.add(Layer(f"{name}_pos_embed", "posembed", [x], {"class_token": True}))
+    tokens = g.layers[x].out_shape[1]
+
+    def ln(x: str, nm: str) -> str:
+        return g.add(Layer(nm, "layernorm", [x], {"epsilon": VIT_EPS}))
+
+    for i in range(depth):
+        nm = f"{name}_block_{i}"
+        y = g.add(Layer(f"{nm}_attn", "mha", [ln(x, f"{nm}_ln1")],
+                        {"num_heads": heads, "key_dim": width // heads, "use_bias": True}))
+        x = g.add(Layer(f"{nm}_add1", "add", [x, y]))
+        y = g.add(Layer(f"{nm}_mlp_fc1", "dense", [ln(x, f"{nm}_ln2")], {"units": mlp, "use_bias": True}))
+        y = g.add(Layer(f"{nm}_mlp_gelu", "act", [y], {"fn": "gelu"}))
+        y = g.add(Layer(f"{nm}_mlp_fc2", "dense", [y], {"units": width, "use_bias": True}))
+        x = g.add(Layer(f"{nm}_add2", "add", [x, y]))
+    x = ln(x, f"{name}_ln")
+    x = g.add(Layer(f"{name}_cls", "crop", [x], {"crop": ((0, 0), (0, tokens - 1))}))      # the class token
+    x = g.add(Layer(f"{name}_flatten", "flatten", [x]))
+    g.add(Layer(f"{name}_head", "dense", [x], {"units": classes, "activation": "softmax", "use_bias": True}))
+    g.output_names = [f"{name}_head"]
+    return g
+
+
 BUILDERS: Dict[str, Callable[..., Graph]] = {
+    **{n: (lambda n: lambda **kw: build_vit(n, **kw))(n) for n in VIT},
     **{n: (lambda n: lambda **kw: build_unet(n, **kw))(n) for n in UNET},
     **{n: (lambda n: lambda **kw: build_convnext(n, **kw))(n) for n in CONVNEXT},
     "vgg16": lambda **kw: build_vgg("vgg16", **kw),

@@ -142,6 +142,23 @@ class ReferenceExecutor:
                                 a.get("epsilon", 1e-3))
         if L.op == "layerscale":
             return ins[0] * self.w[f"{L.name}/gamma"]
+        if L.op == "mha":
+            # Keras MultiHeadAttention(x, x): attention over all positions, the query scaled before the dot product
+            w = lambda p: self.w[f"{L.name}/{p}/kernel"]
+            b = lambda p: self.w.get(f"{L.name}/{p}/bias", 0.0)
+            x = ins[0].reshape(ins[0].shape[0], -1, ins[0].shape[-1])           # (B, T, C)
+            q = (torch.einsum("btc,chd->bthd", x, w("query")) + b("query")) * (1.0 / float(a["key_dim"]) ** 0.5)
+            k = torch.einsum("btc,chd->bthd", x, w("key")) + b("key")
+            v = torch.einsum("btc,chd->bthd", x, w("value")) + b("value")
+            p = torch.softmax(torch.einsum("bqhd,bkhd->bhqk", q, k), dim=-1)
+            y = torch.einsum("bhqk,bkhd->bqhd", p, v)
+            y = torch.einsum("bqhd,hdc->bqc", y, w("attention_output")) + b("attention_output")
+            return y.reshape(ins[0].shape)
+        if L.op == "posembed":
+            x = ins[0].reshape(ins[0].shape[0], -1, ins[0].shape[-1])
+            if a.get("class_token"):
+                x = torch.cat([self.w[f"{L.name}/class_token"].expand(x.shape[0], 1, -1), x], dim=1)
+            return (x + self.w[f"{L.name}/position_embedding"]).unsqueeze(1)
         if L.op == "relu":
             y = torch.relu(ins[0])
             return y if a.get("max_value") is None else torch.clamp(y, max=float(a["max_value"]))

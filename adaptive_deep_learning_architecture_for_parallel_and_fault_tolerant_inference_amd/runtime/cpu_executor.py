@@ -20,9 +20,9 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from ..graph.ir import Graph, bn_params, conv_kernel, depthwise_kernel
+from ..graph.ir import Graph, bn_params, conv_bias, conv_kernel, depthwise_kernel
 from ..ops.conv import fold_bn
-from .plan import Step, compile_plan
+from .plan import Step, compile_plan, tensor_shape
 
 _mod = None
 _lock = threading.Lock()
@@ -55,7 +55,8 @@ class CpuExecutor:
     """Runs one (sub)graph on the host CPU with the native `_cpu` ops (fp32)."""
 
     KINDS = ("conv", "gconv", "dwconv", "maxpool", "avgpool", "bn", "add", "relu", "act", "binary", "affine", "gmp", "copy",
-             "concat", "gap", "dense", "softmax", "pad", "layernorm", "deconv", "upsample", "crop")
+             "concat", "gap", "dense", "softmax", "pad", "layernorm", "deconv", "upsample", "crop", "attention",
+             "posembed")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], outputs: Optional[Sequence[str]] = None):
         self.g = g
@@ -79,7 +80,7 @@ class CpuExecutor:
         if p.get("bn"):
             bn = bn_params(weights, p["bn"])
             eps = self.g.layers[p["bn"]].attrs.get("epsilon", 1e-3)
-        return fold_bn(conv_kernel(weights, p), weights.get(f"{p['conv']}/bias"), bn, eps,
+        return fold_bn(conv_kernel(weights, p), conv_bias(weights, p), bn, eps,
                        scale=weights[f"{p['scale']}/gamma"] if p.get("scale") else None)
 
     def _pack(self, weights: Dict[str, np.ndarray]) -> None:
@@ -120,6 +121,10 @@ class CpuExecutor:
                 c = self.g.layers[st.p["layer"]].out_shape[-1]
                 self.packed[i] = tuple(np.ascontiguousarray(weights.get(f"{st.p['layer']}/{w}", d), np.float32)
                                        for w, d in (("gamma", np.ones(c)), ("beta", np.zeros(c))))
+            elif st.kind == "posembed":
+                n = st.p["layer"]
+                cls = weights[f"{n}/class_token"].reshape(-1) if st.p["class_token"] else None
+                self.packed[i] = (cls, np.ascontiguousarray(weights[f"{n}/position_embedding"], np.float32))
             elif st.kind == "affine":            # Keras Rescaling / Normalization: y = x * scale + shift
                 L = self.g.layers[st.p["layer"]]
                 c = L.out_shape[-1]
@@ -136,7 +141,7 @@ class CpuExecutor:
 
     # ------------------------------------------------------------ run
     def _shape(self, name: str, batch: int):
-        return (batch,) + tuple(self.g.layers[name.split("#")[0]].out_shape)
+        return (batch,) + tensor_shape(self.g, name)
 
     def _step(self, i: int, st: Step, vals: Dict[str, np.ndarray], batch: int) -> np.ndarray:
         m = self.mod
@@ -147,6 +152,11 @@ class CpuExecutor:
         if k == "conv":
             w, b = self.packed[i]
             (pt, _), (pl, _) = p["pads"]
+            if p.get("dense"):                  # a GEMM over the last axis, whatever the rank: (T, C) tokens too
+                y4 = y.reshape(batch, 1, -1, y.shape[-1])
+                m.conv2d(ins[0].reshape(batch, 1, -1, ins[0].shape[-1]), w, b, y4, 1, 0, 0, int(p["relu"]), 0.3,
+                         ins[1].reshape(y4.shape) if p.get("residual") else None)
+                return y
             if ins[0].ndim != 4:                # a Reshape((1, 1, C)) aliased onto a GAP row (squeeze-excite)
                 ins[0] = ins[0].reshape((batch,) + tuple(self.g.layers[self.g.layers[p["conv"]].inputs[0]].out_shape))
             m.conv2d(ins[0], w, b, y, int(p["stride"]), int(pt), int(pl), int(p["relu"]), 0.3,
@@ -177,6 +187,15 @@ class CpuExecutor:
         elif k == "layernorm":
             gm, bt = self.packed[i]
             m.layernorm(ins[0], gm, bt, y, float(p["eps"]))
+        elif k == "attention":
+            m.attention(ins[0].reshape(-1, ins[0].shape[-1]), y.reshape(-1, y.shape[-1]), batch, int(p["tokens"]),
+                        int(p["heads"]), int(p["key_dim"]), int(p["value_dim"]))
+        elif k == "posembed":
+            cls, pos = self.packed[i]
+            ct = 0 if cls is None else 1
+            if ct:
+                y[:, 0, 0] = cls + pos[0]
+            y[:, 0, ct:] = ins[0].reshape(batch, -1, y.shape[-1]) + pos[ct:]
         elif k == "add":
             m.binary(ins[0], ins[1], y, 0, int(p["relu"]), 0.3)
         elif k == "relu":

@@ -29,11 +29,12 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ..graph.ir import Graph, bn_params, conv_kernel, depthwise_kernel
+from ..graph.ir import Graph, bn_params, conv_bias, conv_kernel, depthwise_kernel
+from ..ops import attention as attn_ops
 from ..ops import conv as conv_ops
 from ..ops import eltwise as E
 from ..ops._lib import private_stream
-from .plan import Step, compile_plan
+from .plan import Step, compile_plan, tensor_shape
 
 TUNING_FILE = Path(__file__).resolve().parent.parent / "tuning" / "gfx950_conv.json"
 _tuning_lock = threading.Lock()
@@ -78,7 +79,7 @@ class SliceExecutor:
 
     FP32_KINDS = ("conv", "pair", "dense", "maxpool", "gap", "softmax", "add", "bn", "relu", "pad", "copy",
                   "dwconv", "avgpool", "concat", "act", "binary", "affine", "stem_f32", "gconv", "layernorm",
-                  "deconv", "upsample", "crop")
+                  "deconv", "upsample", "crop", "attention", "posembed")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], batch: int, device="cuda",
                  outputs: Optional[Sequence[str]] = None, tune: bool = False, num_sets: int = 1,
@@ -118,8 +119,9 @@ class SliceExecutor:
 
     # ------------------------------------------------------------ shapes
     def shape_of(self, name: str) -> Tuple[int, ...]:
-        base = name.split("#")[0]
-        shp = tuple(self.g.layers[base].out_shape)
+        shp = tensor_shape(self.g, name)        # a MultiHeadAttention's `#qkv` / `#ctx` are (1, T, channels) maps
+        if len(shp) == 2:
+            shp = (1,) + shp                    # a (T, C) token tensor is stored as the (1, T, C) map
         # activations are stored with channels padded to a multiple of 8 (16-byte
         # vectors); only the user's fp32 image keeps its true channel count
         if len(shp) == 3 and shp[-1] % 8 and self.dtype_of(name) != torch.float32 and not self.fp32:
@@ -239,6 +241,8 @@ class SliceExecutor:
                                   torch.tensor(bt - mu * s, dtype=torch.float32, device=dev))
             elif st.kind == "layernorm":
                 self.packed[i] = self._pack_layernorm(weights, st, self.shape_of(st.out)[-1])
+            elif st.kind == "posembed":
+                self.packed[i] = self._pack_posembed(weights, st)
             elif st.kind == "deconv":            # the bounds-checked kernel on bf16 activations (no bf16 MFMA path)
                 kf, bf = self._folded(weights, st.p)      # (kh, kw, cin, filters): BN scales the last axis
                 self.packed[i] = conv_ops.pack_deconv_bf16(kf, bf, st.p["stride"], st.p["pads"], dev)
@@ -284,6 +288,8 @@ class SliceExecutor:
                                   torch.tensor(bt - mu * sc, dtype=torch.float32, device=dev))
             elif st.kind == "layernorm":
                 self.packed[i] = self._pack_layernorm(weights, st, self.shape_of(st.out)[-1])
+            elif st.kind == "posembed":
+                self.packed[i] = self._pack_posembed(weights, st)
             elif st.kind == "dwconv":
                 p = st.p
                 k = depthwise_kernel(weights, p["conv"])                      # (kh, kw, C), multiplier 1
@@ -310,6 +316,27 @@ class SliceExecutor:
                 self.packed[i] = (torch.tensor(np.ascontiguousarray(sc), dtype=torch.float32, device=dev),
                                   torch.tensor(np.ascontiguousarray(sh), dtype=torch.float32, device=dev))
 
+    def _pack_posembed(self, weights: Dict[str, np.ndarray], st: Step):
+        """(class token [C] or None, position embedding [T + ct, C]) fp32, true channel width in both precisions."""
+        n = st.p["layer"]
+        cls = None
+        if st.p["class_token"]:
+            cls = torch.tensor(np.ascontiguousarray(weights[f"{n}/class_token"], np.float32).reshape(-1),
+                               device=self.device)
+        return cls, torch.tensor(np.ascontiguousarray(weights[f"{n}/position_embedding"], np.float32),
+                                 device=self.device)
+
+    def _launch_tokens(self, i: int, st: Step, b, stream) -> None:
+        """The attention core and the position embedding: one wrapper each for both precisions."""
+        if st.kind == "attention":
+            p = st.p
+            attn_ops.attention(b[st.ins[0]], b[st.out], self.batch, p["tokens"], p["heads"], p["key_dim"],
+                               p["value_dim"], stream=stream)
+        else:
+            cls, pos = self.packed[i]
+            attn_ops.posembed(b[st.ins[0]], cls, pos, b[st.out], C=self.g.layers[st.p["layer"]].out_shape[-1],
+                              stream=stream)
+
     def _pack_layernorm(self, weights: Dict[str, np.ndarray], st: Step, cp: int):
         """(gamma, beta) fp32 [cp] of a layernorm step, with Keras' defaults for scale=False / center=False;
         the bf16 layout's padding channels get gamma = beta = 0, which makes them come out as zeros."""
@@ -329,7 +356,7 @@ class SliceExecutor:
         if p["bn"]:
             bn = bn_params(weights, p["bn"])
             eps = self.g.layers[p["bn"]].attrs.get("epsilon", 1e-3)
-        return conv_ops.fold_bn(conv_kernel(weights, p), weights.get(f"{cname}/bias"), bn, eps,
+        return conv_ops.fold_bn(conv_kernel(weights, p), conv_bias(weights, p), bn, eps,
                                 scale=weights[f"{p['scale']}/gamma"] if p.get("scale") else None)
 
     # ----------------------------------------------------------- buffers
@@ -779,6 +806,8 @@ class SliceExecutor:
                 gm, bt = self.packed[i]
                 E.layernorm(b[st.ins[0]], gm, bt, b[st.out], self.g.layers[st.p["layer"]].out_shape[-1], st.p["eps"],
                             stream=stream)
+            elif k in ("attention", "posembed"):
+                self._launch_tokens(i, st, b, stream)
             elif k == "act":
                 E.act(b[st.ins[0]], b[st.out], st.p["mode"], st.p["alpha"], stream=stream)
             elif k == "binary":
@@ -907,6 +936,8 @@ class SliceExecutor:
         elif k == "layernorm":
             gm, bt = self.packed[i]
             E.layernorm_f32(b[st.ins[0]], gm, bt, b[st.out], st.p["eps"], stream=stream)
+        elif k in ("attention", "posembed"):
+            self._launch_tokens(i, st, b, stream)
         elif k == "deconv":
             conv_ops.deconv_forward_f32(b[st.ins[0]], self.packed[i], b[st.out], relu=st.p["relu"], stream=stream)
         elif k == "upsample":

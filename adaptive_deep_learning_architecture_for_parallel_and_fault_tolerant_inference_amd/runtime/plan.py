@@ -17,6 +17,14 @@ kernels:
 * ``dwconv``   DepthwiseConv2D, or Conv2D(groups=C) with one channel per group,
                [+BN folded] [+ReLU/ReLU6], explicit pads
 * ``layernorm`` LayerNormalization over the last axis; nothing fuses into it
+* ``attention`` the core of a MultiHeadAttention layer `n`, softmax(Q K^T) V per head.  The layer
+               compiles to three steps: a ``conv`` (1x1, the Dense path) `n#qkv` whose weights are the
+               three projections side by side, [Q | K | V] with 1/sqrt(key_dim) folded into Q; this
+               step, `n#qkv` -> `n#ctx`; and a ``conv`` (1x1) `n#ctx` -> `n`, the output projection,
+               which takes the block's Add as its residual like any Dense.  The `#` tensors are
+               internal (a cut can only name `n`); a kind of its own, so no pair, sibling, stem or
+               bottleneck pass ever sees it
+* ``posembed`` ViT class token + learned position embedding
 * ``gconv``    Conv2D(groups > 1) [+BN folded] [+ReLU/ReLU6], explicit pads; no
                residual fusion, and a kind of its own so that no pass written
                for dense convs (pair, siblings, stem, bottleneck) ever sees it
@@ -58,6 +66,21 @@ class Step:
     ins: List[str]                 # tensor names consumed (physical names)
     covers: List[str]              # graph layers executed by this step
     p: Dict = field(default_factory=dict)
+
+
+def tensor_shape(g: Graph, name: str) -> tuple:
+    """Per-image shape of a plan tensor: the layer's own, or for the two internal tensors of a
+    MultiHeadAttention layer (`n#qkv`, `n#ctx`) a (1, T, channels) token map."""
+    base, _, tag = name.partition("#")
+    L = g.layers[base]
+    if tag in ("qkv", "ctx"):
+        h, d = int(L.attrs["num_heads"]), int(L.attrs["key_dim"])
+        dv = int(L.attrs.get("value_dim") or d)
+        tokens = 1
+        for v in L.out_shape[:-1]:
+            tokens *= v
+        return (1, tokens, h * (2 * d + dv) if tag == "qkv" else h * dv)
+    return tuple(L.out_shape)
 
 
 def _phys(name: str, packed: Set[str]) -> str:
@@ -138,6 +161,25 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
             raise NotImplementedError(f"{L.op} activation {act!r} ({n})")
         return ACT_MODE[act]
 
+    def residual_add(n: str, cover: List[str]):
+        """(residual, output, relu) of a Dense-like layer `n` whose single consumer is a two-input Add with a
+        tensor already produced: the Add (and a ReLU / ReLU6 after it) joins `cover` and runs in the conv
+        epilogue.  (None, n, 0) when there is none."""
+        c1 = single(n)
+        if c1 is None or g.layers[c1].op != "add" or len(g.layers[c1].inputs) != 2:
+            return None, n, 0
+        other = [i for i in g.layers[c1].inputs if i != n]
+        if len(other) != 1 or alias.get(other[0], other[0]) not in produced:
+            return None, n, 0
+        cover.append(c1)
+        out, relu = c1, 0
+        c2 = single(c1)
+        if 0 < act_mode(c2) <= 2:
+            relu = act_mode(c2)
+            cover.append(c2)
+            out = c2
+        return alias.get(other[0], other[0]), out, relu
+
     for n in g.order:
         if n in done:
             continue
@@ -151,10 +193,11 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                 done.add(n)
                 continue
             steps.append(Step("pad", n, [R(L.inputs[0])], [n], {"pad": a["pad"]}))
-        elif L.op in ("conv", "dwconv") or (L.op == "dense" and len(g.layers[L.inputs[0]].out_shape) == 3):
+        elif L.op in ("conv", "dwconv") or (L.op == "dense" and len(g.layers[L.inputs[0]].out_shape) in (2, 3)):
             if L.op == "dense":
-                # Dense on (H, W, C) is a 1x1 conv: it gets the pointwise kernels, the tuning table and
-                # the conv epilogue; the weight packers reshape its (cin, units) kernel (p["dense"])
+                # Dense on (H, W, C), or on a (T, C) token tensor, is a 1x1 conv: it gets the pointwise
+                # kernels, the tuning table and the conv epilogue; the weight packers reshape its
+                # (cin, units) kernel (p["dense"])
                 if a.get("activation") == "softmax":
                     raise NotImplementedError(f"Dense(activation='softmax') on a rank-3 tensor ({n})")
                 a = {"filters": a["units"], "kernel": (1, 1), "stride": 1, "padding": "valid",
@@ -218,6 +261,8 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                     relu = act_mode(c1)
                     cover.append(c1)
                     out = c1
+                elif L.op == "dense":           # a transformer block's Add directly after its last Dense
+                    res, out, relu = residual_add(n, cover)
             kernel = tuple(_pair(a["kernel"]))
             if depthwise:
                 steps.append(Step("dwconv", out, [R(src)], cover,
@@ -342,6 +387,33 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
         elif L.op == "layernorm":
             steps.append(Step("layernorm", n, [R(L.inputs[0])], [n],
                               {"layer": n, "eps": float(a.get("epsilon", 1e-3))}))
+            done.add(n)
+        elif L.op == "mha":
+            h, d = int(a["num_heads"]), int(a["key_dim"])
+            dv = int(a.get("value_dim") or d)
+            tokens = 1
+            for v in L.out_shape[:-1]:
+                tokens *= v
+            head = {"heads": h, "key_dim": d, "value_dim": dv}
+
+            def proj(part: str, filters: int, res) -> Dict:
+                # a Dense step whose weights the packers assemble from the layer's projections (graph/ir.py
+                # mha_projection); "dense" keeps it out of the sibling merge
+                return {"conv": n, "mha": part, "dense": True, "bn": None, "relu": 0, "residual": res,
+                        "pads": ((0, 0), (0, 0)), "stride": 1, "kernel": (1, 1), "filters": filters,
+                        "packed_input": False, **head}
+
+            steps.append(Step("conv", n + "#qkv", [R(L.inputs[0])], [], proj("qkv", h * (2 * d + dv), None)))
+            steps.append(Step("attention", n + "#ctx", [n + "#qkv"], [], {"layer": n, "tokens": tokens, **head}))
+            cover = [n]
+            res, out, relu = residual_add(n, cover)
+            steps.append(Step("conv", out, [n + "#ctx"] + ([res] if res else []), cover,
+                              proj("out", L.out_shape[-1], res)))
+            steps[-1].p["relu"] = relu
+            done.update(cover)
+        elif L.op == "posembed":
+            steps.append(Step("posembed", n, [R(L.inputs[0])], [n],
+                              {"layer": n, "class_token": bool(a.get("class_token"))}))
             done.add(n)
         elif L.op == "gmp":
             steps.append(Step("gmp", n, [R(L.inputs[0])], [n]))
@@ -565,7 +637,8 @@ def _fuse_stem_f32(g: Graph, steps: List[Step], outset: Set[str]) -> List[Step]:
         return [j for j, s in enumerate(steps) if t in s.ins]
 
     for i, cv in enumerate(steps):
-        if cv.kind != "conv" or len(cv.ins) != 1 or g.layers[cv.ins[0]].op != "input":
+        if (cv.kind != "conv" or len(cv.ins) != 1 or cv.p.get("dense") or cv.ins[0] not in g.layers
+                or g.layers[cv.ins[0]].op != "input"):
             continue
         p = cv.p
         h, w, c = g.layers[cv.ins[0]].out_shape

@@ -343,6 +343,57 @@ void crop2d(const Arr<float>& x, Arr<float>& y, int t, int l) {
                   sizeof(float) * OW * C);
 }
 
+// Self-attention core, softmax(Q K^T) V per (image, head): qkv [B*T][ld_in] rows of [Q | K | V] (head-major, Q
+// already scaled by 1/sqrt(d)), out [B*T][ld_out] with heads * dv channels (the rest of a row becomes zero): the
+// argument layout of the GPU op (csrc/kernels/attention.hip).  fp32, the row maximum subtracted before the exponent.
+void attention(const Arr<float>& qkv, Arr<float>& out, int B, int T, int heads, int d, int dv) {
+  need(qkv.ndim() >= 2 && out.ndim() >= 2 && B >= 1 && T >= 1 && heads >= 1 && d >= 1 && dv >= 1, "attention args");
+  const long ld_in = qkv.shape(qkv.ndim() - 1), ld_out = out.shape(out.ndim() - 1);
+  need(qkv.size() == (long)B * T * ld_in && out.size() == (long)B * T * ld_out && ld_in >= (long)heads * (2 * d + dv)
+           && ld_out >= (long)heads * dv, "attention shapes");
+  const float* xp = cptr(qkv);
+  float* yp = mptr(out);
+  py::gil_scoped_release nogil;
+#pragma omp parallel
+  {
+    std::vector<float> p(T);
+#pragma omp for collapse(2) schedule(static)
+    for (int b = 0; b < B; ++b)
+      for (int h = 0; h < heads; ++h) {
+        const float* base = xp + (size_t)b * T * ld_in;
+        const float* kb = base + heads * d + h * d;
+        const float* vb = base + 2 * heads * d + h * dv;
+        for (int q = 0; q < T; ++q) {
+          const float* qr = base + (size_t)q * ld_in + h * d;
+          float mx = -INFINITY;
+          for (int k = 0; k < T; ++k) {
+            const float* kr = kb + (size_t)k * ld_in;
+            float sc = 0.f;
+            for (int i = 0; i < d; ++i) sc += qr[i] * kr[i];
+            p[k] = sc;
+            mx = std::max(mx, sc);
+          }
+          float l = 0.f;
+          for (int k = 0; k < T; ++k) {
+            p[k] = std::exp(p[k] - mx);
+            l += p[k];
+          }
+          float* orow = yp + ((size_t)b * T + q) * ld_out + h * dv;
+          for (int c = 0; c < dv; ++c) orow[c] = 0.f;
+          for (int k = 0; k < T; ++k) {
+            const float* vr = vb + (size_t)k * ld_in;
+            const float pk = p[k];
+            for (int c = 0; c < dv; ++c) orow[c] += pk * vr[c];
+          }
+          const float inv = 1.f / l;
+          for (int c = 0; c < dv; ++c) orow[c] *= inv;
+          if (h == heads - 1)
+            for (long c = (long)heads * dv; c < ld_out; ++c) yp[((size_t)b * T + q) * ld_out + c] = 0.f;
+        }
+      }
+  }
+}
+
 // ------------------------------------------------------------------ depthwise
 // x [N,H,W,C]; w [KH,KW,C]; bias [C]; y [N,OH,OW,C]
 ADAPT_CLONES
@@ -620,6 +671,8 @@ PYBIND11_MODULE(_cpu, m) {
   m.def("global_pool", &global_pool, py::arg("x"), py::arg("y"), py::arg("kind") = 0);
   m.def("affine", &affine, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("y"), py::arg("act") = 0,
         py::arg("alpha") = 0.3f);
+  m.def("attention", &attention, py::arg("qkv"), py::arg("out"), py::arg("B"), py::arg("T"), py::arg("heads"),
+        py::arg("key_dim"), py::arg("value_dim"));
   m.def("layernorm", &layernorm, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("y"), py::arg("eps"));
   m.def("activation", &activation, py::arg("x"), py::arg("y"), py::arg("act"), py::arg("alpha") = 0.3f);
   m.def("binary", &binary, py::arg("a"), py::arg("b"), py::arg("y"), py::arg("op"), py::arg("act") = 0,

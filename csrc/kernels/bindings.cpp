@@ -415,6 +415,25 @@ PYBIND11_MODULE(_C, m) {
     check(adapt::upsample_bf16(P<const bf16>(x), P<bf16>(y), B, H, W, Cp, C, SH, SW, bilinear, S(s)),
           "upsample_bf16");
   });
+  m.def("attention_f32", [](u64 qkv, u64 out, int B, int T, int heads, int d, int dv, int ld_in, int ld_out, u64 s) {
+    check(adapt::attention_f32(P<const float>(qkv), P<float>(out), B, T, heads, d, dv, ld_in, ld_out, S(s)),
+          "attention_f32");
+  });
+  m.def("attention_bf16", [](u64 qkv, u64 out, int B, int T, int heads, int d, int dv, int ld_in, int ld_out, u64 s) {
+    check(adapt::attention_bf16(P<const bf16>(qkv), P<bf16>(out), B, T, heads, d, dv, ld_in, ld_out, S(s)),
+          "attention_bf16");
+  });
+  m.def("attention_path", &adapt::attention_path);
+  m.def("attention_query_tile", &adapt::attention_query_tile);
+  m.def("attention_key_tile", &adapt::attention_key_tile);
+  m.def("posembed_f32", [](u64 x, u64 cls, u64 pos, u64 y, int B, int T, int C, int ct, u64 s) {
+    check(adapt::posembed_f32(P<const float>(x), P<const float>(cls), P<const float>(pos), P<float>(y), B, T, C, ct,
+                              S(s)), "posembed_f32");
+  });
+  m.def("posembed_bf16", [](u64 x, u64 cls, u64 pos, u64 y, int B, int T, int Cp, int C, int ct, u64 s) {
+    check(adapt::posembed_bf16(P<const bf16>(x), P<const float>(cls), P<const float>(pos), P<bf16>(y), B, T, Cp, C, ct,
+                               S(s)), "posembed_bf16");
+  });
   m.def("crop_f32", [](u64 x, u64 y, int B, int H, int W, int C, int OH, int OW, int T, int L, u64 s) {
     check(adapt::crop_f32(P<const float>(x), P<float>(y), B, H, W, C, OH, OW, T, L, S(s)), "crop_f32");
   });

@@ -371,6 +371,22 @@ hipError_t upsample_bf16(const bf16* x, bf16* y, int B, int H, int W, int Cp, in
 hipError_t crop_f32(const float* x, float* y, int B, int H, int W, int C, int OH, int OW, int T, int L, hipStream_t s);
 hipError_t crop_bf16(const bf16* x, bf16* y, int B, int H, int W, int Cp, int C, int OH, int OW, int T, int L,
                      hipStream_t s);
+// Self-attention core (attention.hip): qkv [B*T][ld_in] rows of [Q | K | V] (head-major, Q pre-scaled), out
+// [B*T][ld_out] with heads*dv true channels (the rest of a row is written as zeros).  d, dv multiples of 16 up
+// to 128 run on the fp32 MFMA (flash-style, online softmax), every other size on a plain kernel.
+hipError_t attention_f32(const float* qkv, float* out, int B, int T, int heads, int d, int dv, int ld_in, int ld_out,
+                         hipStream_t s);
+hipError_t attention_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, int d, int dv, int ld_in, int ld_out,
+                          hipStream_t s);
+int attention_path(int d, int dv);     // 1: MFMA path, 0: plain kernel
+int attention_query_tile();            // queries per block of the MFMA path
+int attention_key_tile();              // keys per LDS tile of the MFMA path
+// ViT class token + position embedding (layers.hip): y[b][0] = cls + pos[0], y[b][ct + t] = x[b][t] + pos[ct + t];
+// cls [C] (null without a class token), pos [T + ct][C] fp32; bf16 rows are Cp wide, padding written as zeros
+hipError_t posembed_f32(const float* x, const float* cls, const float* pos, float* y, int B, int T, int C, int ct,
+                        hipStream_t s);
+hipError_t posembed_bf16(const bf16* x, const float* cls, const float* pos, bf16* y, int B, int T, int Cp, int C,
+                         int ct, hipStream_t s);
 bool gconv_f32_mfma_ok(int Cin, int Cout, int G);     // shape rule of the MFMA path
 // mfma: which path to launch (the caller packed w for it); an ineligible shape is an error, never a fall-through
 hipError_t gconv_f32_forward(const GconvF32Params& p, bool mfma, hipStream_t s);

@@ -420,4 +420,83 @@ hipError_t concat_into(const bf16* x, int Cx, int Cpx, bf16* y, int Cpy, int off
   return hipGetLastError();
 }
 
+// ViT class token + learned position embedding: y[b][0] = cls + pos[0] (with a class token, ct = 1),
+// y[b][ct + t] = x[b][t] + pos[ct + t].  x is [B][T][ld], y [B][T + ct][ld] (fp32 rows of C channels, or bf16
+// rows padded to ld with channels C..ld-1 written as zeros whatever x holds there); cls [C] and pos [T + ct][C]
+// are fp32.  VEC = 16 bytes of activations per thread where ld and the bases allow, else 1.
+namespace {
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void posembed_kernel(const T* __restrict__ x, const float* __restrict__ cls,
+                                                        const float* __restrict__ pos, T* __restrict__ y, int Tn,
+                                                        int C, int ld, int ct, size_t total) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int nv = ld / VEC;
+  const int v = (int)(idx % nv);
+  const size_t row = idx / nv;
+  const int t = (int)(row % (Tn + ct));
+  const size_t b = row / (Tn + ct);
+  const bool tok = t >= ct;                           // a token row; otherwise the class token's
+  const T* xr = x + (tok ? (b * Tn + (t - ct)) * ld + (size_t)v * VEC : 0);
+  float f[VEC];
+  if constexpr (VEC == 1) {
+    f[0] = (tok && v < C) ? (float)xr[0] : 0.f;
+  } else if constexpr (sizeof(T) == 4) {
+    f32x4 q = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (tok) q = *(const f32x4*)xr;
+    f[0] = q.x; f[1] = q.y; f[2] = q.z; f[3] = q.w;
+  } else {
+    V8 q;
+    q.u = u32x4{0u, 0u, 0u, 0u};
+    if (tok) q.u = *(const u32x4*)xr;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) f[e] = (float)q.e[e];
+  }
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) {
+    const int c = v * VEC + e;
+    f[e] = c < C ? (tok ? f[e] : cls[c]) + pos[(size_t)t * C + c] : 0.f;      // padding never enters
+  }
+  T* yr = y + row * ld + (size_t)v * VEC;
+  if constexpr (VEC == 1) {
+    yr[0] = (T)f[0];
+  } else if constexpr (sizeof(T) == 4) {
+    *(f32x4*)yr = f32x4{f[0], f[1], f[2], f[3]};
+  } else {
+    V8 q;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) q.e[e] = f2bf(f[e]);
+    *(u32x4*)yr = q.u;
+  }
+}
+
+template <typename T>
+hipError_t posembed_launch(const T* x, const float* cls, const float* pos, T* y, int B, int Tn, int C, int ld, int ct,
+                           hipStream_t s) {
+  constexpr int VEC = 16 / sizeof(T);
+  if (B < 1 || Tn < 1 || C < 1 || ld < C || ct < 0 || ct > 1 || (ct && !cls)) return hipErrorInvalidValue;
+  const size_t rows = (size_t)B * (Tn + ct);
+  if (ld % VEC == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
+    const size_t total = rows * (ld / VEC);
+    hipLaunchKernelGGL((posembed_kernel<T, VEC>), dim3(grid_of(total)), dim3(256), 0, s, x, cls, pos, y, Tn, C, ld, ct,
+                       total);
+  } else {
+    const size_t total = rows * ld;
+    hipLaunchKernelGGL((posembed_kernel<T, 1>), dim3(grid_of(total)), dim3(256), 0, s, x, cls, pos, y, Tn, C, ld, ct,
+                       total);
+  }
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t posembed_f32(const float* x, const float* cls, const float* pos, float* y, int B, int T, int C, int ct,
+                        hipStream_t s) {
+  return posembed_launch<float>(x, cls, pos, y, B, T, C, C, ct, s);
+}
+
+hipError_t posembed_bf16(const bf16* x, const float* cls, const float* pos, bf16* y, int B, int T, int Cp, int C,
+                         int ct, hipStream_t s) {
+  return posembed_launch<bf16>(x, cls, pos, y, B, T, C, Cp, ct, s);
+}
+
 }  // namespace adapt

@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Timings of the self-attention core, hipGraph-timed like tools/deconv_bench.py.  Per shape, in one process, the
+implementations interleaved round by round, in microseconds:
+
+* ours     csrc/kernels/attention.hip through ops/attention.py `attention`, fp32 activations;
+* ours16   the same kernel on bf16 activations (fp32 MFMA math; there is no bf16-MFMA attention);
+* sdpa     `torch.nn.functional.scaled_dot_product_attention` in fp32 on [B, h, T, d] tensors (scale 1: Q is
+           already scaled, as in our layout): the library reference point;
+* unfused  `torch.matmul`, `softmax`, `torch.matmul` in fp32, the T x T scores through memory.
+
+The torch paths read Q, K, V from contiguous [B, h, T, d] tensors prepared once (not timed); ours reads the
+[B * T][h * (2 d + dv)] rows the QKV projection writes.  TF/s is on the true 2 * T^2 * h * (d + dv) MACs per image.
+Shapes: ViT-Ti / S / B / L at 197 tokens (224 x 224 input) and ViT-B at 577 tokens (384 x 384).
+
+    python tools/attention_bench.py [--batch 32] [--reps 20] [--rounds 5]
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+from adaptive_deep_learning_architecture_for_parallel_and_fault_tolerant_inference_amd.ops import attention as A  # noqa: E402
+
+# (name, tokens, heads, key_dim = value_dim)
+SHAPES = [("vit_ti16", 197, 3, 64), ("vit_s16", 197, 6, 64), ("vit_b16", 197, 12, 64), ("vit_l16", 197, 16, 64),
+          ("vit_b16@384", 577, 12, 64)]
+
+
+def capture(run, reps):
+    """A hipGraph of `reps` calls of `run`, warmed up."""
+    run()
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        for _ in range(reps):
+            run()
+    g.replay()
+    torch.cuda.synchronize()
+    return g
+
+
+def interleaved_us(runs, reps, rounds):
+    """Median microseconds per call of each of `runs` (name -> callable): every round replays each
+    implementation's graph once, in turn."""
+    graphs = {}
+    for name, run in runs.items():
+        try:
+            graphs[name] = capture(run, reps)
+        except RuntimeError as e:                                # a library path that cannot be captured
+            print(f"  {name} not graph-timed: {str(e).splitlines()[0]}")
+    times = {name: [] for name in graphs}
+    for _ in range(rounds):
+        for name, g in graphs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            g.replay()
+            e1.record()
+            e1.synchronize()
+            times[name].append(e0.elapsed_time(e1) / reps * 1e3)
+    return {name: sorted(times[name])[rounds // 2] if times.get(name) else float("nan") for name in runs}
+
+
+def bench(name, B, T, h, d, reps, rounds):
+    qkv = torch.randn(B * T, 3 * h * d, device="cuda")
+    qkv[:, :h * d] *= d ** -0.5                                  # the scale the projection folds into Q
+    out = torch.empty(B * T, h * d, device="cuda")
+    qkv16, out16 = qkv.to(torch.bfloat16), torch.empty(B * T, h * d, device="cuda", dtype=torch.bfloat16)
+    q, k, v = (qkv[:, i * h * d:(i + 1) * h * d].reshape(B, T, h, d).permute(0, 2, 1, 3).contiguous() for i in range(3))
+
+    def unfused():
+        return torch.matmul(torch.softmax(torch.matmul(q, k.transpose(-1, -2)), dim=-1), v)
+
+    def sdpa():
+        return F.scaled_dot_product_attention(q, k, v, scale=1.0)
+
+    t = interleaved_us({"ours": lambda: A.attention(qkv, out, B, T, h, d, d),
+                        "ours16": lambda: A.attention(qkv16, out16, B, T, h, d, d),
+                        "sdpa": sdpa, "unfused": unfused}, reps, rounds)
+    want = unfused().permute(0, 2, 1, 3).reshape(B * T, h * d)
+    diff = (want - out).abs().max().item()
+    diff16 = (want - out16.float()).abs().max().item()
+    flop = 2.0 * B * T * T * h * 2 * d
+    tf = {n: flop / u / 1e6 for n, u in t.items()}
+    print(f"{name:12s} B{B} T{T} h{h} d{d} [{A.attention_path(d, d)}]: ours {t['ours']:8.1f} us ({tf['ours']:5.1f} TF/s)"
+          f" | ours bf16 act {t['ours16']:8.1f} us ({tf['ours16']:5.1f} TF/s)"
+          f" | sdpa {t['sdpa']:8.1f} us ({tf['sdpa']:5.1f} TF/s, {t['sdpa'] / t['ours']:5.2f}x)"
+          f" | unfused {t['unfused']:8.1f} us ({tf['unfused']:5.1f} TF/s, {t['unfused'] / t['ours']:5.2f}x)"
+          f" | max diff vs unfused {diff:.2e} (bf16 act {diff16:.2e})", flush=True)
+    return t
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    a = ap.parse_args()
+    print(torch.cuda.get_device_name(0))
+    for name, T, h, d in SHAPES:
+        bench(name, a.batch, T, h, d, a.reps, a.rounds)
+
+
+if __name__ == "__main__":
+    main()

@@ -51,6 +51,13 @@ OPS = (
     "mha",        # Keras MultiHeadAttention as self-attention over all positions: num_heads, key_dim, value_dim
                   # (absent means key_dim), use_bias; input (H, W, C) or (T, C), output the same shape
     "posembed",   # ViT class token + learned position embedding: attrs class_token; (H, W, C) -> (1, T + ct, C)
+    "winattn",    # Swin window attention (the project's own layer, Keras class WindowAttention): num_heads, key_dim,
+                  # window (M), shift (0 <= s < M), use_bias; (H, W, C) -> (H, W, C), H and W multiples of M.
+                  # Weights as `mha` plus relative_position_bias_table ((2M-1)^2, heads)
+    "space_to_depth",  # Swin patch merging's rearrangement (Keras class SpaceToDepth): attrs block (2);
+                  # (H, W, C) -> (H/2, W/2, 4C), out[y, x, (2 dx + dy) C + c] = in[2y + dy, 2x + dx, c]: the
+                  # concatenation of x[0::2,0::2], x[1::2,0::2], x[0::2,1::2], x[1::2,1::2] (not tf.nn.space_to_depth,
+                  # whose block order is (2 dy + dx))
 )
 
 # activations the runtime executes (fused into conv / dense / eltwise epilogues,
@@ -117,6 +124,14 @@ def mha_projection(weights, name: str, head: Dict, part: str):
         return kernel, None
     bs = [(weights[f"{name}/{q}/bias"].astype(np.float64) * scale[q]).reshape(-1) for q in ("query", "key", "value")]
     return kernel, np.concatenate(bs).astype(np.float32)
+
+
+def window_index(m: int):
+    """Swin's relative position index of an M x M window, (M^2, M^2) ints into the (2M-1)^2 rows of the bias
+    table: index[(i, j), (k, l)] = (i - k + M - 1)(2M - 1) + (j - l + M - 1)."""
+    import numpy as np
+    i, j = np.divmod(np.arange(m * m), m)
+    return (i[:, None] - i[None, :] + m - 1) * (2 * m - 1) + (j[:, None] - j[None, :] + m - 1)
 
 
 def same_pads(size: int, k: int, s: int) -> Tuple[int, int]:
@@ -210,6 +225,15 @@ class Layer:
                 if self.attrs.get("use_bias", True):
                     out.append((f"{self.name}/{part}/bias", bshp))
             return out
+        if self.op == "winattn":
+            c, h, d, m = in_shapes[0][-1], self.attrs["num_heads"], self.attrs["key_dim"], self.attrs["window"]
+            out = []
+            for part, shp, bshp in (("query", (c, h, d), (h, d)), ("key", (c, h, d), (h, d)),
+                                    ("value", (c, h, d), (h, d)), ("attention_output", (h, d, c), (c,))):
+                out.append((f"{self.name}/{part}/kernel", shp))
+                if self.attrs.get("use_bias", True):
+                    out.append((f"{self.name}/{part}/bias", bshp))
+            return out + [(f"{self.name}/relative_position_bias_table", ((2 * m - 1) ** 2, h))]
         if self.op == "posembed":
             t, c = _tokens(in_shapes[0]), in_shapes[0][-1]
             ct = 1 if self.attrs.get("class_token") else 0
@@ -247,6 +271,10 @@ class Layer:
             h, d = self.attrs["num_heads"], self.attrs["key_dim"]
             dv = self.attrs.get("value_dim") or d
             return t * c * h * (2 * d + dv) + t * t * h * (d + dv) + t * h * dv * c
+        if self.op == "winattn":                # projections (h d = C in Swin), scores and P V inside M x M windows
+            (hh, ww, c), m = in_shapes[0], self.attrs["window"]
+            hd = self.attrs["num_heads"] * self.attrs["key_dim"]
+            return 4 * hh * ww * c * hd + 2 * hh * ww * m * m * hd
         return 0
 
     def to_json(self) -> Dict:
@@ -312,6 +340,24 @@ class Graph:
                 raise ValueError(f"mha {layer.name!r}: needs one input of rank 2 or 3 (got rank {rank}), "
                                  f"num_heads >= 1 and key_dim >= 1 (got {layer.attrs.get('num_heads')}, "
                                  f"{layer.attrs.get('key_dim')})")
+        if layer.op == "winattn":
+            shp = self.layers[layer.inputs[0]].out_shape
+            a = layer.attrs
+            m, sh = int(a.get("window", 0)), int(a.get("shift", 0))
+            if (len(layer.inputs) != 1 or len(shp) != 3 or int(a.get("num_heads", 0)) < 1
+                    or int(a.get("key_dim", 0)) < 1 or m < 1 or not 0 <= sh < m):
+                raise ValueError(f"winattn {layer.name!r}: needs one (H, W, C) input (got {shp}), num_heads >= 1, "
+                                 f"key_dim >= 1, window >= 1 and 0 <= shift < window (got {a.get('num_heads')}, "
+                                 f"{a.get('key_dim')}, {a.get('window')}, {a.get('shift')})")
+            if shp[0] % m or shp[1] % m:
+                raise ValueError(f"winattn {layer.name!r}: the {shp[0]} x {shp[1]} map is not a multiple of the "
+                                 f"{m} x {m} window")
+        if layer.op == "space_to_depth":
+            shp = self.layers[layer.inputs[0]].out_shape
+            if (len(layer.inputs) != 1 or len(shp) != 3 or int(layer.attrs.get("block", 2)) != 2 or shp[0] % 2
+                    or shp[1] % 2):
+                raise ValueError(f"space_to_depth {layer.name!r}: needs block 2 and an (H, W, C) input with even "
+                                 f"H and W (got block {layer.attrs.get('block')}, {shp})")
         if layer.op == "posembed":
             shp = self.layers[layer.inputs[0]].out_shape
             if len(shp) != 3:
@@ -359,8 +405,10 @@ class Graph:
                 raise ValueError(f"crop {layer.name!r}: {a['crop']} leaves nothing of {ins[0]}")
             return (h - t - b, w - l - r, c)
         if layer.op in ("bn", "relu", "softmax", "identity", "act", "rescale", "normalization", "layernorm",
-                        "layerscale", "mha"):
+                        "layerscale", "mha", "winattn"):
             return ins[0]
+        if layer.op == "space_to_depth":
+            return (ins[0][0] // 2, ins[0][1] // 2, 4 * ins[0][2])
         if layer.op == "posembed":
             return (1, _tokens(ins[0]) + (1 if a.get("class_token") else 0), ins[0][-1])
         if layer.op == "binary":

@@ -248,6 +248,13 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
         if cfg.get("value_dim") is not None and int(cfg["value_dim"]) != a["key_dim"]:
             a["value_dim"] = int(cfg["value_dim"])
         return Layer(name, "mha", inputs, a)
+    if cls == "WindowAttention":                       # the project's own layer (graph/ir.py "winattn")
+        return Layer(name, "winattn", inputs,
+                     {"num_heads": int(cfg["num_heads"]), "key_dim": int(cfg["key_dim"]),
+                      "window": int(cfg["window_size"]), "shift": int(cfg.get("shift_size", 0)),
+                      "use_bias": bool(cfg.get("use_bias", True))})
+    if cls == "SpaceToDepth":                          # the project's own layer (graph/ir.py "space_to_depth")
+        return Layer(name, "space_to_depth", inputs, {"block": int(cfg.get("block_size", 2))})
     if cls == "ClassTokenPositionEmbedding":           # the project's own layer (graph/ir.py "posembed")
         return Layer(name, "posembed", inputs, {"class_token": bool(cfg.get("class_token", True))})
     if cls == "LayerScale":
@@ -399,6 +406,13 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
         cls = "MultiHeadAttention"
         cfg.update(num_heads=a["num_heads"], key_dim=a["key_dim"], value_dim=a.get("value_dim") or a["key_dim"],
                    dropout=0.0, use_bias=a.get("use_bias", True), output_shape=None, attention_axes=None)
+    elif L.op == "winattn":
+        cls = "WindowAttention"
+        cfg.update(num_heads=a["num_heads"], key_dim=a["key_dim"], window_size=a["window"],
+                   shift_size=a.get("shift", 0), use_bias=a.get("use_bias", True))
+    elif L.op == "space_to_depth":
+        cls = "SpaceToDepth"
+        cfg.update(block_size=a.get("block", 2))
     elif L.op == "posembed":
         cls = "ClassTokenPositionEmbedding"
         cfg.update(class_token=bool(a.get("class_token")))

@@ -131,7 +131,8 @@ def layer_costs(g: Graph, batch: int = 32, hw: Optional[HwModel] = None) -> Dict
             continue
         # deconv: its true MACs (input pixels x taps x cin x filters, the phase form multiplies no stuffed
         # zeros) against its bytes; upsample / crop have no MACs and cost their input + output traffic.
-        # mha: the MACs of its two projection GEMMs and the T x T core (graph/ir.py); posembed: its traffic
+        # mha: the MACs of its two projection GEMMs and the T x T core (graph/ir.py); posembed: its traffic.
+        # winattn: 4 H W C^2 + 2 H W M^2 C MACs (projections and the window-local core); space_to_depth: its traffic
         t = max(2.0 * macs / hw.mfma_flops, byts / hw.hbm_bw) + hw.launch_s
         out[n] = t
     return out

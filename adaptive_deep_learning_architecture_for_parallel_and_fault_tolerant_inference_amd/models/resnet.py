@@ -146,10 +146,13 @@ def init_weights(g: Graph, seed: int = 0, layers: Optional[List[str]] = None) ->
                     "beta": (rng.standard_normal(c) * 0.05).astype(np.float32)}
             for wname, _ in specs:                 # scale=False / center=False drop gamma / beta
                 out[wname] = vals[wname.rsplit("/", 1)[1]]
-        elif L.op == "mha":
-            # projections: fan-in C (h * dv for the output projection), biases zero
+        elif L.op in ("mha", "winattn"):
+            # projections: fan-in C (h * dv for the output projection), biases zero; a window attention's
+            # relative position bias table: N(0, 0.02)
             for wname, shp in specs:
-                if wname.endswith("/bias"):
+                if wname.endswith("/relative_position_bias_table"):
+                    out[wname] = (rng.standard_normal(shp) * 0.02).astype(np.float32)
+                elif wname.endswith("/bias"):
                     out[wname] = np.zeros(shp, np.float32)
                 else:
                     fan_in = shp[0] * shp[1] if "/attention_output/" in wname else shp[0]

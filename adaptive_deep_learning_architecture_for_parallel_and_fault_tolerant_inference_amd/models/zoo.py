@@ -16,12 +16,15 @@ takes an arbitrary Keras JSON):
 * ResNeXt-50 / -101 (32x4d)  (Conv2D(groups=32) 3x3 in every block, ResNet layer names)
 * ConvNeXt-Tiny ... -XLarge  (LayerNormalization, Dense on (H, W, C), LayerScale, a 7x7 Conv2D(groups=C))
 * ViT-Ti / S / B / L at patch 16  (MultiHeadAttention as self-attention, class token + position embedding)
+* Swin-Tiny / Small / Base / Large at patch 4, window 7  (WindowAttention with relative position bias and
+  shifted windows, SpaceToDepth patch merging)
 
 Parameter totals (Keras, include_top, 1000 classes; checked by tests):
 VGG16 138,357,544; VGG19 143,667,240; MobileNetV2 3,538,984; DenseNet121 8,062,504;
 EfficientNetB0 5,330,571; InceptionV3 23,851,784; ResNeXt50 25,097,128; ResNeXt101 44,315,560;
 ConvNeXt Tiny 28,589,128, Small 50,223,688, Base 88,591,464, Large 197,767,336, XLarge 350,196,968;
-ViT (published sizes, patch 16) Ti 5,717,416, S 22,050,664, B 86,567,656, L 304,326,632.
+ViT (published sizes, patch 16) Ti 5,717,416, S 22,050,664, B 86,567,656, L 304,326,632;
+Swin (published sizes) Tiny 28,288,354, Small 49,606,258, Base 87,768,224, Large 196,532,476.
 
 Not from `keras.applications` (models whose output is a map, not a class vector):
 
@@ -506,7 +509,72 @@ def build_vit(name: str = "vit_b16", classes: int = 1000, input_shape=None) -> G
     return g
 
 
+# -------------------------------------------------------------------- Swin
+# name -> (patch, window, width C, depths, heads, default input); micro: same naming / structure, for fast tests
+SWIN = {
+    "swin_tiny": (4, 7, 96, (2, 2, 6, 2), (3, 6, 12, 24), (224, 224, 3)),
+    "swin_small": (4, 7, 96, (2, 2, 18, 2), (3, 6, 12, 24), (224, 224, 3)),
+    "swin_base": (4, 7, 128, (2, 2, 18, 2), (4, 8, 16, 32), (224, 224, 3)),
+    "swin_large": (4, 7, 192, (2, 2, 18, 2), (6, 12, 24, 48), (224, 224, 3)),
+    "swin_micro": (4, 4, 32, (2, 2), (2, 4), (32, 32, 3)),
+}
+SWIN_EPS = 1e-5
+SWIN_MLP_RATIO = 4
+
+
+def build_swin(name: str = "swin_tiny", classes: int = 1000, input_shape=None) -> Graph:
+    """Swin Transformer (Liu et al. 2021; the published Tiny / Small / Base / Large at patch 4, window 7) as a
+    flat graph on (H, W, C) maps: a 4x4 / 4 patch conv and LayerNormalization; per stage `depth` blocks of
+    LayerNormalization -> WindowAttention -> Add and LayerNormalization -> Dense 4C -> GELU -> Dense C -> Add,
+    odd blocks shifted by M // 2 (none when the stage's map is a single window, as in the published model);
+    between stages SpaceToDepth -> LayerNormalization(4C) -> Dense(2C, no bias); then LayerNormalization,
+    GlobalAveragePooling2D and the Dense softmax head."""
+    patch, window, width, depths, heads, default_shape = SWIN[name]
+    shape = tuple(input_shape or default_shape)
+    if len(shape) != 3 or shape[0] % patch or shape[1] % patch:
+        raise ValueError(f"{name}: input {shape} is not (H, W, C) with H and W multiples of the {patch}-pixel patch")
+    g = Graph(name)
+    x = g.add(Layer("input_1", "input", [], {"shape": shape}))
+    x = _conv(g, x, f"{name}_patch_embed", width, patch, stride=patch)
+
+    def ln(x: str, nm: str) -> str:
+        return g.add(Layer(nm, "layernorm", [x], {"epsilon": SWIN_EPS}))
+
+    x = ln(x, f"{name}_patch_embed_ln")
+    for s, (depth, nh) in enumerate(zip(depths, heads)):
+        c = width << s
+        if s:
+            h, w, _ = g.layers[x].out_shape
+            if h % 2 or w % 2:
+                raise ValueError(f"{name}: stage {s}'s input map {h} x {w} cannot be merged 2 x 2 (input {shape})")
+            x = g.add(Layer(f"{name}_stage_{s}_merge", "space_to_depth", [x], {"block": 2}))
+            x = ln(x, f"{name}_stage_{s}_merge_ln")
+            x = g.add(Layer(f"{name}_stage_{s}_merge_reduction", "dense", [x], {"units": c, "use_bias": False}))
+        h, w, _ = g.layers[x].out_shape
+        if h % window or w % window:
+            raise ValueError(f"{name}: stage {s}'s {h} x {w} map is not a multiple of the {window} x {window} "
+                             f"window (input {shape})")
+        for i in range(depth):
+            nm = f"{name}_stage_{s}_block_{i}"
+            shift = window // 2 if i % 2 and (h, w) != (window, window) else 0
+            y = g.add(Layer(f"{nm}_attn", "winattn", [ln(x, f"{nm}_ln1")],
+                            {"num_heads": nh, "key_dim": c // nh, "window": window, "shift": shift,
+                             "use_bias": True}))
+            x = g.add(Layer(f"{nm}_add1", "add", [x, y]))
+            y = g.add(Layer(f"{nm}_mlp_fc1", "dense", [ln(x, f"{nm}_ln2")],
+                            {"units": SWIN_MLP_RATIO * c, "use_bias": True}))
+            y = g.add(Layer(f"{nm}_mlp_gelu", "act", [y], {"fn": "gelu"}))
+            y = g.add(Layer(f"{nm}_mlp_fc2", "dense", [y], {"units": c, "use_bias": True}))
+            x = g.add(Layer(f"{nm}_add2", "add", [x, y]))
+    x = ln(x, f"{name}_ln")
+    x = g.add(Layer(f"{name}_avg_pool", "gap", [x]))
+    g.add(Layer(f"{name}_head", "dense", [x], {"units": classes, "activation": "softmax", "use_bias": True}))
+    g.output_names = [f"{name}_head"]
+    return g
+
+
 BUILDERS: Dict[str, Callable[..., Graph]] = {
+    **{n: (lambda n: lambda **kw: build_swin(n, **kw))(n) for n in SWIN},
     **{n: (lambda n: lambda **kw: build_vit(n, **kw))(n) for n in VIT},
     **{n: (lambda n: lambda **kw: build_unet(n, **kw))(n) for n in UNET},
     **{n: (lambda n: lambda **kw: build_convnext(n, **kw))(n) for n in CONVNEXT},

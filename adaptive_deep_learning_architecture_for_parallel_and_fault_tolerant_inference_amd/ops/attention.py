@@ -1,5 +1,6 @@
-"""Wrappers for the self-attention core (csrc/kernels/attention.hip) and the ViT class token / position
-embedding kernel (csrc/kernels/layers.hip).
+"""Wrappers for the self-attention core (csrc/kernels/attention.hip), Swin's window attention core and its bias
+packer (csrc/kernels/window_attention.hip) and the ViT class token / position embedding kernel
+(csrc/kernels/layers.hip).
 
 Shapes, dtypes, strides and the 32-bit index range are checked here before any launch; a shape the kernels do
 not take is an error, never a fall-back to torch.
@@ -8,6 +9,7 @@ from __future__ import annotations
 
 from typing import Optional
 
+import numpy as np
 import torch
 
 from ._lib import kernels, ptr, stream_handle
@@ -47,6 +49,83 @@ def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, tokens: int, hea
         raise ValueError("attention: tensors must hold fewer than 2^31 elements (32-bit index math)")
     fn = kernels().attention_f32 if qkv.dtype == torch.float32 else kernels().attention_bf16
     fn(ptr(qkv), ptr(out), B, T, h, d, dv, int(ld_in), int(ld_out), stream_handle(stream))
+    return out
+
+
+def window_attention_tiles():
+    """(queries per block, keys per LDS tile) of the window attention's MFMA path; the packed bias' rows are
+    padded to the key tile."""
+    k = kernels()
+    return int(k.window_attention_query_tile()), int(k.window_attention_key_tile())
+
+
+def window_attention_path(key_dim: int) -> str:
+    """'mfma' or 'plain' (one wave per query) for a window attention head of this size."""
+    return "mfma" if kernels().window_attention_path(int(key_dim)) else "plain"
+
+
+def window_bias(table, window: int, shift: int, device=None) -> torch.Tensor:
+    """The bias a window attention kernel adds to its scores, packed once per layer: fp32
+    [classes][heads][Tp][Tp] with Tp = window^2 rounded up to the key tile and zeros in the padding.
+    bias[c, h, q, k] = table[index[q, k], h] + mask_c[q, k]: Swin's relative position bias (`table`
+    [(2M-1)^2][heads], numpy or torch) plus, under a shift, the additive -100 between tokens of different
+    regions.  Inside one window the regions only depend on whether the window is in the last window row and /
+    or the last window column, so there are four classes, c = 2 (last row) + (last column), and one without a
+    shift.  Token (i, j) of such a window has row part 1 for i < M - shift, else 2 (0 off the last window row),
+    the column part alike, and region 3 x row part + column part."""
+    from ..graph.ir import window_index
+    M, s = int(window), int(shift)
+    t = np.asarray(table.detach().cpu() if torch.is_tensor(table) else table, np.float32)
+    if M < 1 or not 0 <= s < M or t.ndim != 2 or t.shape[0] != (2 * M - 1) ** 2:
+        raise ValueError(f"window_bias: table {t.shape} is not [(2M-1)^2][heads] for window {M}, or the shift {s} "
+                         f"is not in [0, {M})")
+    T = M * M
+    kt = window_attention_tiles()[1]
+    Tp = (T + kt - 1) // kt * kt
+    rel = t[window_index(M).reshape(-1)].reshape(T, T, -1).transpose(2, 0, 1)          # (heads, T, T)
+    part = np.where(np.arange(M) < M - s, 1, 2)
+    out = np.zeros((4 if s else 1, t.shape[1], Tp, Tp), np.float32)
+    for c in range(out.shape[0]):
+        rows = part if c & 2 else np.zeros(M, np.int64)
+        cols = part if c & 1 else np.zeros(M, np.int64)
+        region = (3 * rows[:, None] + cols[None, :]).reshape(-1)
+        mask = np.where(region[:, None] != region[None, :], np.float32(-100.0), np.float32(0.0))
+        out[c, :, :T, :T] = rel + mask
+    res = torch.from_numpy(out)
+    return res.to(device) if device is not None else res
+
+
+def window_attention(qkv: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, batch: int, height: int, width: int,
+                     window: int, shift: int, heads: int, key_dim: int, stream=None) -> torch.Tensor:
+    """Swin window attention core on an NHWC map, nothing rolled or partitioned in memory
+    (csrc/kernels/window_attention.hip).  qkv [..., ld_in] holds batch * height * width rows of [Q | K | V]
+    (head-major, heads x key_dim each; Q already scaled), `bias` is what `window_bias` packed for this window and
+    shift, out [..., ld_out] gets heads * key_dim channels per row and zeros in the rest of the row.  fp32 or
+    bf16 activations (both tensors alike, the bias always fp32)."""
+    B, H, W, M, s, h, d = (int(v) for v in (batch, height, width, window, shift, heads, key_dim))
+    if qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"window_attention: fp32 or bf16 tensors, got {qkv.dtype}")
+    _chk(qkv, qkv.dtype, "qkv"); _chk(out, qkv.dtype, "out"); _chk(bias, torch.float32, "bias")
+    if min(B, H, W, M, h, d) < 1:
+        raise ValueError(f"window_attention: batch, map, window, heads and head size must be positive "
+                         f"({B}, {H}, {W}, {M}, {h}, {d})")
+    if H % M or W % M:
+        raise ValueError(f"window_attention: the {H} x {W} map is not a multiple of the {M} x {M} window")
+    if not 0 <= s < M:
+        raise ValueError(f"window_attention: shift {s} is not in [0, {M})")
+    kt = window_attention_tiles()[1]
+    Tp = (M * M + kt - 1) // kt * kt
+    if tuple(bias.shape) != (4 if s else 1, h, Tp, Tp):
+        raise ValueError(f"window_attention: bias{tuple(bias.shape)} is not {(4 if s else 1, h, Tp, Tp)} "
+                         f"(window_bias of window {M}, shift {s}, {h} heads)")
+    ld_in, ld_out = qkv.shape[-1], out.shape[-1]
+    if qkv.numel() != B * H * W * ld_in or out.numel() != B * H * W * ld_out or ld_in < 3 * h * d or ld_out < h * d:
+        raise ValueError(f"window_attention: qkv{tuple(qkv.shape)} out{tuple(out.shape)} do not hold {B} x {H} x {W} "
+                         f"rows of {h} heads of {d}")
+    if max(qkv.numel(), out.numel(), bias.numel(), B * H * W * h) >= 2 ** 31:
+        raise ValueError("window_attention: tensors must hold fewer than 2^31 elements (32-bit index math)")
+    fn = kernels().window_attention_f32 if qkv.dtype == torch.float32 else kernels().window_attention_bf16
+    fn(ptr(qkv), ptr(bias), ptr(out), B, H, W, M, s, h, d, int(ld_in), int(ld_out), stream_handle(stream))
     return out
 
 

@@ -437,6 +437,35 @@ def crop(x: torch.Tensor, out: torch.Tensor, top: int, left: int, C: Optional[in
     return out
 
 
+def space_to_depth(x: torch.Tensor, out: torch.Tensor, C: Optional[int] = None, stream=None) -> torch.Tensor:
+    """Swin patch merging's rearrangement (csrc/kernels/resize.hip): x [B,H,W,C] -> out [B,H/2,W/2,4C] with
+    out[..., (2 dx + dy) C + c] = x[:, 2y + dy, 2x + dx, c], the concatenation of x[0::2,0::2], x[1::2,0::2],
+    x[0::2,1::2], x[1::2,1::2]; a bit-exact copy.  This is not `tf.nn.space_to_depth`, whose block order is
+    (2 dy + dx).  fp32 or bf16; bf16 rows are padded to 8 channels with `C` real ones in x: the 4C real channels
+    of `out` are contiguous, the rest of its row is written as zeros and x's padding is never read."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"space_to_depth: fp32 or bf16 tensors, got {x.dtype}")
+    _chk(x, x.dtype, "x"); _chk(out, x.dtype, "out")
+    if x.dim() != 4 or out.dim() != 4:
+        raise ValueError(f"space_to_depth: bad shapes x{tuple(x.shape)} out{tuple(out.shape)}")
+    B, H, W, Cpx = x.shape
+    C = Cpx if C is None else int(C)
+    bf = x.dtype == torch.bfloat16
+    Cpy = (4 * C + 7) // 8 * 8 if bf else 4 * C
+    if (not bf and C != Cpx) or (bf and (Cpx % 8 or not 0 < C <= Cpx)):
+        raise ValueError(f"space_to_depth: fp32 rows are not padded, bf16 rows are padded to 8 channels (row {Cpx}, C={C})")
+    if H % 2 or W % 2 or H < 2 or W < 2 or tuple(out.shape) != (B, H // 2, W // 2, Cpy):
+        raise ValueError(f"space_to_depth: takes {tuple(x.shape)} (H and W even) to {(B, H // 2, W // 2, Cpy)}, "
+                         f"got {tuple(out.shape)}")
+    if max(x.numel(), out.numel()) >= 2 ** 31 or x.numel() == 0:
+        raise ValueError("space_to_depth: tensors must hold 1 .. 2^31 - 1 elements")
+    if bf:
+        kernels().space_to_depth_bf16(ptr(x), ptr(out), B, H, W, Cpx, Cpy, C, stream_handle(stream))
+    else:
+        kernels().space_to_depth_f32(ptr(x), ptr(out), B, H, W, C, stream_handle(stream))
+    return out
+
+
 def avgpool_f32(x: torch.Tensor, out: torch.Tensor, k, s: int, pads=((0, 0), (0, 0)), stream=None) -> torch.Tensor:
     _chk(x, torch.float32, "x"); _chk(out, torch.float32, "out")
     kh, kw = (k, k) if isinstance(k, int) else k

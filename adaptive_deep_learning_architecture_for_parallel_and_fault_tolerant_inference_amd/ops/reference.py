@@ -23,6 +23,11 @@ def _same(x: torch.Tensor, kh: int, kw: int, s: int, value: float = 0.0) -> torc
     return F.pad(x, (l, r, t, b), value=value)
 
 
+def _heads(b):
+    """A (heads, d) projection bias broadcast over (windows, heads, tokens, d); 0.0 (no bias) stays as it is."""
+    return b[:, None, :] if torch.is_tensor(b) else b
+
+
 def _act(y: torch.Tensor, act, alpha: float = 0.3) -> torch.Tensor:
     """Keras activations by name (tf.keras 2.15 definitions)."""
     if act in (None, "linear"):
@@ -154,6 +159,49 @@ class ReferenceExecutor:
             y = torch.einsum("bhqk,bkhd->bqhd", p, v)
             y = torch.einsum("bqhd,hdc->bqc", y, w("attention_output")) + b("attention_output")
             return y.reshape(ins[0].shape)
+        if L.op == "winattn":
+            # Swin (Liu et al. 2021) the published way: roll, partition into windows, a gather of the bias table,
+            # an explicit additive -100 mask between the regions of a shifted map, reverse, roll back
+            w = lambda p: self.w[f"{L.name}/{p}/kernel"]
+            b = lambda p: self.w.get(f"{L.name}/{p}/bias", 0.0)
+            B, H, W, C = ins[0].shape
+            M, s, h, d = int(a["window"]), int(a.get("shift", 0)), int(a["num_heads"]), int(a["key_dim"])
+
+            def partition(t):                   # (B, H, W, c) -> (B * windows, M * M, c)
+                c = t.shape[-1]
+                return t.reshape(B, H // M, M, W // M, M, c).permute(0, 1, 3, 2, 4, 5).reshape(-1, M * M, c)
+
+            x = torch.roll(ins[0], shifts=(-s, -s), dims=(1, 2)) if s else ins[0]
+            xw = partition(x)
+            q = (torch.einsum("ntc,chd->nhtd", xw, w("query")) + _heads(b("query"))) * (1.0 / float(d) ** 0.5)
+            k = torch.einsum("ntc,chd->nhtd", xw, w("key")) + _heads(b("key"))
+            v = torch.einsum("ntc,chd->nhtd", xw, w("value")) + _heads(b("value"))
+            coords = torch.stack(torch.meshgrid(torch.arange(M), torch.arange(M), indexing="ij")).flatten(1)
+            rel = (coords[:, :, None] - coords[:, None, :]).permute(1, 2, 0) + (M - 1)
+            index = (rel[..., 0] * (2 * M - 1) + rel[..., 1]).to(ins[0].device)
+            table = self.w[f"{L.name}/relative_position_bias_table"]
+            attn = q @ k.transpose(-2, -1) + table[index.reshape(-1)].reshape(M * M, M * M, h).permute(2, 0, 1)
+            if s:
+                img = torch.zeros((1, H, W, 1), dtype=ins[0].dtype, device=ins[0].device)
+                cnt = 0
+                for hs in (slice(0, -M), slice(-M, -s), slice(-s, None)):
+                    for ws in (slice(0, -M), slice(-M, -s), slice(-s, None)):
+                        img[:, hs, ws, :] = cnt
+                        cnt += 1
+                mw = img.reshape(1, H // M, M, W // M, M, 1).permute(0, 1, 3, 2, 4, 5).reshape(-1, M * M)
+                mask = mw[:, None, :] - mw[:, :, None]
+                mask = torch.where(mask != 0, torch.full_like(mask, -100.0), torch.zeros_like(mask))
+                nw = mask.shape[0]
+                attn = (attn.reshape(B, nw, h, M * M, M * M) + mask[None, :, None]).reshape(-1, h, M * M, M * M)
+            y = (torch.softmax(attn, dim=-1) @ v).permute(0, 2, 1, 3)                   # (n, t, h, d)
+            y = y.reshape(B, H // M, W // M, M, M, h * d).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, h * d)
+            if s:
+                y = torch.roll(y, shifts=(s, s), dims=(1, 2))
+            return (torch.einsum("bhwk,kc->bhwc", y, w("attention_output").reshape(h * d, -1))
+                    + b("attention_output"))
+        if L.op == "space_to_depth":
+            x = ins[0]
+            return torch.cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], dim=-1)
         if L.op == "posembed":
             x = ins[0].reshape(ins[0].shape[0], -1, ins[0].shape[-1])
             if a.get("class_token"):

@@ -56,7 +56,7 @@ class CpuExecutor:
 
     KINDS = ("conv", "gconv", "dwconv", "maxpool", "avgpool", "bn", "add", "relu", "act", "binary", "affine", "gmp", "copy",
              "concat", "gap", "dense", "softmax", "pad", "layernorm", "deconv", "upsample", "crop", "attention",
-             "posembed")
+             "posembed", "winattn", "space_to_depth")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], outputs: Optional[Sequence[str]] = None):
         self.g = g
@@ -125,6 +125,9 @@ class CpuExecutor:
                 n = st.p["layer"]
                 cls = weights[f"{n}/class_token"].reshape(-1) if st.p["class_token"] else None
                 self.packed[i] = (cls, np.ascontiguousarray(weights[f"{n}/position_embedding"], np.float32))
+            elif st.kind == "winattn":           # the raw table: the native op does the index and region math
+                self.packed[i] = (np.ascontiguousarray(
+                    weights[f"{st.p['layer']}/relative_position_bias_table"], np.float32),)
             elif st.kind == "affine":            # Keras Rescaling / Normalization: y = x * scale + shift
                 L = self.g.layers[st.p["layer"]]
                 c = L.out_shape[-1]
@@ -190,6 +193,12 @@ class CpuExecutor:
         elif k == "attention":
             m.attention(ins[0].reshape(-1, ins[0].shape[-1]), y.reshape(-1, y.shape[-1]), batch, int(p["tokens"]),
                         int(p["heads"]), int(p["key_dim"]), int(p["value_dim"]))
+        elif k == "winattn":
+            m.window_attention(ins[0].reshape(-1, ins[0].shape[-1]), self.packed[i][0], y.reshape(-1, y.shape[-1]),
+                               batch, int(p["height"]), int(p["width"]), int(p["window"]), int(p["shift"]),
+                               int(p["heads"]), int(p["key_dim"]))
+        elif k == "space_to_depth":
+            m.space_to_depth(ins[0], y)
         elif k == "posembed":
             cls, pos = self.packed[i]
             ct = 0 if cls is None else 1

@@ -79,7 +79,7 @@ class SliceExecutor:
 
     FP32_KINDS = ("conv", "pair", "dense", "maxpool", "gap", "softmax", "add", "bn", "relu", "pad", "copy",
                   "dwconv", "avgpool", "concat", "act", "binary", "affine", "stem_f32", "gconv", "layernorm",
-                  "deconv", "upsample", "crop", "attention", "posembed")
+                  "deconv", "upsample", "crop", "attention", "posembed", "winattn", "space_to_depth")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], batch: int, device="cuda",
                  outputs: Optional[Sequence[str]] = None, tune: bool = False, num_sets: int = 1,
@@ -243,6 +243,9 @@ class SliceExecutor:
                 self.packed[i] = self._pack_layernorm(weights, st, self.shape_of(st.out)[-1])
             elif st.kind == "posembed":
                 self.packed[i] = self._pack_posembed(weights, st)
+            elif st.kind == "winattn":           # relative position bias + shift mask, fp32 in both precisions
+                self.packed[i] = attn_ops.window_bias(weights[f"{st.p['layer']}/relative_position_bias_table"],
+                                                      st.p["window"], st.p["shift"], device=dev)
             elif st.kind == "deconv":            # the bounds-checked kernel on bf16 activations (no bf16 MFMA path)
                 kf, bf = self._folded(weights, st.p)      # (kh, kw, cin, filters): BN scales the last axis
                 self.packed[i] = conv_ops.pack_deconv_bf16(kf, bf, st.p["stride"], st.p["pads"], dev)
@@ -290,6 +293,9 @@ class SliceExecutor:
                 self.packed[i] = self._pack_layernorm(weights, st, self.shape_of(st.out)[-1])
             elif st.kind == "posembed":
                 self.packed[i] = self._pack_posembed(weights, st)
+            elif st.kind == "winattn":           # relative position bias + shift mask, fp32 in both precisions
+                self.packed[i] = attn_ops.window_bias(weights[f"{st.p['layer']}/relative_position_bias_table"],
+                                                      st.p["window"], st.p["shift"], device=dev)
             elif st.kind == "dwconv":
                 p = st.p
                 k = depthwise_kernel(weights, p["conv"])                      # (kh, kw, C), multiplier 1
@@ -327,11 +333,18 @@ class SliceExecutor:
                                  device=self.device)
 
     def _launch_tokens(self, i: int, st: Step, b, stream) -> None:
-        """The attention core and the position embedding: one wrapper each for both precisions."""
+        """The attention cores, the position embedding and space-to-depth: one wrapper each for both precisions."""
         if st.kind == "attention":
             p = st.p
             attn_ops.attention(b[st.ins[0]], b[st.out], self.batch, p["tokens"], p["heads"], p["key_dim"],
                                p["value_dim"], stream=stream)
+        elif st.kind == "winattn":
+            p = st.p
+            attn_ops.window_attention(b[st.ins[0]], self.packed[i], b[st.out], self.batch, p["height"], p["width"],
+                                      p["window"], p["shift"], p["heads"], p["key_dim"], stream=stream)
+        elif st.kind == "space_to_depth":
+            E.space_to_depth(b[st.ins[0]], b[st.out], C=self.g.layers[st.ins[0].split("#")[0]].out_shape[-1],
+                             stream=stream)
         else:
             cls, pos = self.packed[i]
             attn_ops.posembed(b[st.ins[0]], cls, pos, b[st.out], C=self.g.layers[st.p["layer"]].out_shape[-1],
@@ -806,7 +819,7 @@ class SliceExecutor:
                 gm, bt = self.packed[i]
                 E.layernorm(b[st.ins[0]], gm, bt, b[st.out], self.g.layers[st.p["layer"]].out_shape[-1], st.p["eps"],
                             stream=stream)
-            elif k in ("attention", "posembed"):
+            elif k in ("attention", "posembed", "winattn", "space_to_depth"):
                 self._launch_tokens(i, st, b, stream)
             elif k == "act":
                 E.act(b[st.ins[0]], b[st.out], st.p["mode"], st.p["alpha"], stream=stream)
@@ -936,7 +949,7 @@ class SliceExecutor:
         elif k == "layernorm":
             gm, bt = self.packed[i]
             E.layernorm_f32(b[st.ins[0]], gm, bt, b[st.out], st.p["eps"], stream=stream)
-        elif k in ("attention", "posembed"):
+        elif k in ("attention", "posembed", "winattn", "space_to_depth"):
             self._launch_tokens(i, st, b, stream)
         elif k == "deconv":
             conv_ops.deconv_forward_f32(b[st.ins[0]], self.packed[i], b[st.out], relu=st.p["relu"], stream=stream)

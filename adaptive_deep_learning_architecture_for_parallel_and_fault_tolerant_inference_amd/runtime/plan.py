@@ -25,6 +25,11 @@ kernels:
                internal (a cut can only name `n`); a kind of its own, so no pair, sibling, stem or
                bottleneck pass ever sees it
 * ``posembed`` ViT class token + learned position embedding
+* ``winattn``  the core of a Swin window attention layer `n`: like ``attention`` three steps, a ``conv``
+               `n#qkv`, this step `n#qkv` -> `n#ctx` on the (H, W, C) map (nothing is rolled or
+               partitioned in memory; the relative position bias and the shift mask are packed once
+               by the executor), and the output-projection ``conv`` with the block's Add as residual
+* ``space_to_depth`` Swin patch merging's 2 x 2 rearrangement, one copy step
 * ``gconv``    Conv2D(groups > 1) [+BN folded] [+ReLU/ReLU6], explicit pads; no
                residual fusion, and a kind of its own so that no pass written
                for dense convs (pair, siblings, stem, bottleneck) ever sees it
@@ -70,9 +75,13 @@ class Step:
 
 def tensor_shape(g: Graph, name: str) -> tuple:
     """Per-image shape of a plan tensor: the layer's own, or for the two internal tensors of a
-    MultiHeadAttention layer (`n#qkv`, `n#ctx`) a (1, T, channels) token map."""
+    MultiHeadAttention layer (`n#qkv`, `n#ctx`) a (1, T, channels) token map; those of a window attention
+    layer keep its (H, W) map."""
     base, _, tag = name.partition("#")
     L = g.layers[base]
+    if tag in ("qkv", "ctx") and L.op == "winattn":     # a window attention's stay (H, W, channels) maps
+        hd = int(L.attrs["num_heads"]) * int(L.attrs["key_dim"])
+        return tuple(L.out_shape[:-1]) + (3 * hd if tag == "qkv" else hd,)
     if tag in ("qkv", "ctx"):
         h, d = int(L.attrs["num_heads"]), int(L.attrs["key_dim"])
         dv = int(L.attrs.get("value_dim") or d)
@@ -388,7 +397,7 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
             steps.append(Step("layernorm", n, [R(L.inputs[0])], [n],
                               {"layer": n, "eps": float(a.get("epsilon", 1e-3))}))
             done.add(n)
-        elif L.op == "mha":
+        elif L.op in ("mha", "winattn"):
             h, d = int(a["num_heads"]), int(a["key_dim"])
             dv = int(a.get("value_dim") or d)
             tokens = 1
@@ -404,7 +413,12 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                         "packed_input": False, **head}
 
             steps.append(Step("conv", n + "#qkv", [R(L.inputs[0])], [], proj("qkv", h * (2 * d + dv), None)))
-            steps.append(Step("attention", n + "#ctx", [n + "#qkv"], [], {"layer": n, "tokens": tokens, **head}))
+            if L.op == "winattn":               # on the (H, W, C) map, windows and shift resolved by the kernel
+                steps.append(Step("winattn", n + "#ctx", [n + "#qkv"], [],
+                                  {"layer": n, "height": L.out_shape[0], "width": L.out_shape[1],
+                                   "window": int(a["window"]), "shift": int(a.get("shift", 0)), **head}))
+            else:
+                steps.append(Step("attention", n + "#ctx", [n + "#qkv"], [], {"layer": n, "tokens": tokens, **head}))
             cover = [n]
             res, out, relu = residual_add(n, cover)
             steps.append(Step("conv", out, [n + "#ctx"] + ([res] if res else []), cover,
@@ -414,6 +428,9 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
         elif L.op == "posembed":
             steps.append(Step("posembed", n, [R(L.inputs[0])], [n],
                               {"layer": n, "class_token": bool(a.get("class_token"))}))
+            done.add(n)
+        elif L.op == "space_to_depth":
+            steps.append(Step("space_to_depth", n, [R(L.inputs[0])], [n]))
             done.add(n)
         elif L.op == "gmp":
             steps.append(Step("gmp", n, [R(L.inputs[0])], [n]))

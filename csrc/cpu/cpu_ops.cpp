@@ -343,6 +343,91 @@ void crop2d(const Arr<float>& x, Arr<float>& y, int t, int l) {
                   sizeof(float) * OW * C);
 }
 
+// Swin patch merging's rearrangement: y [N,H/2,W/2,4C], y[n, i, j, (2 dx + dy) C + c] = x[n, 2i + dy, 2j + dx, c]
+void space_to_depth(const Arr<float>& x, Arr<float>& y) {
+  need(x.ndim() == 4 && y.ndim() == 4, "space_to_depth ranks");
+  const int N = x.shape(0), H = x.shape(1), W = x.shape(2), C = x.shape(3);
+  need(H % 2 == 0 && W % 2 == 0 && y.shape(0) == N && y.shape(1) == H / 2 && y.shape(2) == W / 2 &&
+           y.shape(3) == 4 * C, "space_to_depth shapes");
+  const float* xp = cptr(x);
+  float* yp = mptr(y);
+  py::gil_scoped_release nogil;
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int n = 0; n < N; ++n)
+    for (int i = 0; i < H / 2; ++i)
+      for (int j = 0; j < W / 2; ++j)
+        for (int dx = 0; dx < 2; ++dx)
+          for (int dy = 0; dy < 2; ++dy)
+            std::memcpy(yp + ((((size_t)n * (H / 2) + i) * (W / 2) + j) * 4 + 2 * dx + dy) * C,
+                        xp + (((size_t)n * H + 2 * i + dy) * W + 2 * j + dx) * C, sizeof(float) * C);
+}
+
+// Swin window attention core on the NHWC map, nothing rolled or partitioned in memory: the argument layout of the
+// GPU op (csrc/kernels/window_attention.hip) except that the bias is the raw table [(2M-1)^2][heads].  Token
+// (i, j) of window (wy, wx) is the map row ((wy M + i + s) mod H) W + (wx M + j + s) mod W; its score against
+// token (k, l) gets table[(i-k+M-1)(2M-1) + (j-l+M-1)][head], and -100 when s > 0 and the two lie in different
+// regions of the rolled frame (rows [0, H-M), [H-M, H-s), [H-s, H), columns alike).
+void window_attention(const Arr<float>& qkv, const Arr<float>& table, Arr<float>& out, int B, int H, int W, int M,
+                      int s, int heads, int d) {
+  need(qkv.ndim() >= 2 && out.ndim() >= 2 && B >= 1 && H >= 1 && W >= 1 && M >= 1 && heads >= 1 && d >= 1 &&
+           s >= 0 && s < M && H % M == 0 && W % M == 0, "window_attention args");
+  const long ld_in = qkv.shape(qkv.ndim() - 1), ld_out = out.shape(out.ndim() - 1);
+  need(qkv.size() == (long)B * H * W * ld_in && out.size() == (long)B * H * W * ld_out &&
+           ld_in >= 3l * heads * d && ld_out >= (long)heads * d, "window_attention shapes");
+  need(table.ndim() == 2 && table.shape(0) == (long)(2 * M - 1) * (2 * M - 1) && table.shape(1) == heads,
+       "window_attention table");
+  const float *xp = cptr(qkv), *tp = cptr(table);
+  float* yp = mptr(out);
+  const int T = M * M, nwy = H / M, nwx = W / M;
+  py::gil_scoped_release nogil;
+#pragma omp parallel
+  {
+    std::vector<float> p(T);
+    std::vector<long> row(T);
+    std::vector<int> reg(T);
+#pragma omp for collapse(3) schedule(static)
+    for (int b = 0; b < B; ++b)
+      for (int wy = 0; wy < nwy; ++wy)
+        for (int wx = 0; wx < nwx; ++wx) {
+          for (int t = 0; t < T; ++t) {
+            const int ry = wy * M + t / M, rx = wx * M + t % M;      // rolled frame
+            row[t] = ((long)b * H + (ry + s) % H) * W + (rx + s) % W;
+            reg[t] = 3 * (ry < H - M ? 0 : ry < H - s ? 1 : 2) + (rx < W - M ? 0 : rx < W - s ? 1 : 2);
+          }
+          for (int h = 0; h < heads; ++h)
+            for (int q = 0; q < T; ++q) {
+              const float* qr = xp + row[q] * ld_in + h * d;
+              float mx = -INFINITY;
+              for (int k = 0; k < T; ++k) {
+                const float* kr = xp + row[k] * ld_in + heads * d + h * d;
+                float sc = 0.f;
+                for (int i = 0; i < d; ++i) sc += qr[i] * kr[i];
+                sc += tp[(long)((q / M - k / M + M - 1) * (2 * M - 1) + (q % M - k % M + M - 1)) * heads + h];
+                if (s > 0 && reg[q] != reg[k]) sc += -100.f;
+                p[k] = sc;
+                mx = std::max(mx, sc);
+              }
+              float l = 0.f;
+              for (int k = 0; k < T; ++k) {
+                p[k] = std::exp(p[k] - mx);
+                l += p[k];
+              }
+              float* orow = yp + row[q] * ld_out + h * d;
+              for (int c = 0; c < d; ++c) orow[c] = 0.f;
+              for (int k = 0; k < T; ++k) {
+                const float* vr = xp + row[k] * ld_in + 2 * heads * d + h * d;
+                const float pk = p[k];
+                for (int c = 0; c < d; ++c) orow[c] += pk * vr[c];
+              }
+              const float inv = 1.f / l;
+              for (int c = 0; c < d; ++c) orow[c] *= inv;
+              if (h == heads - 1)
+                for (long c = (long)heads * d; c < ld_out; ++c) yp[row[q] * ld_out + c] = 0.f;
+            }
+        }
+  }
+}
+
 // Self-attention core, softmax(Q K^T) V per (image, head): qkv [B*T][ld_in] rows of [Q | K | V] (head-major, Q
 // already scaled by 1/sqrt(d)), out [B*T][ld_out] with heads * dv channels (the rest of a row becomes zero): the
 // argument layout of the GPU op (csrc/kernels/attention.hip).  fp32, the row maximum subtracted before the exponent.
@@ -673,6 +758,9 @@ PYBIND11_MODULE(_cpu, m) {
         py::arg("alpha") = 0.3f);
   m.def("attention", &attention, py::arg("qkv"), py::arg("out"), py::arg("B"), py::arg("T"), py::arg("heads"),
         py::arg("key_dim"), py::arg("value_dim"));
+  m.def("window_attention", &window_attention, py::arg("qkv"), py::arg("table"), py::arg("out"), py::arg("B"),
+        py::arg("H"), py::arg("W"), py::arg("window"), py::arg("shift"), py::arg("heads"), py::arg("key_dim"));
+  m.def("space_to_depth", &space_to_depth, py::arg("x"), py::arg("y"));
   m.def("layernorm", &layernorm, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("y"), py::arg("eps"));
   m.def("activation", &activation, py::arg("x"), py::arg("y"), py::arg("act"), py::arg("alpha") = 0.3f);
   m.def("binary", &binary, py::arg("a"), py::arg("b"), py::arg("y"), py::arg("op"), py::arg("act") = 0,

@@ -426,6 +426,25 @@ PYBIND11_MODULE(_C, m) {
   m.def("attention_path", &adapt::attention_path);
   m.def("attention_query_tile", &adapt::attention_query_tile);
   m.def("attention_key_tile", &adapt::attention_key_tile);
+  m.def("window_attention_f32", [](u64 qkv, u64 bias, u64 out, int B, int H, int W, int M, int shift, int heads, int d,
+                                   int ld_in, int ld_out, u64 s) {
+    check(adapt::window_attention_f32(P<const float>(qkv), P<const float>(bias), P<float>(out), B, H, W, M, shift,
+                                      heads, d, ld_in, ld_out, S(s)), "window_attention_f32");
+  });
+  m.def("window_attention_bf16", [](u64 qkv, u64 bias, u64 out, int B, int H, int W, int M, int shift, int heads, int d,
+                                    int ld_in, int ld_out, u64 s) {
+    check(adapt::window_attention_bf16(P<const bf16>(qkv), P<const float>(bias), P<bf16>(out), B, H, W, M, shift,
+                                       heads, d, ld_in, ld_out, S(s)), "window_attention_bf16");
+  });
+  m.def("window_attention_path", &adapt::window_attention_path);
+  m.def("window_attention_query_tile", &adapt::window_attention_query_tile);
+  m.def("window_attention_key_tile", &adapt::window_attention_key_tile);
+  m.def("space_to_depth_f32", [](u64 x, u64 y, int B, int H, int W, int C, u64 s) {
+    check(adapt::space_to_depth_f32(P<const float>(x), P<float>(y), B, H, W, C, S(s)), "space_to_depth_f32");
+  });
+  m.def("space_to_depth_bf16", [](u64 x, u64 y, int B, int H, int W, int Cpx, int Cpy, int C, u64 s) {
+    check(adapt::space_to_depth_bf16(P<const bf16>(x), P<bf16>(y), B, H, W, Cpx, Cpy, C, S(s)), "space_to_depth_bf16");
+  });
   m.def("posembed_f32", [](u64 x, u64 cls, u64 pos, u64 y, int B, int T, int C, int ct, u64 s) {
     check(adapt::posembed_f32(P<const float>(x), P<const float>(cls), P<const float>(pos), P<float>(y), B, T, C, ct,
                               S(s)), "posembed_f32");

@@ -381,6 +381,23 @@ hipError_t attention_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, i
 int attention_path(int d, int dv);     // 1: MFMA path, 0: plain kernel
 int attention_query_tile();            // queries per block of the MFMA path
 int attention_key_tile();              // keys per LDS tile of the MFMA path
+// Swin window attention core (window_attention.hip): qkv the NHWC map [B*H*W][ld_in], rows of [Q | K | V]
+// (head-major, heads x d each, Q pre-scaled), attention inside M x M windows of the grid shifted by `shift`,
+// nothing rolled or partitioned in memory.  bias [classes][heads][Tp][Tp] fp32 (Tp = M^2 rounded up to the key
+// tile; 4 classes under a shift, else 1) holds the relative position bias plus the shift mask, host-packed.  out
+// [B*H*W][ld_out] with heads*d true channels (the rest of a row is written as zeros).  d a multiple of 16 up to
+// 128 runs on the fp32 MFMA, every other size on a plain kernel.
+hipError_t window_attention_f32(const float* qkv, const float* bias, float* out, int B, int H, int W, int M, int shift,
+                                int heads, int d, int ld_in, int ld_out, hipStream_t s);
+hipError_t window_attention_bf16(const bf16* qkv, const float* bias, bf16* out, int B, int H, int W, int M, int shift,
+                                 int heads, int d, int ld_in, int ld_out, hipStream_t s);
+int window_attention_path(int d);      // 1: MFMA path, 0: plain kernel
+int window_attention_query_tile();     // queries per block of the MFMA path
+int window_attention_key_tile();       // keys per LDS tile of the MFMA path; the packed bias rows are padded to it
+// Swin patch merging's rearrangement (resize.hip): y[b][oy][ox][(2 dx + dy) C + c] = x[b][2 oy + dy][2 ox + dx][c],
+// a bit-exact copy; bf16 rows are Cpx / Cpy wide with C / 4 C true channels, y's padding written as zeros
+hipError_t space_to_depth_f32(const float* x, float* y, int B, int H, int W, int C, hipStream_t s);
+hipError_t space_to_depth_bf16(const bf16* x, bf16* y, int B, int H, int W, int Cpx, int Cpy, int C, hipStream_t s);
 // ViT class token + position embedding (layers.hip): y[b][0] = cls + pos[0], y[b][ct + t] = x[b][t] + pos[ct + t];
 // cls [C] (null without a class token), pos [T + ct][C] fp32; bf16 rows are Cp wide, padding written as zeros
 hipError_t posembed_f32(const float* x, const float* cls, const float* pos, float* y, int B, int T, int C, int ct,

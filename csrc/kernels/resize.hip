@@ -1,4 +1,5 @@
-// UpSampling2D (nearest / bilinear) and Cropping2D, NHWC, fp32 and bf16, for gfx950.
+// UpSampling2D (nearest / bilinear), Cropping2D and Swin's space-to-depth (described at its kernel below), NHWC,
+// fp32 and bf16, for gfx950.
 //
 //   nearest   y[b][oy][ox][c] = x[b][oy / SH][ox / SW][c]                                    (a bit-exact copy)
 //   bilinear  tf.image.resize with half-pixel centres: fy = max((oy + 0.5) / SH - 0.5, 0), y0 = floor(fy),
@@ -150,7 +151,57 @@ hipError_t resize_bf16(const bf16* x, bf16* y, const ResizeGeom& g, int Cp, int 
   return hipGetLastError();
 }
 
+// Swin patch merging's rearrangement: y[b][oy][ox][(2 dx + dy) C + c] = x[b][2 oy + dy][2 ox + dx][c], a bit-exact
+// copy.  x rows are ldx wide with C true channels, y rows ldy wide with 4 C true channels, contiguous; the rest
+// of a y row is written as zeros and the padding of x is never read.  VEC: one thread per 16-byte vector (C a
+// multiple of the vector, so a vector never straddles two source pixels and there is no padding); otherwise one
+// thread per element of y.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(RS_NT) void space_to_depth_kernel(const T* __restrict__ x, T* __restrict__ y, int H,
+                                                               int W, int C, int ldx, int ldy, int total) {
+  constexpr int N = VEC ? 16 / (int)sizeof(T) : 1;
+  const int idx = blockIdx.x * RS_NT + threadIdx.x;
+  if (idx >= total) return;
+  const int per = ldy / N;
+  const int c0 = (idx % per) * N;
+  int pix = idx / per;
+  const int OW = W >> 1, OH = H >> 1;
+  const int ox = pix % OW;
+  pix /= OW;
+  const int oy = pix % OH, img = pix / OH;
+  if (c0 >= 4 * C) {                                  // layout padding of the output row (scalar path only)
+    y[idx] = T(0.f);
+    return;
+  }
+  const int blk = c0 / C, c = c0 - blk * C;
+  const int src = ((img * H + 2 * oy + (blk & 1)) * W + 2 * ox + (blk >> 1)) * ldx + c;
+  if (VEC) ((u32x4*)y)[idx] = *(const u32x4*)(x + src);
+  else y[idx] = x[src];
+}
+
+template <typename T>
+hipError_t space_to_depth_launch(const T* x, T* y, int B, int H, int W, int C, int ldx, int ldy, hipStream_t s) {
+  constexpr int N = 16 / (int)sizeof(T);
+  if (B < 1 || H < 2 || W < 2 || H % 2 || W % 2 || C < 1 || ldx < C || (long)ldy < 4l * C) return hipErrorInvalidValue;
+  if ((double)B * H * W * ldx >= 2147483648.0 || (double)B * (H / 2) * (W / 2) * ldy >= 2147483648.0)
+    return hipErrorInvalidValue;
+  const bool vec = C % N == 0 && ldx == C && ldy == 4 * C && aligned16(x) && aligned16(y);
+  const int total = B * (H / 2) * (W / 2) * (vec ? ldy / N : ldy);
+  const dim3 grid((unsigned)((total + RS_NT - 1) / RS_NT));
+  if (vec) hipLaunchKernelGGL((space_to_depth_kernel<T, true>), grid, dim3(RS_NT), 0, s, x, y, H, W, C, ldx, ldy, total);
+  else hipLaunchKernelGGL((space_to_depth_kernel<T, false>), grid, dim3(RS_NT), 0, s, x, y, H, W, C, ldx, ldy, total);
+  return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t space_to_depth_f32(const float* x, float* y, int B, int H, int W, int C, hipStream_t s) {
+  return space_to_depth_launch<float>(x, y, B, H, W, C, C, 4 * C, s);
+}
+
+hipError_t space_to_depth_bf16(const bf16* x, bf16* y, int B, int H, int W, int Cpx, int Cpy, int C, hipStream_t s) {
+  return space_to_depth_launch<bf16>(x, y, B, H, W, C, Cpx, Cpy, s);
+}
 
 hipError_t upsample_f32(const float* x, float* y, int B, int H, int W, int C, int SH, int SW, int bilinear,
                         hipStream_t s) {

@@ -13,7 +13,7 @@ worker list / cut list in the source) (`README.md:36-56`).  Subcommands:
   summary      model summary (layers, shapes, params)
 
 --model takes a family name (resnet50/101/152, vgg16/19, mobilenet_v2,
-densenet121/169/201, convnext_tiny ... convnext_xlarge, unet, unet_bilinear, vit_ti16 ... vit_l16, swin_tiny ... swin_large, ...: models/zoo.py) or a Keras ``model.to_json()`` file (*.json), with
+densenet121/169/201, convnext_tiny ... convnext_xlarge, unet, unet_bilinear, vit_ti16 ... vit_l16, swin_tiny ... swin_large, sd_vae_decoder, ...: models/zoo.py) or a Keras ``model.to_json()`` file (*.json), with
 --weights pointing at its ``get_weights()`` list saved as .npz.
 
 All take --config FILE (YAML) plus ADAPT_* environment overrides (utils/config.py).

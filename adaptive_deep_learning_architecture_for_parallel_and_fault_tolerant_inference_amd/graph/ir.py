@@ -44,6 +44,8 @@ OPS = (
     "normalization",  # Keras Normalization(axis=-1): weights mean, variance, count
     "layernorm",  # Keras LayerNormalization over the last axis: attrs epsilon; center / scale only when False
     "layerscale",  # ConvNeXt LayerScale: y = x * gamma (per channel); attrs init_values
+    "groupnorm",  # Keras GroupNormalization over (H, W, C / G) of an (H, W, C) map: attrs groups (the resolved G;
+                  # Keras' groups=-1, instance norm, is stored as C), epsilon; center / scale only when False
     "deconv",     # Keras Conv2DTranspose: filters, kernel=(kh,kw), stride, padding('valid'|'same'), use_bias,
                   # activation; kernel (kh, kw, filters, cin) (Keras HWOI), no output_padding, no dilation
     "upsample",   # Keras UpSampling2D: size=(sh,sw), interpolation ('nearest' | 'bilinear', half-pixel centres)
@@ -208,7 +210,7 @@ class Layer:
         if self.op == "normalization":
             c = in_shapes[0][-1]
             return [(f"{self.name}/mean", (c,)), (f"{self.name}/variance", (c,)), (f"{self.name}/count", ())]
-        if self.op == "layernorm":
+        if self.op in ("layernorm", "groupnorm"):
             # Keras omits gamma for scale=False and beta for center=False, as BatchNormalization does
             c = in_shapes[0][-1]
             keep = (("gamma", self.attrs.get("scale", True)), ("beta", self.attrs.get("center", True)))
@@ -327,6 +329,17 @@ class Graph:
             if not isinstance(gr, int) or gr < 1 or cin % gr or layer.attrs["filters"] % gr:
                 raise ValueError(f"conv {layer.name!r}: groups={gr} must divide the input channels ({cin}) "
                                  f"and filters ({layer.attrs['filters']})")
+        if layer.op == "groupnorm":
+            shp = self.layers[layer.inputs[0]].out_shape if len(layer.inputs) == 1 else ()
+            gr = layer.attrs.get("groups", 32)
+            if len(shp) != 3:
+                raise ValueError(f"groupnorm {layer.name!r}: needs one (H, W, C) input, got {tuple(shp)}")
+            if not isinstance(gr, int) or isinstance(gr, bool) or gr == 0 or gr < -1:
+                raise ValueError(f"groupnorm {layer.name!r}: groups must be a positive int or -1, got {gr!r}")
+            gr = shp[-1] if gr == -1 else gr
+            if shp[-1] % gr:
+                raise ValueError(f"groupnorm {layer.name!r}: groups={gr} must divide the {shp[-1]} channels")
+            layer.attrs["groups"] = gr              # the resolved G
         if layer.op == "upsample":
             sz = layer.attrs.get("size")
             if (not isinstance(sz, tuple) or len(sz) != 2 or any(not isinstance(v, int) or v < 1 for v in sz)
@@ -405,7 +418,7 @@ class Graph:
                 raise ValueError(f"crop {layer.name!r}: {a['crop']} leaves nothing of {ins[0]}")
             return (h - t - b, w - l - r, c)
         if layer.op in ("bn", "relu", "softmax", "identity", "act", "rescale", "normalization", "layernorm",
-                        "layerscale", "mha", "winattn"):
+                        "layerscale", "mha", "winattn", "groupnorm"):
             return ins[0]
         if layer.op == "space_to_depth":
             return (ins[0][0] // 2, ins[0][1] // 2, 4 * ins[0][2])

@@ -241,6 +241,17 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
             if not cfg.get(k, True):
                 a[k] = False
         return Layer(name, "layernorm", inputs, a)
+    if cls == "GroupNormalization":
+        axis = cfg.get("axis", -1)
+        axis = axis[0] if isinstance(axis, (list, tuple)) and len(axis) == 1 else axis
+        if axis not in (-1, 3):
+            raise NotImplementedError(f"{name}: GroupNormalization over axis {cfg.get('axis')} (only the channel "
+                                      f"axis of an (H, W, C) map, -1 or 3, is supported)")
+        a = {"groups": int(cfg.get("groups", 32)), "epsilon": float(cfg.get("epsilon", 1e-3))}
+        for k in ("center", "scale"):
+            if not cfg.get(k, True):
+                a[k] = False
+        return Layer(name, "groupnorm", inputs, a)
     if cls == "MultiHeadAttention":
         # the call (self-attention only) and attention_axes / output_shape are checked in from_keras_json
         a = {"num_heads": int(cfg["num_heads"]), "key_dim": int(cfg["key_dim"]),
@@ -401,6 +412,10 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
     elif L.op == "layernorm":
         cls = "LayerNormalization"
         cfg.update(axis=[-1], epsilon=a.get("epsilon", 1e-3), center=a.get("center", True),
+                   scale=a.get("scale", True))
+    elif L.op == "groupnorm":
+        cls = "GroupNormalization"
+        cfg.update(groups=a["groups"], axis=-1, epsilon=a.get("epsilon", 1e-3), center=a.get("center", True),
                    scale=a.get("scale", True))
     elif L.op == "mha":
         cls = "MultiHeadAttention"

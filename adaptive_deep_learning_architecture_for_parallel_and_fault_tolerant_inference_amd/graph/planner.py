@@ -129,6 +129,11 @@ def layer_costs(g: Graph, batch: int = 32, hw: Optional[HwModel] = None) -> Dict
             byts = g.tensor_bytes(n, hw.act_bytes) * batch   # residual read inside the conv epilogue
             out[n] = byts / hw.hbm_bw
             continue
+        if L.op == "groupnorm":
+            # bytes-bound like layernorm, with its pass count: the split form (csrc/kernels/groupnorm.hip) reads
+            # the map twice and writes it once, three launches.  Uncalibrated: no planner fit includes a GN model
+            out[n] = 1.5 * byts / hw.hbm_bw + 3 * hw.launch_s
+            continue
         # deconv: its true MACs (input pixels x taps x cin x filters, the phase form multiplies no stuffed
         # zeros) against its bytes; upsample / crop have no MACs and cost their input + output traffic.
         # mha: the MACs of its two projection GEMMs and the T x T core (graph/ir.py); posembed: its traffic.

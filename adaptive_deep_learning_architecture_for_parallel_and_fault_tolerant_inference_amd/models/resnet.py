@@ -140,7 +140,7 @@ def init_weights(g: Graph, seed: int = 0, layers: Optional[List[str]] = None) ->
                     "moving_variance": rng.uniform(0.5, 1.5, c).astype(np.float32)}
             for wname, _ in specs:                 # scale=False / center=False drop gamma / beta
                 out[wname] = vals[wname.rsplit("/", 1)[1]]
-        elif L.op == "layernorm":
+        elif L.op in ("layernorm", "groupnorm"):
             c = g.in_shapes(n)[0][-1]
             vals = {"gamma": rng.uniform(0.8, 1.2, c).astype(np.float32),
                     "beta": (rng.standard_normal(c) * 0.05).astype(np.float32)}

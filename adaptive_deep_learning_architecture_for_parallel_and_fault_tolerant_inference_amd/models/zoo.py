@@ -30,6 +30,10 @@ Not from `keras.applications` (models whose output is a map, not a class vector)
 
 * U-Net (`unet`, `unet_bilinear`, test size `unet_tiny`): Conv2DTranspose or UpSampling2D decoders, skip
   Concatenates; 31,031,745 parameters at base 64, depth 4, one class, RGB input.
+* Stable Diffusion VAE decoder (`sd_vae_decoder`, test size `vae_decoder_micro`): GroupNormalization + swish
+  residual blocks, one-head MultiHeadAttention on the (H, W, C) map, nearest UpSampling2D; a 64 x 64 x 4 latent
+  to a 512 x 512 x 3 image, 49,490,199 parameters (the published decoder's 49,490,179 and the 20 of the 1x1
+  post-quantisation conv in front of it).
 """
 from __future__ import annotations
 
@@ -462,6 +466,61 @@ def build_unet(name: str = "unet", classes: int = 1, input_shape=None, base: int
     return g
 
 
+# ------------------------------------------------- Stable Diffusion VAE decoder
+# name -> (widths per level, residual blocks per level, GN groups, latent shape); micro: same naming / structure
+VAE_DECODER = {
+    "sd_vae_decoder": ((512, 512, 256, 128), 3, 32, (64, 64, 4)),
+    "vae_decoder_micro": ((32, 32, 16, 8), 1, 4, (8, 8, 4)),
+}
+VAE_EPS = 1e-5
+VAE_LATENT_SCALE = 0.18215
+
+
+def build_vae_decoder(name: str = "sd_vae_decoder", input_shape=None) -> Graph:
+    """The Stable Diffusion v1 VAE decoder as KerasCV publishes it, as flat layers in its creation order:
+    Rescaling(1 / 0.18215), the 1x1 post-quantisation conv, a 3x3 conv to the widest level, the middle (residual
+    block, attention block, residual block), then per level its residual blocks and, between levels, nearest
+    UpSampling2D(2) and a 3x3 conv; GroupNormalization, swish and a 3x3 conv to RGB close it.  A residual block is
+    GN, swish, 3x3 conv, GN, swish, 3x3 conv plus the shortcut (a 1x1 conv where the width changes); the attention
+    block is GN, a one-head MultiHeadAttention of key_dim C over the map (the published q / k / v / out 1x1 convs
+    are its four projections: the same parameters) and the Add.  Every conv is 'same'."""
+    widths, nblocks, groups, default_shape = VAE_DECODER[name]
+    g = Graph(name)
+    x = g.add(Layer("input_1", "input", [], {"shape": tuple(input_shape or default_shape)}))
+
+    def gn(x: str, nm: str) -> str:
+        return g.add(Layer(nm, "groupnorm", [x], {"groups": groups, "epsilon": VAE_EPS}))
+
+    def swish(x: str, nm: str) -> str:
+        return g.add(Layer(nm, "act", [x], {"fn": "swish"}))
+
+    def block(x: str, nm: str, f: int) -> str:
+        y = _conv(g, swish(gn(x, f"{nm}_norm1"), f"{nm}_swish1"), f"{nm}_conv1", f, 3, padding="same")
+        y = _conv(g, swish(gn(y, f"{nm}_norm2"), f"{nm}_swish2"), f"{nm}_conv2", f, 3, padding="same")
+        if g.layers[x].out_shape[-1] != f:
+            x = _conv(g, x, f"{nm}_shortcut", f, 1)
+        return g.add(Layer(f"{nm}_add", "add", [x, y]))
+
+    x = g.add(Layer("rescaling", "rescale", [x], {"scale": 1.0 / VAE_LATENT_SCALE, "offset": 0.0}))
+    x = _conv(g, x, "post_quant_conv", g.layers[x].out_shape[-1], 1)
+    x = _conv(g, x, "conv_in", widths[0], 3, padding="same")
+    x = block(x, "mid_block1", widths[0])
+    y = g.add(Layer("mid_attn", "mha", [gn(x, "mid_attn_norm")],
+                    {"num_heads": 1, "key_dim": widths[0], "use_bias": True}))
+    x = g.add(Layer("mid_attn_add", "add", [x, y]))
+    x = block(x, "mid_block2", widths[0])
+    for i, f in enumerate(widths):
+        for j in range(nblocks):
+            x = block(x, f"up{i}_block{j + 1}", f)
+        if i + 1 < len(widths):
+            x = g.add(Layer(f"up{i}_upsample", "upsample", [x], {"size": (2, 2), "interpolation": "nearest"}))
+            x = _conv(g, x, f"up{i}_conv", f, 3, padding="same")
+    x = swish(gn(x, "norm_out"), "swish_out")
+    x = _conv(g, x, "conv_out", 3, 3, padding="same")
+    g.output_names = [x]
+    return g
+
+
 # --------------------------------------------------------------------- ViT
 # name -> (patch, width, depth, heads, mlp, default input); micro: same naming / structure, for fast tests
 VIT = {
@@ -576,6 +635,7 @@ def build_swin(name: str = "swin_tiny", classes: int = 1000, input_shape=None) -
 BUILDERS: Dict[str, Callable[..., Graph]] = {
     **{n: (lambda n: lambda **kw: build_swin(n, **kw))(n) for n in SWIN},
     **{n: (lambda n: lambda **kw: build_vit(n, **kw))(n) for n in VIT},
+    **{n: (lambda n: lambda **kw: build_vae_decoder(n, **kw))(n) for n in VAE_DECODER},
     **{n: (lambda n: lambda **kw: build_unet(n, **kw))(n) for n in UNET},
     **{n: (lambda n: lambda **kw: build_convnext(n, **kw))(n) for n in CONVNEXT},
     "vgg16": lambda **kw: build_vgg("vgg16", **kw),

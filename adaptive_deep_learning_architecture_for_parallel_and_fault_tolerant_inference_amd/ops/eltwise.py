@@ -390,6 +390,85 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: tor
     return out
 
 
+GROUPNORM_PATHS = {0: "scalar split", 1: "vector split", 2: "vector single launch"}
+
+
+def _groupnorm_geom(B: int, P: int, C: int, groups: int, bf16: bool):
+    """(C stored, G): bf16 rows are stored padded to 8 channels; Keras' groups=-1 is one group per channel."""
+    G = C if groups == -1 else int(groups)
+    if min(B, P, C) < 1 or G < 1 or C % G:
+        raise ValueError(f"groupnorm: groups={groups} must be -1 or a positive divisor of the {C} channels "
+                         f"(batch {B}, {P} pixels)")
+    return (-(-C // 8) * 8 if bf16 else C), G
+
+
+def groupnorm_path(B: int, P: int, C: int, groups: int, bf16: bool) -> int:
+    """The path csrc/kernels/groupnorm.hip takes for B images of P pixels x C channels (GROUPNORM_PATHS):
+    0 scalar accesses, 1 vector accesses with a statistics and an apply launch, 2 vector accesses in one launch."""
+    Cs, G = _groupnorm_geom(B, P, C, groups, bf16)
+    return int(kernels().groupnorm_path(B, P, C, Cs, G, bool(bf16)))
+
+
+def groupnorm_slabs(B: int, P: int, C: int, groups: int, bf16: bool) -> int:
+    """Pixel slabs per image of the statistics launch (1 on the single-launch path)."""
+    Cs, G = _groupnorm_geom(B, P, C, groups, bf16)
+    return int(kernels().groupnorm_slabs(B, P, C, Cs, G, bool(bf16)))
+
+
+def groupnorm_workspace(B: int, P: int, C: int, groups: int, bf16: bool) -> int:
+    """fp32 elements of workspace `groupnorm_f32` / `groupnorm` need for that shape (0 on the single-launch path):
+    per-slab (n, mean, M2) partials, then the finalised (mu, rstd) per (image, group)."""
+    Cs, G = _groupnorm_geom(B, P, C, groups, bf16)
+    return int(kernels().groupnorm_workspace_floats(B, P, C, Cs, G, bool(bf16)))
+
+
+def _groupnorm_args(what, x, gamma, beta, out, C, groups, workspace, dtype):
+    _chk(x, dtype, "x"); _chk(out, dtype, "out")
+    _chk(gamma, torch.float32, "gamma"); _chk(beta, torch.float32, "beta")
+    Cs = x.shape[-1] if x.dim() == 4 else 0
+    if (x.dim() != 4 or out.shape != x.shape or gamma.numel() != Cs or beta.numel() != Cs or not 0 < C <= Cs
+            or x.numel() == 0 or x.numel() >= 2 ** 31):
+        raise ValueError(f"{what}: bad shapes x{tuple(x.shape)} out{tuple(out.shape)} gamma{tuple(gamma.shape)} "
+                         f"beta{tuple(beta.shape)} C={C}")
+    B, P = x.shape[0], x.shape[1] * x.shape[2]
+    bf16 = dtype == torch.bfloat16
+    if _groupnorm_geom(B, P, C, groups, bf16)[0] != Cs:
+        raise ValueError(f"{what}: {C} channels are stored as {_groupnorm_geom(B, P, C, groups, bf16)[0]}, got {Cs}")
+    G = C if groups == -1 else int(groups)
+    need = groupnorm_workspace(B, P, C, G, bf16)
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.float32, device=x.device)
+    if need:
+        _chk(workspace, torch.float32, "workspace")
+        if workspace.numel() < need:
+            raise ValueError(f"{what}: workspace holds {workspace.numel()} floats, {need} needed")
+    return B, P, G, (ptr(workspace) if need else 0), (workspace.numel() if need else 0)
+
+
+def groupnorm_f32(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: torch.Tensor, groups: int,
+                  eps: float, act: int = 0, alpha: float = 0.3, workspace: Optional[torch.Tensor] = None,
+                  stream=None) -> torch.Tensor:
+    """fp32 GroupNormalization (csrc/kernels/groupnorm.hip): x [B, H, W, C], gamma / beta [C], `groups` groups of
+    C / groups channels (-1: one per channel), then activation `act` (ActMode).  `workspace`: fp32
+    [groupnorm_workspace(...)], allocated here when None (pass one to stay graph-capturable)."""
+    C = x.shape[-1]
+    B, P, G, ws, nws = _groupnorm_args("groupnorm_f32", x, gamma, beta, out, C, groups, workspace, torch.float32)
+    kernels().groupnorm_f32(ptr(x), ptr(gamma), ptr(beta), ptr(out), ws, nws, B, P, C, G, float(eps), int(act),
+                            float(alpha), stream_handle(stream))
+    return out
+
+
+def groupnorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: torch.Tensor, C: int, groups: int,
+              eps: float, act: int = 0, alpha: float = 0.3, workspace: Optional[torch.Tensor] = None,
+              stream=None) -> torch.Tensor:
+    """bf16 GroupNormalization over the first C of the Cp stored channels: x [B, H, W, Cp], gamma / beta fp32 [Cp].
+    Channels C..Cp-1 are layout padding: out of the statistics whatever they hold, zeros in `out`."""
+    B, P, G, ws, nws = _groupnorm_args("groupnorm", x, gamma, beta, out, int(C), groups, workspace, torch.bfloat16)
+    kernels().groupnorm(ptr(x), ptr(gamma), ptr(beta), ptr(out), ws, nws, B, P, x.shape[-1], int(C), G, float(eps),
+                        int(act), float(alpha), stream_handle(stream))
+    return out
+
+
 def _resize_args(x: torch.Tensor, out: torch.Tensor, dtype, what: str, C):
     if dtype not in (torch.float32, torch.bfloat16):
         raise ValueError(f"{what}: fp32 or bf16 tensors, got {dtype}")

@@ -56,7 +56,7 @@ class CpuExecutor:
 
     KINDS = ("conv", "gconv", "dwconv", "maxpool", "avgpool", "bn", "add", "relu", "act", "binary", "affine", "gmp", "copy",
              "concat", "gap", "dense", "softmax", "pad", "layernorm", "deconv", "upsample", "crop", "attention",
-             "posembed", "winattn", "space_to_depth")
+             "posembed", "winattn", "space_to_depth", "groupnorm")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], outputs: Optional[Sequence[str]] = None):
         self.g = g
@@ -117,7 +117,7 @@ class CpuExecutor:
                 eps = self.g.layers[st.p["bn"]].attrs.get("epsilon", 1e-3)
                 sc = gm / np.sqrt(var + eps)
                 self.packed[i] = (sc.astype(np.float32), (bt - mu * sc).astype(np.float32))
-            elif st.kind == "layernorm":         # Keras' defaults for scale=False / center=False
+            elif st.kind in ("layernorm", "groupnorm"):     # Keras' defaults for scale=False / center=False
                 c = self.g.layers[st.p["layer"]].out_shape[-1]
                 self.packed[i] = tuple(np.ascontiguousarray(weights.get(f"{st.p['layer']}/{w}", d), np.float32)
                                        for w, d in (("gamma", np.ones(c)), ("beta", np.zeros(c))))
@@ -190,6 +190,9 @@ class CpuExecutor:
         elif k == "layernorm":
             gm, bt = self.packed[i]
             m.layernorm(ins[0], gm, bt, y, float(p["eps"]))
+        elif k == "groupnorm":
+            gm, bt = self.packed[i]
+            m.groupnorm(ins[0], gm, bt, y, int(p["groups"]), float(p["eps"]), int(p["act"]), 0.3)
         elif k == "attention":
             m.attention(ins[0].reshape(-1, ins[0].shape[-1]), y.reshape(-1, y.shape[-1]), batch, int(p["tokens"]),
                         int(p["heads"]), int(p["key_dim"]), int(p["value_dim"]))

@@ -79,7 +79,7 @@ class SliceExecutor:
 
     FP32_KINDS = ("conv", "pair", "dense", "maxpool", "gap", "softmax", "add", "bn", "relu", "pad", "copy",
                   "dwconv", "avgpool", "concat", "act", "binary", "affine", "stem_f32", "gconv", "layernorm",
-                  "deconv", "upsample", "crop", "attention", "posembed", "winattn", "space_to_depth")
+                  "deconv", "upsample", "crop", "attention", "posembed", "winattn", "space_to_depth", "groupnorm")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], batch: int, device="cuda",
                  outputs: Optional[Sequence[str]] = None, tune: bool = False, num_sets: int = 1,
@@ -239,7 +239,7 @@ class SliceExecutor:
                 s = gm / np.sqrt(var + eps)
                 self.packed[i] = (torch.tensor(s, dtype=torch.float32, device=dev),
                                   torch.tensor(bt - mu * s, dtype=torch.float32, device=dev))
-            elif st.kind == "layernorm":
+            elif st.kind in ("layernorm", "groupnorm"):
                 self.packed[i] = self._pack_layernorm(weights, st, self.shape_of(st.out)[-1])
             elif st.kind == "posembed":
                 self.packed[i] = self._pack_posembed(weights, st)
@@ -289,7 +289,7 @@ class SliceExecutor:
                 sc = gm / np.sqrt(var + eps)
                 self.packed[i] = (torch.tensor(sc, dtype=torch.float32, device=dev),
                                   torch.tensor(bt - mu * sc, dtype=torch.float32, device=dev))
-            elif st.kind == "layernorm":
+            elif st.kind in ("layernorm", "groupnorm"):
                 self.packed[i] = self._pack_layernorm(weights, st, self.shape_of(st.out)[-1])
             elif st.kind == "posembed":
                 self.packed[i] = self._pack_posembed(weights, st)
@@ -351,7 +351,7 @@ class SliceExecutor:
                               stream=stream)
 
     def _pack_layernorm(self, weights: Dict[str, np.ndarray], st: Step, cp: int):
-        """(gamma, beta) fp32 [cp] of a layernorm step, with Keras' defaults for scale=False / center=False;
+        """(gamma, beta) fp32 [cp] of a layernorm / groupnorm step, with Keras' defaults for scale=False / center=False;
         the bf16 layout's padding channels get gamma = beta = 0, which makes them come out as zeros."""
         name = st.p["layer"]
         c = self.g.layers[name].out_shape[-1]
@@ -399,7 +399,7 @@ class SliceExecutor:
             self._bound = self.num_sets - 1        # the live attributes are the last set's
             self._bind(0)
 
-    _PRIVATE = ("internal", "_arena", "_logits", "_dense_part", "_gap_part", "_ws", "_ctr", "_ws_side", "_ctr_side")
+    _PRIVATE = ("internal", "_arena", "_logits", "_dense_part", "_gap_part", "_gn_ws", "_ws", "_ctr", "_ws_side", "_ctr_side")
 
     def _private_state(self) -> Dict[str, object]:
         return {k: getattr(self, k) for k in self._PRIVATE}
@@ -476,6 +476,17 @@ class SliceExecutor:
                     need = E.gap_scratch_elems(shp[0], shp[1] * shp[2], shp[3])
                     if need:
                         self._gap_part[i] = torch.empty(need, dtype=torch.float32, device=dev)
+        # GroupNormalization partials (csrc/kernels/groupnorm.hip): one workspace, sized for the largest step, as
+        # the steps run one after the other; allocated here, once, so the launches stay graph-capturable
+        self._gn_ws: Optional[torch.Tensor] = None
+        need = 0
+        for st in self.steps:
+            if st.kind == "groupnorm" and self.device.type == "cuda":
+                shp = self.shape_of(st.ins[0])
+                need = max(need, E.groupnorm_workspace(shp[0], shp[1] * shp[2], self.g.layers[st.p["layer"]].out_shape[-1],
+                                                       st.p["groups"], not self.fp32))
+        if need:
+            self._gn_ws = torch.empty(need, dtype=torch.float32, device=dev)
         self._ws: Optional[torch.Tensor] = None
         self._ctr: Optional[torch.Tensor] = None
         self._ws_side: Optional[torch.Tensor] = None
@@ -819,6 +830,10 @@ class SliceExecutor:
                 gm, bt = self.packed[i]
                 E.layernorm(b[st.ins[0]], gm, bt, b[st.out], self.g.layers[st.p["layer"]].out_shape[-1], st.p["eps"],
                             stream=stream)
+            elif k == "groupnorm":
+                gm, bt = self.packed[i]
+                E.groupnorm(b[st.ins[0]], gm, bt, b[st.out], self.g.layers[st.p["layer"]].out_shape[-1],
+                            st.p["groups"], st.p["eps"], act=st.p["act"], workspace=self._gn_ws, stream=stream)
             elif k in ("attention", "posembed", "winattn", "space_to_depth"):
                 self._launch_tokens(i, st, b, stream)
             elif k == "act":
@@ -949,6 +964,10 @@ class SliceExecutor:
         elif k == "layernorm":
             gm, bt = self.packed[i]
             E.layernorm_f32(b[st.ins[0]], gm, bt, b[st.out], st.p["eps"], stream=stream)
+        elif k == "groupnorm":
+            gm, bt = self.packed[i]
+            E.groupnorm_f32(b[st.ins[0]], gm, bt, b[st.out], st.p["groups"], st.p["eps"], act=st.p["act"],
+                            workspace=self._gn_ws, stream=stream)
         elif k in ("attention", "posembed", "winattn", "space_to_depth"):
             self._launch_tokens(i, st, b, stream)
         elif k == "deconv":

@@ -17,6 +17,9 @@ kernels:
 * ``dwconv``   DepthwiseConv2D, or Conv2D(groups=C) with one channel per group,
                [+BN folded] [+ReLU/ReLU6], explicit pads
 * ``layernorm`` LayerNormalization over the last axis; nothing fuses into it
+* ``groupnorm`` GroupNormalization over (H, W, C / G) per image; an activation directly after it (an
+               ``act`` or ``relu`` layer of ``ACT_MODE``, its sole consumer, not exposed by a cut or an
+               output) folds into the step as `act`, the ``binary`` step's rule: GN + swish is one launch
 * ``attention`` the core of a MultiHeadAttention layer `n`, softmax(Q K^T) V per head.  The layer
                compiles to three steps: a ``conv`` (1x1, the Dense path) `n#qkv` whose weights are the
                three projections side by side, [Q | K | V] with 1/sqrt(key_dim) folded into Q; this
@@ -397,6 +400,19 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
             steps.append(Step("layernorm", n, [R(L.inputs[0])], [n],
                               {"layer": n, "eps": float(a.get("epsilon", 1e-3))}))
             done.add(n)
+        elif L.op == "groupnorm":
+            cover = [n]
+            out = n
+            mode = 0
+            c = single(n)
+            if act_mode(c):
+                mode = act_mode(c)
+                cover.append(c)
+                out = c
+            steps.append(Step("groupnorm", out, [R(L.inputs[0])], cover,
+                              {"layer": n, "groups": int(a["groups"]), "eps": float(a.get("epsilon", 1e-3)),
+                               "act": mode}))
+            done.update(cover)
         elif L.op in ("mha", "winattn"):
             h, d = int(a["num_heads"]), int(a["key_dim"])
             dv = int(a.get("value_dim") or d)

@@ -634,6 +634,43 @@ void layernorm(const Arr<float>& x, const Arr<float>& gamma, const Arr<float>& b
   }
 }
 
+// Keras GroupNormalization on an NHWC map: per (image, group) the mean and the biased variance over (H, W, C / G)
+// from the centred values (two passes in double, never E[x^2] - mu^2), then
+// y = act((x - mu) * rsqrt(var + eps) * gamma[c] + beta[c])
+void groupnorm(const Arr<float>& x, const Arr<float>& gamma, const Arr<float>& beta, Arr<float>& y, int groups,
+               float eps, int act, float alpha) {
+  need(x.ndim() == 4 && y.ndim() == 4, "groupnorm ranks");
+  const int N = x.shape(0), C = x.shape(3);
+  const long P = (long)x.shape(1) * x.shape(2);
+  need(N >= 1 && P >= 1 && C >= 1 && groups >= 1 && C % groups == 0, "groupnorm groups");
+  need(y.shape(0) == N && y.shape(1) == x.shape(1) && y.shape(2) == x.shape(2) && y.shape(3) == C &&
+           gamma.size() == C && beta.size() == C, "groupnorm shapes");
+  const int Cg = C / groups;
+  const float *xp = cptr(x), *gp = cptr(gamma), *bp = cptr(beta);
+  float* yp = mptr(y);
+  py::gil_scoped_release nogil;
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int n = 0; n < N; ++n)
+    for (int g = 0; g < groups; ++g) {
+      const float* xb = xp + (long)n * P * C + (long)g * Cg;
+      float* yb = yp + (long)n * P * C + (long)g * Cg;
+      double s = 0.0;
+      for (long p = 0; p < P; ++p)
+        for (int c = 0; c < Cg; ++c) s += xb[p * C + c];
+      const double mu = s / ((double)P * Cg);
+      double q = 0.0;
+      for (long p = 0; p < P; ++p)
+        for (int c = 0; c < Cg; ++c) {
+          const double d = xb[p * C + c] - mu;
+          q += d * d;
+        }
+      const double rstd = 1.0 / std::sqrt(q / ((double)P * Cg) + (double)eps);
+      for (long p = 0; p < P; ++p)
+        for (int c = 0; c < Cg; ++c)
+          yb[p * C + c] = act_f((float)((xb[p * C + c] - mu) * rstd) * gp[g * Cg + c] + bp[g * Cg + c], act, alpha);
+    }
+}
+
 // y = act(x)
 void activation(const Arr<float>& x, Arr<float>& y, int act, float alpha) {
   need(y.size() == x.size(), "act shapes");
@@ -762,6 +799,8 @@ PYBIND11_MODULE(_cpu, m) {
         py::arg("H"), py::arg("W"), py::arg("window"), py::arg("shift"), py::arg("heads"), py::arg("key_dim"));
   m.def("space_to_depth", &space_to_depth, py::arg("x"), py::arg("y"));
   m.def("layernorm", &layernorm, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("y"), py::arg("eps"));
+  m.def("groupnorm", &groupnorm, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("y"), py::arg("groups"),
+        py::arg("eps"), py::arg("act") = 0, py::arg("alpha") = 0.3f);
   m.def("activation", &activation, py::arg("x"), py::arg("y"), py::arg("act"), py::arg("alpha") = 0.3f);
   m.def("binary", &binary, py::arg("a"), py::arg("b"), py::arg("y"), py::arg("op"), py::arg("act") = 0,
         py::arg("alpha") = 0.3f);

@@ -395,6 +395,19 @@ PYBIND11_MODULE(_C, m) {
                            eps, S(s)), "layernorm");
   });
   m.def("layernorm_lanes", &adapt::layernorm_lanes);
+  m.def("groupnorm_f32", [](u64 x, u64 gamma, u64 beta, u64 y, u64 ws, u64 ws_floats, int B, int Px, int C, int G,
+                            float eps, int act, float alpha, u64 s) {
+    check(adapt::groupnorm_f32(P<const float>(x), P<const float>(gamma), P<const float>(beta), P<float>(y),
+                               P<float>(ws), (size_t)ws_floats, B, Px, C, G, eps, act, alpha, S(s)), "groupnorm_f32");
+  });
+  m.def("groupnorm", [](u64 x, u64 gamma, u64 beta, u64 y, u64 ws, u64 ws_floats, int B, int Px, int Cp, int C, int G,
+                        float eps, int act, float alpha, u64 s) {
+    check(adapt::groupnorm(P<const bf16>(x), P<const float>(gamma), P<const float>(beta), P<bf16>(y), P<float>(ws),
+                           (size_t)ws_floats, B, Px, Cp, C, G, eps, act, alpha, S(s)), "groupnorm");
+  });
+  m.def("groupnorm_path", &adapt::groupnorm_path);
+  m.def("groupnorm_slabs", &adapt::groupnorm_slabs);
+  m.def("groupnorm_workspace_floats", &adapt::groupnorm_workspace_floats);
   m.def("deconv_f32_mfma_ok", &adapt::deconv_f32_mfma_ok);
   m.def("deconv_f32_forward", [](u64 x, u64 w, u64 b, u64 y, int B, int H, int W, int Cin, int OH, int OW, int Cout,
                                  int KH, int KW, int Sd, int pt, int pl, int act, bool mfma, u64 s) {

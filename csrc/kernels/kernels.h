@@ -232,6 +232,18 @@ hipError_t layernorm_f32(const float* x, const float* gamma, const float* beta, 
 hipError_t layernorm(const bf16* x, const float* gamma, const float* beta, bf16* y, int rows, int Cp, int C, float eps,
                      hipStream_t s);
 int layernorm_lanes(int nvec);   // lanes per row for `nvec` 16-byte vectors per row; 0 = the looped path
+// GroupNormalization on an NHWC map (groupnorm.hip): x / y [B][P][C] fp32, or [B][P][Cp] bf16 with channels C..Cp-1
+// layout padding (kept out of the statistics, written as zeros; gamma / beta then hold Cp floats).  G groups of
+// C / G channels, then the activation `act` (common.h ActMode).  `ws`: groupnorm_workspace_floats() floats, owned
+// by the caller (may be null where that is 0).  x, y, gamma, beta 16-byte aligned on the vector paths.
+hipError_t groupnorm_f32(const float* x, const float* gamma, const float* beta, float* y, float* ws, size_t ws_floats,
+                         int B, int P, int C, int G, float eps, int act, float alpha, hipStream_t s);
+hipError_t groupnorm(const bf16* x, const float* gamma, const float* beta, bf16* y, float* ws, size_t ws_floats, int B,
+                     int P, int Cp, int C, int G, float eps, int act, float alpha, hipStream_t s);
+// the path a shape takes (Cs: stored channels): 0 scalar split, 1 vector split, 2 vector single launch, -1 refused
+int groupnorm_path(int B, int P, int C, int Cs, int G, bool bf16_act);
+int groupnorm_slabs(int B, int P, int C, int Cs, int G, bool bf16_act);      // slabs per image of the statistics launch
+size_t groupnorm_workspace_floats(int B, int P, int C, int Cs, int G, bool bf16_act);
 hipError_t avgpool_f32(const float* x, float* y, int B, int H, int W, int C, int OH, int OW, int KH, int KW, int S,
                        int pad_t, int pad_l, hipStream_t s);
 hipError_t concat_f32(const float* x, int Cx, float* y, int Cy, int off, size_t pixels, hipStream_t s);

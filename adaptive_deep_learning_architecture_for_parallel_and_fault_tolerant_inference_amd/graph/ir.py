@@ -50,12 +50,17 @@ OPS = (
                   # activation; kernel (kh, kw, filters, cin) (Keras HWOI), no output_padding, no dilation
     "upsample",   # Keras UpSampling2D: size=(sh,sw), interpolation ('nearest' | 'bilinear', half-pixel centres)
     "crop",       # Keras Cropping2D: crop=((t,b),(l,r))
-    "mha",        # Keras MultiHeadAttention as self-attention over all positions: num_heads, key_dim, value_dim
-                  # (absent means key_dim), use_bias; input (H, W, C) or (T, C), output the same shape
+    "mha",        # Keras MultiHeadAttention over all positions: num_heads, key_dim, value_dim (absent means key_dim),
+                  # use_bias; inputs [query], [query, value] or [query, value, key] in Keras argument order (one input
+                  # is self-attention, a missing key means key = value), each (H, W, C) or (T, C); value and key have
+                  # the same token count, their channel counts are their own; output the query's shape
     "posembed",   # ViT class token + learned position embedding: attrs class_token; (H, W, C) -> (1, T + ct, C)
     "winattn",    # Swin window attention (the project's own layer, Keras class WindowAttention): num_heads, key_dim,
                   # window (M), shift (0 <= s < M), use_bias; (H, W, C) -> (H, W, C), H and W multiples of M.
                   # Weights as `mha` plus relative_position_bias_table ((2M-1)^2, heads)
+    "queries",    # a learned constant tensor (the project's own layer, Keras class LearnedQueries): attrs length N,
+                  # dim C, initializer ("normal" | "zeros"); weight embeddings (N, C); the one input supplies only the
+                  # batch size; output (1, N, C), the same for every image
     "space_to_depth",  # Swin patch merging's rearrangement (Keras class SpaceToDepth): attrs block (2);
                   # (H, W, C) -> (H/2, W/2, 4C), out[y, x, (2 dx + dy) C + c] = in[2y + dy, 2x + dx, c]: the
                   # concatenation of x[0::2,0::2], x[1::2,0::2], x[0::2,1::2], x[1::2,1::2] (not tf.nn.space_to_depth,
@@ -108,23 +113,38 @@ def conv_bias(weights, p: Dict):
     return weights.get(f"{p['conv']}/bias")
 
 
+MHA_PARTS = {"q": ("query",), "k": ("key",), "v": ("value",), "qk": ("query", "key"), "kv": ("key", "value"),
+             "qkv": ("query", "key", "value")}
+
+
+def mha_sources(inputs: Sequence[str]) -> Tuple[str, str, str]:
+    """(query, key, value) source tensors of an `mha` layer's inputs ([query], [query, value] or
+    [query, value, key], Keras argument order; a missing key means key = value)."""
+    q = inputs[0]
+    v = inputs[1] if len(inputs) > 1 else q
+    k = inputs[2] if len(inputs) > 2 else v
+    return q, k, v
+
+
 def mha_projection(weights, name: str, head: Dict, part: str):
-    """(kernel, bias or None) of the two GEMMs around the attention core of MultiHeadAttention layer `name`;
-    `head` holds heads, key_dim, value_dim.  part "qkv": the query / key / value projections side by side,
-    (C, h * (2 d + dv)) ordered [Q | K | V] and head-major inside each, with Keras' 1/sqrt(key_dim) query scale
-    folded into the Q columns and the Q bias.  part "out": the output projection (h * dv, C)."""
+    """(kernel, bias or None) of the GEMMs around the attention core of MultiHeadAttention layer `name`;
+    `head` holds heads, key_dim, value_dim.  The input projections that share a source tensor stand side by side
+    in one GEMM: part "qkv" is (C, h * (2 d + dv)) ordered [Q | K | V], "qk" [Q | K], "kv" [K | V], and "q", "k",
+    "v" one projection each (MHA_PARTS), head-major inside each projection, with Keras' 1/sqrt(key_dim) query
+    scale folded into the Q columns and the Q bias.  part "out": the output projection (h * dv, C)."""
     import numpy as np
     h, d, dv = head["heads"], head["key_dim"], head["value_dim"]
     if part == "out":
         return (weights[f"{name}/attention_output/kernel"].reshape(h * dv, -1),
                 weights.get(f"{name}/attention_output/bias"))
     scale = {"query": 1.0 / np.sqrt(np.float64(d)), "key": 1.0, "value": 1.0}
-    ks = [(weights[f"{name}/{q}/kernel"].astype(np.float64) * scale[q]).reshape(-1, h * w)
-          for q, w in (("query", d), ("key", d), ("value", dv))]
+    width = {"query": d, "key": d, "value": dv}
+    ks = [(weights[f"{name}/{q}/kernel"].astype(np.float64) * scale[q]).reshape(-1, h * width[q])
+          for q in MHA_PARTS[part]]
     kernel = np.concatenate(ks, axis=1).astype(np.float32)
     if f"{name}/query/bias" not in weights:
         return kernel, None
-    bs = [(weights[f"{name}/{q}/bias"].astype(np.float64) * scale[q]).reshape(-1) for q in ("query", "key", "value")]
+    bs = [(weights[f"{name}/{q}/bias"].astype(np.float64) * scale[q]).reshape(-1) for q in MHA_PARTS[part]]
     return kernel, np.concatenate(bs).astype(np.float32)
 
 
@@ -220,9 +240,10 @@ class Layer:
         if self.op == "mha":
             c, h, d = in_shapes[0][-1], self.attrs["num_heads"], self.attrs["key_dim"]
             dv = self.attrs.get("value_dim") or d
+            _, ck, cv = (s[-1] for s in mha_sources(in_shapes))      # each projection follows its own source
             out = []
-            for part, shp, bshp in (("query", (c, h, d), (h, d)), ("key", (c, h, d), (h, d)),
-                                    ("value", (c, h, dv), (h, dv)), ("attention_output", (h, dv, c), (c,))):
+            for part, shp, bshp in (("query", (c, h, d), (h, d)), ("key", (ck, h, d), (h, d)),
+                                    ("value", (cv, h, dv), (h, dv)), ("attention_output", (h, dv, c), (c,))):
                 out.append((f"{self.name}/{part}/kernel", shp))
                 if self.attrs.get("use_bias", True):
                     out.append((f"{self.name}/{part}/bias", bshp))
@@ -236,6 +257,8 @@ class Layer:
                 if self.attrs.get("use_bias", True):
                     out.append((f"{self.name}/{part}/bias", bshp))
             return out + [(f"{self.name}/relative_position_bias_table", ((2 * m - 1) ** 2, h))]
+        if self.op == "queries":
+            return [(f"{self.name}/embeddings", (int(self.attrs["length"]), int(self.attrs["dim"])))]
         if self.op == "posembed":
             t, c = _tokens(in_shapes[0]), in_shapes[0][-1]
             ct = 1 if self.attrs.get("class_token") else 0
@@ -272,7 +295,10 @@ class Layer:
             t, c = _tokens(in_shapes[0]), in_shapes[0][-1]
             h, d = self.attrs["num_heads"], self.attrs["key_dim"]
             dv = self.attrs.get("value_dim") or d
-            return t * c * h * (2 * d + dv) + t * t * h * (d + dv) + t * h * dv * c
+            _, sk, sv = mha_sources(in_shapes)
+            tk = _tokens(sk)
+            return (t * c * h * d + tk * sk[-1] * h * d + tk * sv[-1] * h * dv + t * tk * h * (d + dv)
+                    + t * h * dv * c)
         if self.op == "winattn":                # projections (h d = C in Swin), scores and P V inside M x M windows
             (hh, ww, c), m = in_shapes[0], self.attrs["window"]
             hd = self.attrs["num_heads"] * self.attrs["key_dim"]
@@ -347,12 +373,31 @@ class Graph:
                 raise ValueError(f"upsample {layer.name!r}: size must be two positive ints and interpolation "
                                  f"'nearest' or 'bilinear' (got {sz}, {layer.attrs.get('interpolation')!r})")
         if layer.op == "mha":
-            rank = len(self.layers[layer.inputs[0]].out_shape)
-            if (len(layer.inputs) != 1 or rank not in (2, 3) or int(layer.attrs.get("num_heads", 0)) < 1
-                    or int(layer.attrs.get("key_dim", 0)) < 1 or int(layer.attrs.get("value_dim") or 1) < 1):
-                raise ValueError(f"mha {layer.name!r}: needs one input of rank 2 or 3 (got rank {rank}), "
-                                 f"num_heads >= 1 and key_dim >= 1 (got {layer.attrs.get('num_heads')}, "
+            shapes = [self.layers[i].out_shape for i in layer.inputs]
+            rank = len(shapes[0])
+            if (not 1 <= len(layer.inputs) <= 3 or any(len(s) not in (2, 3) for s in shapes)
+                    or int(layer.attrs.get("num_heads", 0)) < 1 or int(layer.attrs.get("key_dim", 0)) < 1
+                    or int(layer.attrs.get("value_dim") or 1) < 1):
+                raise ValueError(f"mha {layer.name!r}: needs one input of rank 2 or 3 (got rank {rank}), or [query, "
+                                 f"value] / [query, value, key] of rank 2 or 3 each (got {shapes}), num_heads >= 1 "
+                                 f"and key_dim >= 1 (got {layer.attrs.get('num_heads')}, "
                                  f"{layer.attrs.get('key_dim')})")
+            _, sk, sv = mha_sources(shapes)
+            if _tokens(sk) != _tokens(sv):
+                raise ValueError(f"mha {layer.name!r}: the key has {_tokens(sk)} tokens and the value "
+                                 f"{_tokens(sv)}; they must agree")
+            osh = layer.attrs.get("output_shape")
+            if osh is not None and [int(v) for v in (osh if isinstance(osh, (list, tuple)) else [osh])] != [
+                    shapes[0][-1]]:
+                raise ValueError(f"mha {layer.name!r}: output_shape={osh} (only the query's {shapes[0][-1]} "
+                                 f"channels)")
+        if layer.op == "queries":
+            a = layer.attrs
+            if (len(layer.inputs) != 1 or int(a.get("length", 0)) < 1 or int(a.get("dim", 0)) < 1
+                    or a.get("initializer", "normal") not in ("normal", "zeros")):
+                raise ValueError(f"queries {layer.name!r}: needs one input (the batch size), length >= 1, dim >= 1 "
+                                 f"and initializer 'normal' or 'zeros' (got {a.get('length')}, {a.get('dim')}, "
+                                 f"{a.get('initializer')!r})")
         if layer.op == "winattn":
             shp = self.layers[layer.inputs[0]].out_shape
             a = layer.attrs
@@ -424,6 +469,8 @@ class Graph:
             return (ins[0][0] // 2, ins[0][1] // 2, 4 * ins[0][2])
         if layer.op == "posembed":
             return (1, _tokens(ins[0]) + (1 if a.get("class_token") else 0), ins[0][-1])
+        if layer.op == "queries":
+            return (1, int(a["length"]), int(a["dim"]))
         if layer.op == "binary":
             return ins[0]
         if layer.op == "reshape":

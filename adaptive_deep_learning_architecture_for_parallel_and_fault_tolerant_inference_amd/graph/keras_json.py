@@ -70,10 +70,12 @@ def _tensor_name(v):
     return None
 
 
-def _mha_input(layer: Dict[str, Any], name: str) -> str:
-    """The one tensor a MultiHeadAttention call attends over.  Keras 2 keeps `value` / `key` in the first
-    inbound entry's kwargs, Keras 3 in the node's "kwargs" (or all of them in "args"); the call must be plain
-    self-attention: query, value and key the same tensor, no mask, no scores returned."""
+def _mha_inputs(layer: Dict[str, Any], name: str, cross_attention: bool) -> List[str]:
+    """The tensors a MultiHeadAttention call attends over, as the `mha` op's inputs: [query] for plain
+    self-attention, [query, value] when the key is the value, else [query, value, key].  Keras 2 keeps `value` /
+    `key` in the first inbound entry's kwargs, Keras 3 in the node's "kwargs" (or all of them in "args"); no mask,
+    no scores returned.  Without `cross_attention` a call whose three tensors are not one is refused by layer
+    name, as it was before the `mha` op took separate sources."""
     nodes = layer.get("inbound_nodes") or []
     if len(nodes) != 1:
         raise NotImplementedError(f"layer {name!r} is called {len(nodes)} times (one call per layer)")
@@ -89,18 +91,20 @@ def _mha_input(layer: Dict[str, Any], name: str) -> str:
     call.update(kwargs)
     q, v = _tensor_name(call.get("query")), _tensor_name(call.get("value"))
     k = _tensor_name(call.get("key")) if call.get("key") is not None else v
-    if q is None or v is None:
+    if q is None or v is None or k is None:
         raise NotImplementedError(f"{name}: MultiHeadAttention call without a query and a value tensor")
-    if not q == v == k:
-        raise NotImplementedError(f"{name}: cross-attention (query {q!r}, value {v!r}, key {k!r}); only "
-                                  f"self-attention over one tensor is supported")
+    if not q == v == k and not cross_attention:
+        raise NotImplementedError(f"{name}: cross-attention (query {q!r}, value {v!r}, key {k!r}); "
+                                  f"from_keras_json(..., cross_attention=True) reads it")
     if call.get("attention_mask") is not None:
         raise NotImplementedError(f"{name}: MultiHeadAttention with an attention_mask")
     if call.get("use_causal_mask"):
         raise NotImplementedError(f"{name}: MultiHeadAttention with use_causal_mask")
     if call.get("return_attention_scores"):
         raise NotImplementedError(f"{name}: MultiHeadAttention with return_attention_scores")
-    return q
+    if q == v == k:
+        return [q]
+    return [q, v] if k == v else [q, v, k]
 
 
 def _check_mha(cfg: Dict[str, Any], in_shape: Tuple[int, ...], name: str) -> None:
@@ -253,7 +257,7 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
                 a[k] = False
         return Layer(name, "groupnorm", inputs, a)
     if cls == "MultiHeadAttention":
-        # the call (self-attention only) and attention_axes / output_shape are checked in from_keras_json
+        # the call (its query / value / key tensors) and attention_axes / output_shape are checked in from_keras_json
         a = {"num_heads": int(cfg["num_heads"]), "key_dim": int(cfg["key_dim"]),
              "use_bias": bool(cfg.get("use_bias", True))}
         if cfg.get("value_dim") is not None and int(cfg["value_dim"]) != a["key_dim"]:
@@ -268,6 +272,9 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
         return Layer(name, "space_to_depth", inputs, {"block": int(cfg.get("block_size", 2))})
     if cls == "ClassTokenPositionEmbedding":           # the project's own layer (graph/ir.py "posembed")
         return Layer(name, "posembed", inputs, {"class_token": bool(cfg.get("class_token", True))})
+    if cls == "LearnedQueries":                        # the project's own layer (graph/ir.py "queries")
+        return Layer(name, "queries", inputs, {"length": int(cfg["length"]), "dim": int(cfg["dim"]),
+                                               "initializer": str(cfg.get("initializer", "normal"))})
     if cls == "LayerScale":
         return Layer(name, "layerscale", inputs, {"init_values": float(cfg.get("init_values", 1e-6))})
     if cls == "StochasticDepth":                       # drops whole residual branches in training only
@@ -344,8 +351,11 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
     raise NotImplementedError(f"layer {name!r}: Keras class {cls!r} is not supported by the runtime")
 
 
-def from_keras_json(s) -> Graph:
-    """Parse ``model.to_json()`` output (str or already-decoded dict) into a Graph."""
+def from_keras_json(s, cross_attention: bool = False) -> Graph:
+    """Parse ``model.to_json()`` output (str or already-decoded dict) into a Graph.  `cross_attention=True` reads a
+    MultiHeadAttention call whose query, value and key are different tensors (the `mha` op's two- and three-input
+    forms); by default such a call is refused by layer name, which is what this function has always done and what
+    callers written against it may rely on.  `Model.from_keras_json`, and through it the command line, pass True."""
     d = json.loads(s) if isinstance(s, (str, bytes)) else s
     if d.get("class_name") not in ("Functional", "Model"):
         raise NotImplementedError(f"only functional models are supported (got {d.get('class_name')!r})")
@@ -354,11 +364,12 @@ def from_keras_json(s) -> Graph:
     for ld in cfg["layers"]:
         name = ld.get("name") or ld["config"]["name"]
         mha = ld["class_name"] == "MultiHeadAttention"
-        inputs = [_mha_input(ld, name)] if mha else _inbound_names(ld)
+        inputs = _mha_inputs(ld, name, cross_attention) if mha else _inbound_names(ld)
         if mha:
-            if inputs[0] not in g.layers:
-                raise ValueError(f"layer {name!r} consumes unknown tensor {inputs[0]!r}")
-            _check_mha(ld["config"], g.layers[inputs[0]].out_shape, name)
+            for i in inputs:
+                if i not in g.layers:
+                    raise ValueError(f"layer {name!r} consumes unknown tensor {i!r}")
+            _check_mha(ld["config"], g.layers[inputs[0]].out_shape, name)      # against the query
         for layer in _layers_from_keras(ld["class_name"], ld["config"], name, inputs):
             g.add(layer)
         if ld["class_name"] == "LayerNormalization":
@@ -431,6 +442,9 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
     elif L.op == "posembed":
         cls = "ClassTokenPositionEmbedding"
         cfg.update(class_token=bool(a.get("class_token")))
+    elif L.op == "queries":
+        cls = "LearnedQueries"
+        cfg.update(length=a["length"], dim=a["dim"], initializer=a.get("initializer", "normal"))
     elif L.op == "layerscale":
         cls = "LayerScale"
         cfg.update(init_values=a.get("init_values", 1e-6), projection_dim=L.out_shape[-1])
@@ -486,8 +500,11 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
     else:
         raise NotImplementedError(L.op)
     inbound = [[[i, 0, 0, {}] for i in L.inputs]] if L.inputs else []
-    if L.op == "mha":                                   # Keras 2: mha(x, x) keeps `value` in the entry's kwargs
-        inbound = [[[L.inputs[0], 0, 0, {"value": [L.inputs[0], 0, 0]}]]]
+    if L.op == "mha":           # Keras 2: mha(q, v[, key=k]) keeps `value` (and `key`) in the entry's kwargs
+        kw = {"value": [L.inputs[1] if len(L.inputs) > 1 else L.inputs[0], 0, 0]}
+        if len(L.inputs) > 2:
+            kw["key"] = [L.inputs[2], 0, 0]
+        inbound = [[[L.inputs[0], 0, 0, kw]]]
     return {"class_name": cls, "config": cfg, "name": L.name, "inbound_nodes": inbound}
 
 

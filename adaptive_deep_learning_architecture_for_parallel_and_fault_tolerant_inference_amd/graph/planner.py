@@ -134,6 +134,19 @@ def layer_costs(g: Graph, batch: int = 32, hw: Optional[HwModel] = None) -> Dict
             # the map twice and writes it once, three launches.  Uncalibrated: no planner fit includes a GN model
             out[n] = 1.5 * byts / hw.hbm_bw + 3 * hw.launch_s
             continue
+        if L.op == "queries":
+            # a broadcast copy of the (N, C) weight: the output's bytes, the input only supplies the batch size.
+            # Uncalibrated: no planner fit includes a model with learned queries
+            out[n] = g.tensor_bytes(n, hw.act_bytes) * batch / hw.hbm_bw + hw.launch_s
+            continue
+        if L.op == "mha" and len(L.inputs) > 1:
+            # separate sources: the MACs of graph/ir.py (each projection over its own source's tokens, the
+            # Tq x Tk core, the output projection) and one launch per projection GEMM, the core and the output
+            # projection.  Uncalibrated, like `queries`; the core's grid is B x heads x ceil(Tq / 64) blocks,
+            # which at few queries and a small batch leaves most CUs idle, and this roofline does not see that
+            launches = len(set(L.inputs)) + 2
+            out[n] = max(2.0 * macs / hw.mfma_flops, byts / hw.hbm_bw) + launches * hw.launch_s
+            continue
         # deconv: its true MACs (input pixels x taps x cin x filters, the phase form multiplies no stuffed
         # zeros) against its bytes; upsample / crop have no MACs and cost their input + output traffic.
         # mha: the MACs of its two projection GEMMs and the T x T core (graph/ir.py); posembed: its traffic.

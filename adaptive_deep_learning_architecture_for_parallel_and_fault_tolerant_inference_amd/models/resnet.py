@@ -160,6 +160,10 @@ def init_weights(g: Graph, seed: int = 0, layers: Optional[List[str]] = None) ->
         elif L.op == "posembed":
             for wname, shp in specs:               # class token and position embedding: N(0, 0.02)
                 out[wname] = (rng.standard_normal(shp) * 0.02).astype(np.float32)
+        elif L.op == "queries":                    # N(0, 1) (an embedding table's default), or the zeros asked for
+            shp = specs[0][1]
+            out[specs[0][0]] = (np.zeros(shp, np.float32) if L.attrs.get("initializer", "normal") == "zeros"
+                                else rng.standard_normal(shp).astype(np.float32))
         elif L.op == "layerscale":
             # O(1), not Keras' 1e-6: with that every residual branch would vanish from the output
             out[specs[0][0]] = rng.uniform(0.1, 0.3, specs[0][1][0]).astype(np.float32)

@@ -34,6 +34,10 @@ Not from `keras.applications` (models whose output is a map, not a class vector)
   residual blocks, one-head MultiHeadAttention on the (H, W, C) map, nearest UpSampling2D; a 64 x 64 x 4 latent
   to a 512 x 512 x 3 image, 49,490,199 parameters (the published decoder's 49,490,179 and the 20 of the 1x1
   post-quantisation conv in front of it).
+* DETR (`detr_resnet50`, test size `detr_micro`): the ResNet-50 backbone, a post-norm transformer encoder and
+  decoder whose MultiHeadAttention layers take separate query / key / value tensors, LearnedQueries for the object
+  queries and the position table; a 480 x 640 x 3 image to (1, 100, 96) class logits and boxes, 41,759,968
+  parameters (Keras counting: BatchNormalization statistics, conv biases and the two tables included).
 """
 from __future__ import annotations
 
@@ -632,7 +636,97 @@ def build_swin(name: str = "swin_tiny", classes: int = 1000, input_shape=None) -
     return g
 
 
+# -------------------------------------------------------------------- DETR
+# name -> (backbone, width, heads, queries, encoder layers, decoder layers, FFN width, default input); micro: same
+# naming / structure behind a three-conv backbone, for fast tests
+DETR = {
+    "detr_resnet50": ("resnet50", 256, 8, 100, 6, 6, 2048, (480, 640, 3)),
+    "detr_micro": ((8, 16, 32), 32, 2, 10, 2, 2, 64, (40, 56, 3)),
+}
+DETR_EPS = 1e-5
+DETR_CLASSES = 92          # 91 COCO category ids + "no object"
+
+
+def build_detr(name: str = "detr_resnet50", classes: int = DETR_CLASSES, input_shape=None) -> Graph:
+    """DETR (Carion et al. 2020) as published, post-norm, as a flat graph.  The ResNet-50 layers of `build_resnet`
+    through `conv5_block3_out` under their Keras names, a 1x1 `input_proj` to the model width, and the map as
+    (1, T, C) tokens.  One position table `pos` (T, C), a LearnedQueries (the published sine values load into it as
+    weights).  Encoder layer: MultiHeadAttention(q = k = src + pos, v = src) -> Add -> LayerNormalization ->
+    Dense(ffn, relu) -> Dense -> Add -> LayerNormalization.  Decoder layer on `tgt` (a zeros LearnedQueries) with
+    `query_embed`: self-attention (q = k = tgt + query_embed, v = tgt), cross-attention (q = tgt + query_embed,
+    k = memory + pos, v = memory) and the FFN, each followed by Add and LayerNormalization.  A final
+    LayerNormalization, the class head Dense(92), the box head Dense(relu), Dense(relu), Dense(4, sigmoid), and the
+    Concatenate of both into one (1, queries, 96) output.  The learned tensors hang off the tensor next to them
+    (`pos` off the projected map, `tgt` and `query_embed` off memory + pos), which only gives them the batch size: a
+    cut never drags the image along, and one inside the decoder ships the running target, the memory, memory + pos
+    and the query embedding."""
+    from .resnet import BN_EPS, STACKS, _stack1
+    backbone, width, heads, nq, enc, dec, ffn, default_shape = DETR[name]
+    shape = tuple(input_shape or default_shape)
+    g = Graph(name)
+    x = g.add(Layer("input_1", "input", [], {"shape": shape}))
+    if isinstance(backbone, str):
+        x = g.add(Layer("conv1_pad", "zeropad", [x], {"pad": ((3, 3), (3, 3))}))
+        x = _conv(g, x, "conv1_conv", 64, 7, stride=2)
+        x = g.add(Layer("conv1_bn", "bn", [x], {"epsilon": BN_EPS}))
+        x = g.add(Layer("conv1_relu", "relu", [x]))
+        x = g.add(Layer("pool1_pad", "zeropad", [x], {"pad": ((1, 1), (1, 1))}))
+        x = g.add(Layer("pool1_pool", "maxpool", [x], {"pool": 3, "stride": 2, "padding": "valid"}))
+        for s, (filters, blocks) in enumerate(zip((64, 128, 256, 512), STACKS[backbone])):
+            x = _stack1(g, x, filters, blocks, 1 if s == 0 else 2, f"conv{s + 2}")
+    else:
+        for i, f in enumerate(backbone):
+            x = _conv(g, x, f"backbone_conv{i + 1}", f, 3, stride=2, padding="same", activation="relu")
+    x = _conv(g, x, "input_proj", width, 1)
+    h, w, _ = g.layers[x].out_shape
+    tokens = h * w
+    src = g.add(Layer("src", "reshape", [x], {"shape": (1, tokens, width)}))
+    pos = g.add(Layer("pos", "queries", [src], {"length": tokens, "dim": width, "initializer": "normal"}))
+
+    def add(a: str, b: str, nm: str) -> str:
+        return g.add(Layer(nm, "add", [a, b]))
+
+    def ln(x: str, nm: str) -> str:
+        return g.add(Layer(nm, "layernorm", [x], {"epsilon": DETR_EPS}))
+
+    def mha(q: str, v: str, k: str, nm: str) -> str:
+        return g.add(Layer(nm, "mha", [q, v, k], {"num_heads": heads, "key_dim": width // heads, "use_bias": True}))
+
+    def ffn_block(x: str, nm: str) -> str:
+        y = g.add(Layer(f"{nm}_ffn_fc1", "dense", [x], {"units": ffn, "activation": "relu", "use_bias": True}))
+        y = g.add(Layer(f"{nm}_ffn_fc2", "dense", [y], {"units": width, "use_bias": True}))
+        return ln(add(x, y, f"{nm}_add_ffn"), f"{nm}_ln_ffn")
+
+    x = src
+    for i in range(enc):
+        nm = f"encoder_{i}"
+        qk = add(x, pos, f"{nm}_qk")
+        x = ln(add(x, mha(qk, x, qk, f"{nm}_attn"), f"{nm}_add_attn"), f"{nm}_ln_attn")
+        x = ffn_block(x, nm)
+    memory = x
+    memory_pos = add(memory, pos, "memory_pos")
+    query_embed = g.add(Layer("query_embed", "queries", [memory_pos], {"length": nq, "dim": width,
+                                                                 "initializer": "normal"}))
+    x = g.add(Layer("tgt", "queries", [memory_pos], {"length": nq, "dim": width, "initializer": "zeros"}))
+    for i in range(dec):
+        nm = f"decoder_{i}"
+        qk = add(x, query_embed, f"{nm}_self_qk")
+        x = ln(add(x, mha(qk, x, qk, f"{nm}_self_attn"), f"{nm}_add_self"), f"{nm}_ln_self")
+        q = add(x, query_embed, f"{nm}_cross_q")
+        x = ln(add(x, mha(q, memory, memory_pos, f"{nm}_cross_attn"), f"{nm}_add_cross"), f"{nm}_ln_cross")
+        x = ffn_block(x, nm)
+    x = ln(x, "decoder_ln")
+    logits = g.add(Layer("class_head", "dense", [x], {"units": classes, "use_bias": True}))
+    y = g.add(Layer("box_head_fc1", "dense", [x], {"units": width, "activation": "relu", "use_bias": True}))
+    y = g.add(Layer("box_head_fc2", "dense", [y], {"units": width, "activation": "relu", "use_bias": True}))
+    boxes = g.add(Layer("box_head_fc3", "dense", [y], {"units": 4, "activation": "sigmoid", "use_bias": True}))
+    g.add(Layer("detections", "concat", [logits, boxes]))
+    g.output_names = ["detections"]
+    return g
+
+
 BUILDERS: Dict[str, Callable[..., Graph]] = {
+    **{n: (lambda n: lambda **kw: build_detr(n, **kw))(n) for n in DETR},
     **{n: (lambda n: lambda **kw: build_swin(n, **kw))(n) for n in SWIN},
     **{n: (lambda n: lambda **kw: build_vit(n, **kw))(n) for n in VIT},
     **{n: (lambda n: lambda **kw: build_vae_decoder(n, **kw))(n) for n in VAE_DECODER},

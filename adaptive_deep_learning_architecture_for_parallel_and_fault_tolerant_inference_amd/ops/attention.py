@@ -1,5 +1,6 @@
-"""Wrappers for the self-attention core (csrc/kernels/attention.hip), Swin's window attention core and its bias
-packer (csrc/kernels/window_attention.hip) and the ViT class token / position embedding kernel
+"""Wrappers for the self-attention core (csrc/kernels/attention.hip), the attention core with separate query /
+key / value sources (csrc/kernels/cross_attention.hip), Swin's window attention core and its bias packer
+(csrc/kernels/window_attention.hip), and the ViT class token / position embedding and learned-queries kernels
 (csrc/kernels/layers.hip).
 
 Shapes, dtypes, strides and the 32-bit index range are checked here before any launch; a shape the kernels do
@@ -49,6 +50,95 @@ def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, tokens: int, hea
         raise ValueError("attention: tensors must hold fewer than 2^31 elements (32-bit index math)")
     fn = kernels().attention_f32 if qkv.dtype == torch.float32 else kernels().attention_bf16
     fn(ptr(qkv), ptr(out), B, T, h, d, dv, int(ld_in), int(ld_out), stream_handle(stream))
+    return out
+
+
+def cross_attention_tiles():
+    """(queries per block, keys per LDS tile) of the cross-attention kernel's MFMA path."""
+    k = kernels()
+    return int(k.cross_attention_query_tile()), int(k.cross_attention_key_tile())
+
+
+def _rows_view(t: torch.Tensor, dtype, name: str):
+    """(row stride, width) of a tensor view whose rows are its last dimension: contiguous, or a column slice of a
+    contiguous buffer (every leading stride then follows from the row stride)."""
+    if t.dtype != dtype:
+        raise ValueError(f"cross_attention: {name}: expected {dtype}, got {t.dtype}")
+    if not t.is_cuda:
+        raise ValueError(f"cross_attention: {name}: must be a device tensor")
+    if t.dim() < 2 or t.numel() == 0 or t.stride(-1) != 1:
+        raise ValueError(f"cross_attention: {name}{tuple(t.shape)}: rows must be the last dimension, unit stride")
+    ld = t.stride(-2)
+    want = ld
+    for i in range(t.dim() - 2, -1, -1):
+        if t.shape[i] != 1 and t.stride(i) != want:
+            raise ValueError(f"cross_attention: {name}{tuple(t.shape)} strides {t.stride()}: not rows of one stride")
+        want *= t.shape[i]
+    if ld < t.shape[-1]:
+        raise ValueError(f"cross_attention: {name}: row stride {ld} below the width {t.shape[-1]}")
+    return int(ld), int(t.shape[-1])
+
+
+def cross_attention_path(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, key_dim: int,
+                         value_dim: Optional[int] = None) -> str:
+    """'mfma' or 'plain' for these views: the MFMA path needs head sizes that are multiples of 16 up to 128, the four
+    addresses aligned to 4 elements and row strides that are multiples of 4."""
+    d, dv = int(key_dim), int(value_dim or key_dim)
+    lds = [t.stride(-2) if t.dim() >= 2 else t.shape[-1] for t in (q, k, v, out)]
+    return "mfma" if kernels().cross_attention_path(ptr(q), ptr(k), ptr(v), ptr(out), d, dv, *(int(x) for x in lds),
+                                                    q.element_size()) else "plain"
+
+
+def cross_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, batch: int, tokens_q: int,
+                    tokens_k: int, heads: int, key_dim: int, value_dim: Optional[int] = None, stream=None) -> torch.Tensor:
+    """out = softmax(Q K^T) V per (image, head) with separate sources (csrc/kernels/cross_attention.hip).  q holds
+    batch * tokens_q rows of heads * key_dim channels (Q already scaled by 1/sqrt(key_dim)), k batch * tokens_k rows
+    of heads * key_dim, v batch * tokens_k rows of heads * value_dim, head-major; each is a tensor view whose row
+    stride may exceed its width: a whole buffer, or a column slice of one ([Q | K] or [K | V] side by side).  out
+    [..., ld_out] (contiguous) gets heads * value_dim channels per row and zeros in the rest of the row.  fp32 or
+    bf16, all four alike."""
+    dv = int(value_dim or key_dim)
+    B, Tq, Tk, h, d = int(batch), int(tokens_q), int(tokens_k), int(heads), int(key_dim)
+    if q.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"cross_attention: fp32 or bf16 tensors, got {q.dtype}")
+    if min(B, Tq, Tk, h, d, dv) < 1:
+        raise ValueError(f"cross_attention: batch, tokens, heads and head sizes must be positive "
+                         f"({B}, {Tq}, {Tk}, {h}, {d}, {dv})")
+    (ldq, wq), (ldk, wk), (ldv, wv) = (_rows_view(t, q.dtype, n) for t, n in ((q, "q"), (k, "k"), (v, "v")))
+    _chk(out, q.dtype, "out")
+    ld_out = int(out.shape[-1])
+    if (q.numel() != B * Tq * wq or k.numel() != B * Tk * wk or v.numel() != B * Tk * wv
+            or out.numel() != B * Tq * ld_out or wq < h * d or wk < h * d or wv < h * dv or ld_out < h * dv):
+        raise ValueError(f"cross_attention: q{tuple(q.shape)} k{tuple(k.shape)} v{tuple(v.shape)} out{tuple(out.shape)} "
+                         f"do not hold {B} x {Tq} query and {B} x {Tk} key / value rows of {h} heads ({d}, {dv})")
+    if max(B * Tq * ldq, B * Tk * ldk, B * Tk * ldv, out.numel(), B * h * Tq) >= 2 ** 31:
+        raise ValueError("cross_attention: every tensor must span fewer than 2^31 elements (32-bit index math)")
+    fn = kernels().attention_qkv_f32 if q.dtype == torch.float32 else kernels().attention_qkv_bf16
+    fn(ptr(q), ptr(k), ptr(v), ptr(out), B, Tq, Tk, h, d, dv, ldq, ldk, ldv, ld_out, stream_handle(stream))
+    return out
+
+
+def queries(emb: torch.Tensor, out: torch.Tensor, C: Optional[int] = None, stream=None) -> torch.Tensor:
+    """LearnedQueries: out[b, 0, t] = emb[t] for every image b.  emb [N, C] fp32, out [B, 1, N, Cp] fp32 (Cp = C)
+    or bf16 (rows padded to Cp channels with `C` real ones; the padding is written as zeros)."""
+    if out.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"queries: fp32 or bf16 output, got {out.dtype}")
+    _chk(emb, torch.float32, "emb"); _chk(out, out.dtype, "out")
+    if emb.dim() != 2 or emb.numel() == 0:
+        raise ValueError(f"queries: emb{tuple(emb.shape)} is not [N, C]")
+    N, Ce = int(emb.shape[0]), int(emb.shape[1])
+    Cp, B = int(out.shape[-1]), int(out.shape[0])
+    C = Ce if C is None else int(C)
+    if C != Ce or Cp < C or (out.dtype == torch.float32 and Cp != C) or (out.dtype == torch.bfloat16 and Cp % 8):
+        raise ValueError(f"queries: emb{tuple(emb.shape)} does not fill rows of {Cp} channels ({C} real, {out.dtype})")
+    if B < 1 or out.numel() != B * N * Cp:
+        raise ValueError(f"queries: out{tuple(out.shape)} is not [B, 1, {N}, {Cp}]")
+    if out.numel() >= 2 ** 31:
+        raise ValueError("queries: tensors must hold fewer than 2^31 elements")
+    if out.dtype == torch.float32:
+        kernels().queries_f32(ptr(emb), ptr(out), B, N, C, stream_handle(stream))
+    else:
+        kernels().queries_bf16(ptr(emb), ptr(out), B, N, Cp, C, stream_handle(stream))
     return out
 
 

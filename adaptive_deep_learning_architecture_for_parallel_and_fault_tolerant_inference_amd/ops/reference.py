@@ -13,7 +13,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ..graph.ir import Graph, _pair, deconv_out_len, deconv_pad_before, same_pads
+from ..graph.ir import Graph, _pair, deconv_out_len, deconv_pad_before, mha_sources, same_pads
 
 
 def _same(x: torch.Tensor, kh: int, kw: int, s: int, value: float = 0.0) -> torch.Tensor:
@@ -155,13 +155,14 @@ class ReferenceExecutor:
         if L.op == "layerscale":
             return ins[0] * self.w[f"{L.name}/gamma"]
         if L.op == "mha":
-            # Keras MultiHeadAttention(x, x): attention over all positions, the query scaled before the dot product
+            # Keras MultiHeadAttention(query, value, key): attention over all positions, the query scaled before the
+            # dot product; one input is (x, x), a missing key is the value
             w = lambda p: self.w[f"{L.name}/{p}/kernel"]
             b = lambda p: self.w.get(f"{L.name}/{p}/bias", 0.0)
-            x = ins[0].reshape(ins[0].shape[0], -1, ins[0].shape[-1])           # (B, T, C)
+            x, xk, xv = (t.reshape(t.shape[0], -1, t.shape[-1]) for t in mha_sources(ins))      # (B, T, C) each
             q = (torch.einsum("btc,chd->bthd", x, w("query")) + b("query")) * (1.0 / float(a["key_dim"]) ** 0.5)
-            k = torch.einsum("btc,chd->bthd", x, w("key")) + b("key")
-            v = torch.einsum("btc,chd->bthd", x, w("value")) + b("value")
+            k = torch.einsum("btc,chd->bthd", xk, w("key")) + b("key")
+            v = torch.einsum("btc,chd->bthd", xv, w("value")) + b("value")
             p = torch.softmax(torch.einsum("bqhd,bkhd->bhqk", q, k), dim=-1)
             y = torch.einsum("bhqk,bkhd->bqhd", p, v)
             y = torch.einsum("bqhd,hdc->bqc", y, w("attention_output")) + b("attention_output")
@@ -214,6 +215,8 @@ class ReferenceExecutor:
             if a.get("class_token"):
                 x = torch.cat([self.w[f"{L.name}/class_token"].expand(x.shape[0], 1, -1), x], dim=1)
             return (x + self.w[f"{L.name}/position_embedding"]).unsqueeze(1)
+        if L.op == "queries":
+            return self.w[f"{L.name}/embeddings"].expand(ins[0].shape[0], 1, -1, -1)
         if L.op == "relu":
             y = torch.relu(ins[0])
             return y if a.get("max_value") is None else torch.clamp(y, max=float(a["max_value"]))

@@ -56,7 +56,7 @@ class CpuExecutor:
 
     KINDS = ("conv", "gconv", "dwconv", "maxpool", "avgpool", "bn", "add", "relu", "act", "binary", "affine", "gmp", "copy",
              "concat", "gap", "dense", "softmax", "pad", "layernorm", "deconv", "upsample", "crop", "attention",
-             "posembed", "winattn", "space_to_depth", "groupnorm")
+             "posembed", "winattn", "space_to_depth", "groupnorm", "queries")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], outputs: Optional[Sequence[str]] = None):
         self.g = g
@@ -125,6 +125,8 @@ class CpuExecutor:
                 n = st.p["layer"]
                 cls = weights[f"{n}/class_token"].reshape(-1) if st.p["class_token"] else None
                 self.packed[i] = (cls, np.ascontiguousarray(weights[f"{n}/position_embedding"], np.float32))
+            elif st.kind == "queries":
+                self.packed[i] = (np.ascontiguousarray(weights[f"{st.p['layer']}/embeddings"], np.float32),)
             elif st.kind == "winattn":           # the raw table: the native op does the index and region math
                 self.packed[i] = (np.ascontiguousarray(
                     weights[f"{st.p['layer']}/relative_position_bias_table"], np.float32),)
@@ -193,6 +195,14 @@ class CpuExecutor:
         elif k == "groupnorm":
             gm, bt = self.packed[i]
             m.groupnorm(ins[0], gm, bt, y, int(p["groups"]), float(p["eps"]), int(p["act"]), 0.3)
+        elif k == "attention" and "tokens_q" in p:      # separate sources: column slices of the projections
+            h, d, dv = int(p["heads"]), int(p["key_dim"]), int(p["value_dim"])
+            q, kk, v = (ins[p[c][0]].reshape(-1, ins[p[c][0]].shape[-1])[:, p[c][1]:p[c][1] + h * w]
+                        for c, w in (("q", d), ("k", d), ("v", dv)))
+            m.cross_attention(q, kk, v, y.reshape(-1, y.shape[-1]), batch, int(p["tokens_q"]), int(p["tokens_k"]),
+                              h, d, dv)
+        elif k == "queries":
+            m.queries(self.packed[i][0], y, batch)
         elif k == "attention":
             m.attention(ins[0].reshape(-1, ins[0].shape[-1]), y.reshape(-1, y.shape[-1]), batch, int(p["tokens"]),
                         int(p["heads"]), int(p["key_dim"]), int(p["value_dim"]))

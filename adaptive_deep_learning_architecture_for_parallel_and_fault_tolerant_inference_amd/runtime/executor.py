@@ -79,7 +79,8 @@ class SliceExecutor:
 
     FP32_KINDS = ("conv", "pair", "dense", "maxpool", "gap", "softmax", "add", "bn", "relu", "pad", "copy",
                   "dwconv", "avgpool", "concat", "act", "binary", "affine", "stem_f32", "gconv", "layernorm",
-                  "deconv", "upsample", "crop", "attention", "posembed", "winattn", "space_to_depth", "groupnorm")
+                  "deconv", "upsample", "crop", "attention", "posembed", "winattn", "space_to_depth", "groupnorm",
+                  "queries")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], batch: int, device="cuda",
                  outputs: Optional[Sequence[str]] = None, tune: bool = False, num_sets: int = 1,
@@ -243,6 +244,9 @@ class SliceExecutor:
                 self.packed[i] = self._pack_layernorm(weights, st, self.shape_of(st.out)[-1])
             elif st.kind == "posembed":
                 self.packed[i] = self._pack_posembed(weights, st)
+            elif st.kind == "queries":           # the (N, C) embeddings, fp32 and true width in both precisions
+                self.packed[i] = torch.tensor(np.ascontiguousarray(weights[f"{st.p['layer']}/embeddings"], np.float32),
+                                              device=dev)
             elif st.kind == "winattn":           # relative position bias + shift mask, fp32 in both precisions
                 self.packed[i] = attn_ops.window_bias(weights[f"{st.p['layer']}/relative_position_bias_table"],
                                                       st.p["window"], st.p["shift"], device=dev)
@@ -293,6 +297,9 @@ class SliceExecutor:
                 self.packed[i] = self._pack_layernorm(weights, st, self.shape_of(st.out)[-1])
             elif st.kind == "posembed":
                 self.packed[i] = self._pack_posembed(weights, st)
+            elif st.kind == "queries":           # the (N, C) embeddings, fp32 and true width in both precisions
+                self.packed[i] = torch.tensor(np.ascontiguousarray(weights[f"{st.p['layer']}/embeddings"], np.float32),
+                                              device=dev)
             elif st.kind == "winattn":           # relative position bias + shift mask, fp32 in both precisions
                 self.packed[i] = attn_ops.window_bias(weights[f"{st.p['layer']}/relative_position_bias_table"],
                                                       st.p["window"], st.p["shift"], device=dev)
@@ -333,11 +340,21 @@ class SliceExecutor:
                                  device=self.device)
 
     def _launch_tokens(self, i: int, st: Step, b, stream) -> None:
-        """The attention cores, the position embedding and space-to-depth: one wrapper each for both precisions."""
-        if st.kind == "attention":
+        """The attention cores, the position embedding, the learned queries and space-to-depth: one wrapper each
+        for both precisions."""
+        if st.kind == "attention" and "tokens_q" in st.p:
+            # separate sources: Q, K and V are column slices of the projection buffers (runtime/plan.py)
+            p = st.p
+            h, d, dv = p["heads"], p["key_dim"], p["value_dim"]
+            q, k, v = (b[st.ins[p[c][0]]][..., p[c][1]:p[c][1] + h * w] for c, w in (("q", d), ("k", d), ("v", dv)))
+            attn_ops.cross_attention(q, k, v, b[st.out], self.batch, p["tokens_q"], p["tokens_k"], h, d, dv,
+                                     stream=stream)
+        elif st.kind == "attention":
             p = st.p
             attn_ops.attention(b[st.ins[0]], b[st.out], self.batch, p["tokens"], p["heads"], p["key_dim"],
                                p["value_dim"], stream=stream)
+        elif st.kind == "queries":
+            attn_ops.queries(self.packed[i], b[st.out], C=self.g.layers[st.p["layer"]].out_shape[-1], stream=stream)
         elif st.kind == "winattn":
             p = st.p
             attn_ops.window_attention(b[st.ins[0]], self.packed[i], b[st.out], self.batch, p["height"], p["width"],
@@ -834,7 +851,7 @@ class SliceExecutor:
                 gm, bt = self.packed[i]
                 E.groupnorm(b[st.ins[0]], gm, bt, b[st.out], self.g.layers[st.p["layer"]].out_shape[-1],
                             st.p["groups"], st.p["eps"], act=st.p["act"], workspace=self._gn_ws, stream=stream)
-            elif k in ("attention", "posembed", "winattn", "space_to_depth"):
+            elif k in ("attention", "posembed", "winattn", "space_to_depth", "queries"):
                 self._launch_tokens(i, st, b, stream)
             elif k == "act":
                 E.act(b[st.ins[0]], b[st.out], st.p["mode"], st.p["alpha"], stream=stream)
@@ -968,7 +985,7 @@ class SliceExecutor:
             gm, bt = self.packed[i]
             E.groupnorm_f32(b[st.ins[0]], gm, bt, b[st.out], st.p["groups"], st.p["eps"], act=st.p["act"],
                             workspace=self._gn_ws, stream=stream)
-        elif k in ("attention", "posembed", "winattn", "space_to_depth"):
+        elif k in ("attention", "posembed", "winattn", "space_to_depth", "queries"):
             self._launch_tokens(i, st, b, stream)
         elif k == "deconv":
             conv_ops.deconv_forward_f32(b[st.ins[0]], self.packed[i], b[st.out], relu=st.p["relu"], stream=stream)

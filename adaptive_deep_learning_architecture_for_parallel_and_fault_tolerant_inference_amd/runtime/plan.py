@@ -26,8 +26,13 @@ kernels:
                step, `n#qkv` -> `n#ctx`; and a ``conv`` (1x1) `n#ctx` -> `n`, the output projection,
                which takes the block's Add as its residual like any Dense.  The `#` tensors are
                internal (a cut can only name `n`); a kind of its own, so no pair, sibling, stem or
-               bottleneck pass ever sees it
+               bottleneck pass ever sees it.  A layer whose query, key and value come from different
+               tensors gets one projection ``conv`` per distinct source, the parts that share a source side
+               by side: `n#qk` and `n#v` (q = k = `src + pos`, v = `src`), `n#q` and `n#kv` (key = value),
+               or `n#q`, `n#k`, `n#v`; its ``attention`` step takes those buffers and records `tokens_q`,
+               `tokens_k` and, as `q` / `k` / `v`, (which input, first column) of each part
 * ``posembed`` ViT class token + learned position embedding
+* ``queries``  a LearnedQueries layer: its (N, C) weight broadcast to every image, one copy step
 * ``winattn``  the core of a Swin window attention layer `n`: like ``attention`` three steps, a ``conv``
                `n#qkv`, this step `n#qkv` -> `n#ctx` on the (H, W, C) map (nothing is rolled or
                partitioned in memory; the relative position bias and the shift mask are packed once
@@ -64,7 +69,7 @@ import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Set
 
-from ..graph.ir import ACT_MODE, Graph, _pair, deconv_pad_before, same_pads
+from ..graph.ir import ACT_MODE, MHA_PARTS, Graph, _pair, deconv_pad_before, mha_sources, same_pads
 
 
 @dataclass
@@ -85,13 +90,17 @@ def tensor_shape(g: Graph, name: str) -> tuple:
     if tag in ("qkv", "ctx") and L.op == "winattn":     # a window attention's stay (H, W, channels) maps
         hd = int(L.attrs["num_heads"]) * int(L.attrs["key_dim"])
         return tuple(L.out_shape[:-1]) + (3 * hd if tag == "qkv" else hd,)
-    if tag in ("qkv", "ctx"):
+    if tag == "ctx" or tag in MHA_PARTS:
+        # "ctx" has the query's tokens; a projection (`n#q`, `n#kv`, ...) the tokens of the source its parts share
         h, d = int(L.attrs["num_heads"]), int(L.attrs["key_dim"])
         dv = int(L.attrs.get("value_dim") or d)
+        src = dict(zip(("query", "key", "value"), mha_sources(L.inputs)))
+        shape = L.out_shape if tag == "ctx" else g.layers[src[MHA_PARTS[tag][0]]].out_shape
         tokens = 1
-        for v in L.out_shape[:-1]:
+        for v in shape[:-1]:
             tokens *= v
-        return (1, tokens, h * (2 * d + dv) if tag == "qkv" else h * dv)
+        width = {"query": h * d, "key": h * d, "value": h * dv}
+        return (1, tokens, h * dv if tag == "ctx" else sum(width[p] for p in MHA_PARTS[tag]))
     return tuple(L.out_shape)
 
 
@@ -428,13 +437,39 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                         "pads": ((0, 0), (0, 0)), "stride": 1, "kernel": (1, 1), "filters": filters,
                         "packed_input": False, **head}
 
-            steps.append(Step("conv", n + "#qkv", [R(L.inputs[0])], [], proj("qkv", h * (2 * d + dv), None)))
+            sq, sk, sv = (R(t) for t in mha_sources(L.inputs)) if L.op == "mha" else (R(L.inputs[0]),) * 3
+            if sq == sk == sv:
+                steps.append(Step("conv", n + "#qkv", [sq], [], proj("qkv", h * (2 * d + dv), None)))
             if L.op == "winattn":               # on the (H, W, C) map, windows and shift resolved by the kernel
                 steps.append(Step("winattn", n + "#ctx", [n + "#qkv"], [],
                                   {"layer": n, "height": L.out_shape[0], "width": L.out_shape[1],
                                    "window": int(a["window"]), "shift": int(a.get("shift", 0)), **head}))
-            else:
+            elif sq == sk == sv:
                 steps.append(Step("attention", n + "#ctx", [n + "#qkv"], [], {"layer": n, "tokens": tokens, **head}))
+            else:
+                # separate sources: one projection per distinct source tensor, the parts that share one side by
+                # side ([Q | K] from `src + pos`, [K | V] when the key is the value); the core then reads Q, K and
+                # V at (which input buffer, first column)
+                if sq == sk:
+                    parts = [("qk", sq), ("v", sv)]
+                elif sk == sv:
+                    parts = [("q", sq), ("kv", sk)]
+                else:
+                    parts = [("q", sq), ("k", sk), ("v", sv)]
+                width = {"q": h * d, "k": h * d, "v": h * dv}
+                where = {}
+                for j, (part, src) in enumerate(parts):
+                    steps.append(Step("conv", f"{n}#{part}", [src], [],
+                                      proj(part, sum(width[c] for c in part), None)))
+                    col = 0
+                    for c in part:
+                        where[c] = (j, col)
+                        col += width[c]
+                tokens_k = 1
+                for v in g.layers[mha_sources(L.inputs)[1]].out_shape[:-1]:
+                    tokens_k *= v
+                steps.append(Step("attention", n + "#ctx", [f"{n}#{part}" for part, _ in parts], [],
+                                  {"layer": n, "tokens_q": tokens, "tokens_k": tokens_k, **where, **head}))
             cover = [n]
             res, out, relu = residual_add(n, cover)
             steps.append(Step("conv", out, [n + "#ctx"] + ([res] if res else []), cover,
@@ -444,6 +479,9 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
         elif L.op == "posembed":
             steps.append(Step("posembed", n, [R(L.inputs[0])], [n],
                               {"layer": n, "class_token": bool(a.get("class_token"))}))
+            done.add(n)
+        elif L.op == "queries":                 # the input only supplies the batch size
+            steps.append(Step("queries", n, [R(L.inputs[0])], [n], {"layer": n}))
             done.add(n)
         elif L.op == "space_to_depth":
             steps.append(Step("space_to_depth", n, [R(L.inputs[0])], [n]))

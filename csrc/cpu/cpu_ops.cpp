@@ -479,6 +479,71 @@ void attention(const Arr<float>& qkv, Arr<float>& out, int B, int T, int heads, 
   }
 }
 
+// Attention core with separate sources, softmax(Q K^T) V per (image, head): q [B*Tq][ldq], k [B*Tk][ldk],
+// v [B*Tk][ldv], each starting at its part's first column (head h at h*d for Q and K, h*dv for V; Q already scaled),
+// out [B*Tq][ld_out] with heads * dv channels (the rest of a row becomes zero): the argument layout of the GPU op
+// (csrc/kernels/cross_attention.hip), the strides being the arrays' last dimensions.  A column slice of a wider
+// array arrives as a dense copy.
+void cross_attention(const Arr<float>& q, const Arr<float>& k, const Arr<float>& v, Arr<float>& out, int B, int Tq,
+                     int Tk, int heads, int d, int dv) {
+  need(q.ndim() >= 2 && k.ndim() >= 2 && v.ndim() >= 2 && out.ndim() >= 2 && B >= 1 && Tq >= 1 && Tk >= 1 &&
+           heads >= 1 && d >= 1 && dv >= 1, "cross_attention args");
+  const long ldq = q.shape(q.ndim() - 1), ldk = k.shape(k.ndim() - 1), ldv = v.shape(v.ndim() - 1),
+             ld_out = out.shape(out.ndim() - 1);
+  need(q.size() == (long)B * Tq * ldq && k.size() == (long)B * Tk * ldk && v.size() == (long)B * Tk * ldv &&
+           out.size() == (long)B * Tq * ld_out && ldq >= (long)heads * d && ldk >= (long)heads * d &&
+           ldv >= (long)heads * dv && ld_out >= (long)heads * dv, "cross_attention shapes");
+  const float *qp = cptr(q), *kp = cptr(k), *vp = cptr(v);
+  float* yp = mptr(out);
+  py::gil_scoped_release nogil;
+#pragma omp parallel
+  {
+    std::vector<float> p(Tk);
+#pragma omp for collapse(2) schedule(static)
+    for (int b = 0; b < B; ++b)
+      for (int h = 0; h < heads; ++h) {
+        const float* kb = kp + (size_t)b * Tk * ldk + h * d;
+        const float* vb = vp + (size_t)b * Tk * ldv + h * dv;
+        for (int qi = 0; qi < Tq; ++qi) {
+          const float* qr = qp + ((size_t)b * Tq + qi) * ldq + h * d;
+          float mx = -INFINITY;
+          for (int kk = 0; kk < Tk; ++kk) {
+            const float* kr = kb + (size_t)kk * ldk;
+            float sc = 0.f;
+            for (int i = 0; i < d; ++i) sc += qr[i] * kr[i];
+            p[kk] = sc;
+            mx = std::max(mx, sc);
+          }
+          float l = 0.f;
+          for (int kk = 0; kk < Tk; ++kk) {
+            p[kk] = std::exp(p[kk] - mx);
+            l += p[kk];
+          }
+          float* orow = yp + ((size_t)b * Tq + qi) * ld_out + h * dv;
+          for (int c = 0; c < dv; ++c) orow[c] = 0.f;
+          for (int kk = 0; kk < Tk; ++kk) {
+            const float* vr = vb + (size_t)kk * ldv;
+            const float pk = p[kk];
+            for (int c = 0; c < dv; ++c) orow[c] += pk * vr[c];
+          }
+          const float inv = 1.f / l;
+          for (int c = 0; c < dv; ++c) orow[c] *= inv;
+          if (h == heads - 1)
+            for (long c = (long)heads * dv; c < ld_out; ++c) yp[((size_t)b * Tq + qi) * ld_out + c] = 0.f;
+        }
+      }
+  }
+}
+
+// Learned queries: out[b][t] = emb[t] for every image, emb [N][C], out [B][...][N][C]
+void queries(const Arr<float>& emb, Arr<float>& out, int B) {
+  need(emb.ndim() == 2 && B >= 1 && out.size() == (long)B * emb.size(), "queries shapes");
+  const float* ep = cptr(emb);
+  float* yp = mptr(out);
+  const size_t n = (size_t)emb.size();
+  for (int b = 0; b < B; ++b) std::memcpy(yp + (size_t)b * n, ep, n * sizeof(float));
+}
+
 // ------------------------------------------------------------------ depthwise
 // x [N,H,W,C]; w [KH,KW,C]; bias [C]; y [N,OH,OW,C]
 ADAPT_CLONES
@@ -798,6 +863,9 @@ PYBIND11_MODULE(_cpu, m) {
   m.def("window_attention", &window_attention, py::arg("qkv"), py::arg("table"), py::arg("out"), py::arg("B"),
         py::arg("H"), py::arg("W"), py::arg("window"), py::arg("shift"), py::arg("heads"), py::arg("key_dim"));
   m.def("space_to_depth", &space_to_depth, py::arg("x"), py::arg("y"));
+  m.def("cross_attention", &cross_attention, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("B"),
+        py::arg("Tq"), py::arg("Tk"), py::arg("heads"), py::arg("d"), py::arg("dv"));
+  m.def("queries", &queries, py::arg("emb"), py::arg("out"), py::arg("B"));
   m.def("layernorm", &layernorm, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("y"), py::arg("eps"));
   m.def("groupnorm", &groupnorm, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("y"), py::arg("groups"),
         py::arg("eps"), py::arg("act") = 0, py::arg("alpha") = 0.3f);

@@ -439,6 +439,25 @@ PYBIND11_MODULE(_C, m) {
   m.def("attention_path", &adapt::attention_path);
   m.def("attention_query_tile", &adapt::attention_query_tile);
   m.def("attention_key_tile", &adapt::attention_key_tile);
+  m.def("attention_qkv_f32", [](u64 q, u64 k, u64 v, u64 out, int B, int Tq, int Tk, int heads, int d, int dv, int ldq,
+                                int ldk, int ldv, int ld_out, u64 s) {
+    check(adapt::attention_qkv_f32(P<const float>(q), P<const float>(k), P<const float>(v), P<float>(out), B, Tq, Tk,
+                                   heads, d, dv, ldq, ldk, ldv, ld_out, S(s)), "attention_qkv_f32");
+  });
+  m.def("attention_qkv_bf16", [](u64 q, u64 k, u64 v, u64 out, int B, int Tq, int Tk, int heads, int d, int dv, int ldq,
+                                 int ldk, int ldv, int ld_out, u64 s) {
+    check(adapt::attention_qkv_bf16(P<const bf16>(q), P<const bf16>(k), P<const bf16>(v), P<bf16>(out), B, Tq, Tk,
+                                    heads, d, dv, ldq, ldk, ldv, ld_out, S(s)), "attention_qkv_bf16");
+  });
+  m.def("cross_attention_path", &adapt::cross_attention_path);
+  m.def("cross_attention_query_tile", &adapt::cross_attention_query_tile);
+  m.def("cross_attention_key_tile", &adapt::cross_attention_key_tile);
+  m.def("queries_f32", [](u64 emb, u64 y, int B, int N, int C, u64 s) {
+    check(adapt::queries_f32(P<const float>(emb), P<float>(y), B, N, C, S(s)), "queries_f32");
+  });
+  m.def("queries_bf16", [](u64 emb, u64 y, int B, int N, int Cp, int C, u64 s) {
+    check(adapt::queries_bf16(P<const float>(emb), P<bf16>(y), B, N, Cp, C, S(s)), "queries_bf16");
+  });
   m.def("window_attention_f32", [](u64 qkv, u64 bias, u64 out, int B, int H, int W, int M, int shift, int heads, int d,
                                    int ld_in, int ld_out, u64 s) {
     check(adapt::window_attention_f32(P<const float>(qkv), P<const float>(bias), P<float>(out), B, H, W, M, shift,

@@ -393,6 +393,19 @@ hipError_t attention_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, i
 int attention_path(int d, int dv);     // 1: MFMA path, 0: plain kernel
 int attention_query_tile();            // queries per block of the MFMA path
 int attention_key_tile();              // keys per LDS tile of the MFMA path
+// Attention core with separate sources (cross_attention.hip): q [B*Tq][ldq], k [B*Tk][ldk], v [B*Tk][ldv], each
+// pointer already offset to its part's first column (head h at h*d for Q and K, h*dv for V; Q pre-scaled), out
+// [B*Tq][ld_out] with heads*dv true channels (the rest of a row is written as zeros).  The MFMA path takes what
+// `attention_path` takes when the four pointers are aligned to 4 elements and the strides are multiples of 4;
+// everything else runs on a plain kernel.
+hipError_t attention_qkv_f32(const float* q, const float* k, const float* v, float* out, int B, int Tq, int Tk,
+                             int heads, int d, int dv, int ldq, int ldk, int ldv, int ld_out, hipStream_t s);
+hipError_t attention_qkv_bf16(const bf16* q, const bf16* k, const bf16* v, bf16* out, int B, int Tq, int Tk, int heads,
+                              int d, int dv, int ldq, int ldk, int ldv, int ld_out, hipStream_t s);
+int cross_attention_path(uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t out, int d, int dv, int ldq, int ldk, int ldv,
+                         int ld_out, int elem_size);    // 1: MFMA path, 0: plain kernel
+int cross_attention_query_tile();      // queries per block of the MFMA path
+int cross_attention_key_tile();        // keys per LDS tile of the MFMA path
 // Swin window attention core (window_attention.hip): qkv the NHWC map [B*H*W][ld_in], rows of [Q | K | V]
 // (head-major, heads x d each, Q pre-scaled), attention inside M x M windows of the grid shifted by `shift`,
 // nothing rolled or partitioned in memory.  bias [classes][heads][Tp][Tp] fp32 (Tp = M^2 rounded up to the key
@@ -416,6 +429,10 @@ hipError_t posembed_f32(const float* x, const float* cls, const float* pos, floa
                         hipStream_t s);
 hipError_t posembed_bf16(const bf16* x, const float* cls, const float* pos, bf16* y, int B, int T, int Cp, int C,
                          int ct, hipStream_t s);
+// Learned queries (layers.hip): y[b][t] = emb[t] for every image b, a broadcast copy; emb [N][C] fp32; bf16 rows are
+// Cp wide, padding written as zeros
+hipError_t queries_f32(const float* emb, float* y, int B, int N, int C, hipStream_t s);
+hipError_t queries_bf16(const float* emb, bf16* y, int B, int N, int Cp, int C, hipStream_t s);
 bool gconv_f32_mfma_ok(int Cin, int Cout, int G);     // shape rule of the MFMA path
 // mfma: which path to launch (the caller packed w for it); an ineligible shape is an error, never a fall-through
 hipError_t gconv_f32_forward(const GconvF32Params& p, bool mfma, hipStream_t s);

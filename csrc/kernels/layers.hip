@@ -499,4 +499,62 @@ hipError_t posembed_bf16(const bf16* x, const float* cls, const float* pos, bf16
   return posembed_launch<bf16>(x, cls, pos, y, B, T, C, Cp, ct, s);
 }
 
+// Learned queries: y[b][t][c] = emb[t][c] for every image b, a broadcast copy like posembed's.  emb [N][C] is fp32,
+// y [B][N][ld] (fp32 rows of C channels, or bf16 rows padded to ld with channels C..ld-1 written as zeros).
+// VEC = 16 bytes of y per thread where ld, C and the bases allow (every vector then lies wholly inside or wholly
+// outside the C channels, and emb is read 16 bytes at a time), else 1.
+namespace {
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void queries_kernel(const float* __restrict__ emb, T* __restrict__ y, int N, int C,
+                                                      int ld, size_t total) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int nv = ld / VEC;
+  const int v = (int)(idx % nv);
+  const size_t row = idx / nv;
+  const int t = (int)(row % N);
+  const float* er = emb + (size_t)t * C + (size_t)v * VEC;
+  T* yr = y + row * ld + (size_t)v * VEC;
+  if constexpr (VEC == 1) {
+    yr[0] = (T)(v < C ? er[0] : 0.f);
+  } else if constexpr (sizeof(T) == 4) {
+    *(f32x4*)yr = *(const f32x4*)er;                  // fp32 rows are not padded: ld == C
+  } else {
+    f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f}, b = a;
+    if (v * VEC < C) {                                // C % 8 == 0 here: the vector is all channels or all padding
+      a = *(const f32x4*)er;
+      b = *(const f32x4*)(er + 4);
+    }
+    V8 q;
+    q.e[0] = f2bf(a.x); q.e[1] = f2bf(a.y); q.e[2] = f2bf(a.z); q.e[3] = f2bf(a.w);
+    q.e[4] = f2bf(b.x); q.e[5] = f2bf(b.y); q.e[6] = f2bf(b.z); q.e[7] = f2bf(b.w);
+    *(u32x4*)yr = q.u;
+  }
+}
+
+template <typename T>
+hipError_t queries_launch(const float* emb, T* y, int B, int N, int C, int ld, hipStream_t s) {
+  constexpr int VEC = 16 / sizeof(T);
+  if (B < 1 || N < 1 || C < 1 || ld < C || !emb || !y) return hipErrorInvalidValue;
+  if (sizeof(T) == 4 && ld != C) return hipErrorInvalidValue;
+  const size_t rows = (size_t)B * N;
+  if (ld % VEC == 0 && C % VEC == 0 && (((uintptr_t)emb | (uintptr_t)y) & 15) == 0) {
+    const size_t total = rows * (ld / VEC);
+    hipLaunchKernelGGL((queries_kernel<T, VEC>), dim3(grid_of(total)), dim3(256), 0, s, emb, y, N, C, ld, total);
+  } else {
+    const size_t total = rows * ld;
+    hipLaunchKernelGGL((queries_kernel<T, 1>), dim3(grid_of(total)), dim3(256), 0, s, emb, y, N, C, ld, total);
+  }
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t queries_f32(const float* emb, float* y, int B, int N, int C, hipStream_t s) {
+  return queries_launch<float>(emb, y, B, N, C, C, s);
+}
+
+hipError_t queries_bf16(const float* emb, bf16* y, int B, int N, int Cp, int C, hipStream_t s) {
+  return queries_launch<bf16>(emb, y, B, N, C, Cp, s);
+}
+
 }  // namespace adapt

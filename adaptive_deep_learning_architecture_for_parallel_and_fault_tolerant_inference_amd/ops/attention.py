@@ -1,4 +1,5 @@
-"""Wrappers for the self-attention core (csrc/kernels/attention.hip), the attention core with separate query /
+"""Wrappers for the self-attention core (csrc/kernels/attention.hip; csrc/kernels/attention_core.h holds the
+scheme of all three), the attention core with separate query /
 key / value sources (csrc/kernels/cross_attention.hip), Swin's window attention core and its bias packer
 (csrc/kernels/window_attention.hip), and the ViT class token / position embedding and learned-queries kernels
 (csrc/kernels/layers.hip).

@@ -9,7 +9,8 @@
 // [B * Tq][ld_out] with heads x dv true channels; channels heads * dv .. ld_out - 1 are layout padding and are
 // written as zeros.  Columns of q / k / v outside the heads are never read.
 //
-// MFMA path (d and dv multiples of 16 up to 128, any Tq, Tk >= 1), the scheme of attention.hip: a block of 4
+// MFMA path (d and dv multiples of 16 up to 128, any Tq, Tk >= 1), the scheme of attention_core.h in a copy of its
+// own (on the core's template this kernel measured up to 0.9 % slower, BASELINE.md "Round 16"): a block of 4
 // waves owns XA_QT = 64 queries of one (image, head), each wave's 16 queries' Q in registers; the keys are walked
 // XA_KT = 32 at a time up to Tk, K / V rows through padded LDS rows and fetched into registers one tile ahead;
 // the score product is taken swapped on v_mfma_f32_16x16x4_f32 (S^T = K Q^T), so a lane's four scores are the B

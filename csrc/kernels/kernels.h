@@ -383,7 +383,8 @@ hipError_t upsample_bf16(const bf16* x, bf16* y, int B, int H, int W, int Cp, in
 hipError_t crop_f32(const float* x, float* y, int B, int H, int W, int C, int OH, int OW, int T, int L, hipStream_t s);
 hipError_t crop_bf16(const bf16* x, bf16* y, int B, int H, int W, int Cp, int C, int OH, int OW, int T, int L,
                      hipStream_t s);
-// Self-attention core (attention.hip): qkv [B*T][ld_in] rows of [Q | K | V] (head-major, Q pre-scaled), out
+// Self-attention core (attention.hip, on the kernel templates of attention_core.h, which holds the scheme):
+// qkv [B*T][ld_in] rows of [Q | K | V] (head-major, Q pre-scaled), out
 // [B*T][ld_out] with heads*dv true channels (the rest of a row is written as zeros).  d, dv multiples of 16 up
 // to 128 run on the fp32 MFMA (flash-style, online softmax), every other size on a plain kernel.
 hipError_t attention_f32(const float* qkv, float* out, int B, int T, int heads, int d, int dv, int ld_in, int ld_out,

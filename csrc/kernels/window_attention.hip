@@ -18,7 +18,8 @@
 // computes no regions.  A lane reads the four keys of its query as one 16-byte load, and the score accumulator
 // starts from it.
 //
-// MFMA path (d a multiple of 16 up to 128): the scheme of attention.hip.  A block of 4 waves owns one (image,
+// MFMA path (d a multiple of 16 up to 128): the scheme of attention_core.h in a copy of its own (on the core's
+// template this kernel measured up to 0.7 % slower, BASELINE.md "Round 16").  A block of 4 waves owns one (image,
 // window, head, tile of WA_QT = 64 queries); the keys of the window are walked WA_KT = 32 at a time, K and V staged
 // through padded LDS rows and fetched one tile ahead; swapped score product S^T = K Q^T on
 // v_mfma_f32_16x16x4_f32, P kept in registers as the B operand of O^T = V^T P^T, online softmax in the lane that

@@ -98,6 +98,9 @@ class PackedConv:
     wino: Optional[torch.Tensor] = None   # fp32 3x3/s1/p1: Winograd-transformed weights (pack_wino_f32)
     pwf: Optional[torch.Tensor] = None    # fp32 1x1/s1: fragment-packed weights of pw_f32.hip (pack_pw_f32)
     wino4s: Optional[torch.Tensor] = None  # fp32 3x3/s1/p1: Winograd F(4x4, 3x3) weights (wino4s_pack_np)
+    # fp32, > 1: the fused residual is a larger [B, res_H, res_W, cout] map and output pixel (oh, ow) adds its
+    # pixel (res_stride oh, res_stride ow), whatever the conv's own stride (runtime/plan.py subsample_lattice)
+    res_stride: int = 0
 
     @property
     def K(self) -> int:
@@ -181,8 +184,10 @@ class ConvFamily(NamedTuple):
     launch: Callable     # (ConvCall) -> None: the family's own shape rules and its kernels() call
 
 
-# A checked call on its way to `ConvFamily.launch`: `ws` / `ctr` are device pointers (0: none needed)
-ConvCall = namedtuple("ConvCall", "x pc out residual relu out2 relu2 cfg ks B H W OH OW ws ctr stream")
+# A checked call on its way to `ConvFamily.launch`: `ws` / `ctr` are device pointers (0: none needed);
+# `res_H` / `res_W` / `res_stride`: the residual's own map when it is sampled (PackedConv.res_stride > 1), else 0
+ConvCall = namedtuple("ConvCall", "x pc out residual relu out2 relu2 cfg ks B H W OH OW ws ctr stream "
+                                  "res_H res_W res_stride", defaults=(0, 0, 0))
 
 
 def _family_table(families) -> dict:
@@ -645,8 +650,9 @@ def pack_pw_f32(kernel_hwio: np.ndarray) -> np.ndarray:
 
 
 def pack_conv_f32(kernel_hwio: np.ndarray, bias: np.ndarray, stride: int, pads, device,
-                  row_align: int = 256) -> PackedConv:
-    """[Npad][Kpad] fp32 weights, k = (kh, kw, ci) with ci innermost; no channel padding."""
+                  row_align: int = 256, res_stride: int = 0) -> PackedConv:
+    """[Npad][Kpad] fp32 weights, k = (kh, kw, ci) with ci innermost; no channel padding.  `res_stride` > 1:
+    the conv's fused residual is sampled every `res_stride` pixels from a larger map (PackedConv.res_stride)."""
     kh, kw, cin, cout = kernel_hwio.shape
     K = kh * kw * cin
     Kpad = int(math.ceil(K / F32_BK) * F32_BK)
@@ -656,7 +662,8 @@ def pack_conv_f32(kernel_hwio: np.ndarray, bias: np.ndarray, stride: int, pads, 
     (pt, pb), (pl, pr) = pads
     pc = PackedConv(w=torch.from_numpy(wt).to(device=device).contiguous(),
                     bias=torch.from_numpy(np.ascontiguousarray(bias, np.float32)).to(device),
-                    kh=kh, kw=kw, cin=cin, cout=cout, stride=stride, pad_t=pt, pad_l=pl, pad_b=pb, pad_r=pr)
+                    kh=kh, kw=kw, cin=cin, cout=cout, stride=stride, pad_t=pt, pad_l=pl, pad_b=pb, pad_r=pr,
+                    res_stride=int(res_stride))
     if wino_supported(pc):
         pc.wino = torch.from_numpy(wino_pack_np(kernel_hwio)).to(device=device).contiguous()
     if wino4s_supported(pc):
@@ -721,7 +728,7 @@ def _f32_tile_launch(c: ConvCall) -> None:
     kernels().conv_f32_forward(ptr(c.x), ptr(pc.w), ptr(pc.bias), ptr(c.residual), ptr(c.out), c.ws, c.B, c.H, c.W,
                                pc.cin, c.OH, c.OW, N, pc.kh, pc.kw, pc.stride, pc.pad_t, pc.pad_l, pc.K, pc.Kpad,
                                c.relu, c.ks, c.cfg, stream_handle(c.stream), c.ctr, ptr(c.out2), int(pc.n_split),
-                               c.relu2)
+                               c.relu2, c.res_H, c.res_W, c.res_stride)
 
 
 def _f32_v1_launch(c: ConvCall) -> None:
@@ -731,7 +738,9 @@ def _f32_v1_launch(c: ConvCall) -> None:
 
 
 def _wino_supported(cfg: int, pc: "PackedConv", residual: bool) -> bool:
-    return pc.wino is not None and wino_supported(pc) and pc.cout % (16 * _WINO_GEOM[cfg][1]) == 0
+    # the Winograd epilogues index the residual by output row: no sampled residual
+    return (pc.wino is not None and wino_supported(pc) and pc.cout % (16 * _WINO_GEOM[cfg][1]) == 0
+            and not (residual and pc.res_stride > 1))
 
 
 def _wino_units(cfg: int, B: int, H: int, W: int, pc: "PackedConv"):
@@ -827,7 +836,7 @@ def _pw_f32_launch(c: ConvCall) -> None:
         raise ValueError(f"pointwise fp32 config {cfg}: no partial last tile round to split")
     kernels().pw_f32_forward(ptr(c.x), ptr(pc.pwf), ptr(pc.bias), ptr(c.residual), ptr(c.out), M, pc.cin, N, c.relu,
                              PW_F32_CFGS[cfg], stream_handle(c.stream), c.B, c.H, c.W, c.OH, c.OW, pc.stride,
-                             ptr(c.out2), ns, c.relu2)
+                             ptr(c.out2), ns, c.relu2, c.res_H, c.res_W, c.res_stride)
 
 
 def _f32s_units(cfg: int, B: int, H: int, W: int, pc: "PackedConv"):
@@ -845,7 +854,8 @@ def _f32s_launch(c: ConvCall) -> None:
         raise ValueError(f"fp32 1x1 GEMM config {c.cfg}: 4-D input, ksplit 1 or -1")
     kernels().conv_f32_forward(ptr(c.x), ptr(pc.w), ptr(pc.bias), ptr(c.residual), ptr(c.out), c.ws, c.B, c.H, c.W,
                                pc.cin, c.OH, c.OW, pc.cout, 1, 1, pc.stride, 0, 0, pc.K, pc.Kpad, c.relu, c.ks, c.cfg,
-                               stream_handle(c.stream), c.ctr, ptr(c.out2), int(pc.n_split), c.relu2)
+                               stream_handle(c.stream), c.ctr, ptr(c.out2), int(pc.n_split), c.relu2, c.res_H, c.res_W,
+                               c.res_stride)
 
 
 F32_V1 = ConvFamily(tuple(c for c in F32_TILES if c not in F32G_CFGS), lambda cfg, pc, residual: True,
@@ -942,7 +952,10 @@ def conv_forward_f32(x: torch.Tensor, pc: PackedConv, out: torch.Tensor, residua
     as the config's family defines it.  `f32_scratch` gives the `workspace` floats (allocated when absent) and
     the `counters` (int32 zeros; every launch leaves them zero) such a launch needs.
     Dual output (``pc.n_split > 0``, two sibling 1x1 convs packed along N, no residual):
-    channels [0, n_split) go to `out` (activation `relu`), the rest to `out2` (`relu2`)."""
+    channels [0, n_split) go to `out` (activation `relu`), the rest to `out2` (`relu2`).
+    Sampled residual (``pc.res_stride`` = s > 1): `residual` is a [B, res_H, res_W, Cout] map of which every
+    s-th pixel is the output map, and output pixel (oh, ow) adds its pixel (s oh, s ow), whatever the conv's
+    own stride; a family without it reports the conv unsupported."""
     if x.dim() == 2:
         B, H, W, C = x.shape[0], 1, 1, x.shape[1]
     else:
@@ -967,8 +980,20 @@ def conv_forward_f32(x: torch.Tensor, pc: PackedConv, out: torch.Tensor, residua
         raise ValueError("out2 given for a single-output conv")
     elif out.numel() != M * N:
         raise ValueError(f"conv output buffer has {out.numel()} elements, need {M * N}")
-    if residual is not None and (residual.numel() != M * N or residual.dtype != torch.float32
-                                 or not residual.is_contiguous()):
+    res_H = res_W = res_stride = 0
+    if residual is not None and pc.res_stride > 1:
+        # sampled residual: a [B, res_H, res_W, N] map of which output pixel (oh, ow) adds pixel (s oh, s ow)
+        res_stride = int(pc.res_stride)
+        if residual.dim() != 4 or residual.dtype != torch.float32 or not residual.is_contiguous():
+            raise ValueError("a sampled residual must be a contiguous fp32 [B, res_H, res_W, Cout] map")
+        res_H, res_W = int(residual.shape[1]), int(residual.shape[2])
+        if (residual.shape[0] != B or residual.shape[3] != N or -(-res_H // res_stride) != OH
+                or -(-res_W // res_stride) != OW or residual.numel() != B * res_H * res_W * N
+                or B * res_H * res_W >= 2 ** 31):
+            raise ValueError(f"sampled residual {tuple(residual.shape)}: every {res_stride}th pixel must give the "
+                             f"[{B}, {OH}, {OW}, {N}] output map")
+    elif residual is not None and (residual.numel() != M * N or residual.dtype != torch.float32
+                                   or not residual.is_contiguous()):
         raise ValueError("residual must be contiguous fp32 with the output's shape")
     if int(relu) not in (0, 1, 2):
         raise ValueError("conv epilogue activation must be 0 (none), 1 (ReLU) or 2 (ReLU6)")
@@ -982,7 +1007,7 @@ def conv_forward_f32(x: torch.Tensor, pc: PackedConv, out: torch.Tensor, residua
     need = family.scratch(cfg, ksplit, B, H, W, pc)
     ws_ptr, ctr_ptr = _scratch_ptrs(need, workspace, counters, x.device)
     family.launch(ConvCall(x, pc, out, residual, int(relu), out2, int(relu2), cfg, ksplit, B, H, W, OH, OW,
-                           ws_ptr, ctr_ptr, stream))
+                           ws_ptr, ctr_ptr, stream, res_H, res_W, res_stride))
     return out
 
 

@@ -34,7 +34,7 @@ from ..ops import attention as attn_ops
 from ..ops import conv as conv_ops
 from ..ops import eltwise as E
 from ..ops._lib import private_stream
-from .plan import Step, compile_plan, tensor_shape
+from .plan import Step, compact_maps, compile_plan, tensor_shape
 
 TUNING_FILE = Path(__file__).resolve().parent.parent / "tuning" / "gfx950_conv.json"
 _tuning_lock = threading.Lock()
@@ -104,6 +104,8 @@ class SliceExecutor:
         self.precision = precision
         self.fp32 = precision == "fp32"
         self.steps: List[Step] = compile_plan(g, self.outputs, fp32=self.fp32)
+        # tensors this plan produces only on the lattice their readers sample: stored as compact maps
+        self._compact: Dict[str, Tuple[int, int]] = compact_maps(self.steps)
         if not self.fp32:
             grouped = [st.p["conv"] for st in self.steps if st.kind == "gconv"]
             if grouped:
@@ -120,7 +122,8 @@ class SliceExecutor:
 
     # ------------------------------------------------------------ shapes
     def shape_of(self, name: str) -> Tuple[int, ...]:
-        shp = tensor_shape(self.g, name)        # a MultiHeadAttention's `#qkv` / `#ctx` are (1, T, channels) maps
+        # a MultiHeadAttention's `#qkv` / `#ctx` are (1, T, channels) maps
+        shp = tensor_shape(self.g, name, self._compact)
         if len(shp) == 2:
             shp = (1,) + shp                    # a (T, C) token tensor is stored as the (1, T, C) map
         # activations are stored with channels padded to a multiple of 8 (16-byte
@@ -264,7 +267,8 @@ class SliceExecutor:
                     k2, b2 = self._folded(weights, st.p["sibling"])
                     n_split = kf.shape[-1]
                     kf, bf = np.concatenate([kf, k2], axis=-1), np.concatenate([bf, b2])
-                self.packed[i] = conv_ops.pack_conv_f32(kf, bf, st.p["stride"], st.p["pads"], dev)
+                self.packed[i] = conv_ops.pack_conv_f32(kf, bf, st.p["stride"], st.p["pads"], dev,
+                                                        res_stride=st.p.get("res_stride", 0))
                 self.packed[i].n_split = n_split
             elif st.kind == "stem_f32":
                 kf, bf = self._folded(weights, st.p)
@@ -1083,5 +1087,7 @@ class SliceExecutor:
         lines = []
         for i, st in enumerate(self.steps):
             extra = f" cfg={self.cfg[i]}" if i in self.cfg else ""
+            if st.p.get("subsample"):            # produced on the lattice its stride-s readers sample
+                extra += f" subsample={st.p['subsample']} -> {st.p['out_hw'][0]}x{st.p['out_hw'][1]}"
             lines.append(f"{i:3d} {st.kind:8s} {st.out:28s} <- {st.ins}{extra}")
         return "\n".join(lines)

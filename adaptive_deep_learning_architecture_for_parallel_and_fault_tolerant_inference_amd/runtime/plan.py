@@ -62,6 +62,10 @@ kernels:
 Fusion never hides a tensor that the slice must emit or that another layer
 consumes, so any cut (including the multi-tensor frontier of BASELINE
 config 2) is executable.
+
+fp32 device plan only: a ``conv`` output that nothing but stride-s 1x1 convs read is produced only at the pixels
+they sample (`subsample_lattice`: `p["subsample"]`, the compact map `p["out_hw"]`, `compact_maps`); it keeps its
+name and kind, and stays full size wherever a cut or an output names it.
 """
 from __future__ import annotations
 
@@ -81,10 +85,19 @@ class Step:
     p: Dict = field(default_factory=dict)
 
 
-def tensor_shape(g: Graph, name: str) -> tuple:
+def compact_maps(steps: List["Step"]) -> Dict[str, tuple]:
+    """{tensor: (rows, columns)} of the tensors a plan produces only on the lattice its readers sample
+    (`subsample_lattice`): the per-plan override `tensor_shape` takes."""
+    return {st.out: tuple(st.p["out_hw"]) for st in steps if st.p.get("subsample")}
+
+
+def tensor_shape(g: Graph, name: str, compact: Optional[Dict[str, tuple]] = None) -> tuple:
     """Per-image shape of a plan tensor: the layer's own, or for the two internal tensors of a
     MultiHeadAttention layer (`n#qkv`, `n#ctx`) a (1, T, channels) token map; those of a window attention
-    layer keep its (H, W) map."""
+    layer keep its (H, W) map.  `compact` (`compact_maps` of the plan in force): the tensors that plan stores
+    as the (ceil(H / s), ceil(W / s), C) map of the pixels its readers sample."""
+    if compact and name in compact:
+        return tuple(compact[name]) + (g.layers[name].out_shape[-1],)
     base, _, tag = name.partition("#")
     L = g.layers[base]
     if tag in ("qkv", "ctx") and L.op == "winattn":     # a window attention's stay (H, W, channels) maps
@@ -549,6 +562,9 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
             steps = _fuse_stem_f32(g, steps, outset)
         if os.environ.get("ADAPT_FUSED_PAIR_F32", "1") == "1":
             steps = fuse_pairs(g, steps, outset, fp32=True)
+        # ADAPT_NO_SUBSAMPLE=1 keeps every tensor at full size (A/B runs, tests)
+        if os.environ.get("ADAPT_NO_SUBSAMPLE", "0") != "1":
+            steps = subsample_lattice(g, steps, outset)
         if os.environ.get("ADAPT_NO_SIBLINGS", "0") != "1":
             steps = merge_siblings(steps)
         return steps
@@ -695,6 +711,95 @@ def merge_siblings(steps: List[Step]) -> List[Step]:
                     break
         out.append(st)
     return out
+
+
+_NO_PADS = ((0, 0), (0, 0))
+
+
+def subsample_lattice(g: Graph, steps: List[Step], outset: Set[str]) -> List[Step]:
+    """A tensor that is only ever sampled on a lattice is produced only on that lattice (fp32 device plan).
+
+    Keras ResNet v1 puts the stride 2 of stages 3-5 on the two 1x1 convs ``conv{s}_block1_0_conv`` and
+    ``conv{s}_block1_1_conv``: they read pixels (2i, 2j) of the previous stage's last ``_out`` tensor, so 3/4 of
+    that tensor is computed, added to its residual, written and never read.  When every reader of a tensor T
+    is ``ins[0]`` of a pad-free 1x1 conv with one common stride s > 1, and T's producer P is a pad-free 1x1 /
+    stride-1 conv (a fused residual and any activation allowed), then "conv, keep pixels (s i, s j)" is the
+    stride-s conv of P's input:
+
+    * P becomes that stride-s conv (`p["stride"] = p["subsample"] = s`) and writes the compact
+      (ceil(H / s), ceil(W / s)) map `p["out_hw"]` (`compact_maps` / `tensor_shape`);
+    * its residual stays the full-resolution tensor, read at the same pixels (`p["res_stride"] = s`);
+    * the readers become stride-1 convs of the compact map (`p["in_subsample"] = s` records it), which
+      `merge_siblings` merges as before.
+
+    T keeps its name and kind.  A T the slice emits (an output or a cut frontier), a T some step takes as
+    its residual, a reader of another kind, stride or padding: any of these keeps T full size."""
+    for P in steps:
+        p, T = P.p, P.out
+        if (P.kind != "conv" or p.get("kernel") != (1, 1) or p.get("stride") != 1 or p.get("pads") != _NO_PADS
+                or p.get("sibling") or p.get("out2") or p.get("packed_input") or p.get("mha")
+                or T in outset or T not in g.layers or len(g.layers[T].out_shape) != 3):
+            continue
+        readers = [st for st in steps if T in st.ins]
+        if not readers or any(st.kind != "conv" or st.ins[0] != T or T in st.ins[1:]
+                              or st.p.get("kernel") != (1, 1) or st.p.get("pads") != _NO_PADS
+                              or st.p.get("packed_input") or st.p.get("sibling") for st in readers):
+            continue
+        strides = {st.p.get("stride") for st in readers}
+        if len(strides) != 1:
+            continue
+        s = strides.pop()
+        if not isinstance(s, int) or s <= 1:
+            continue
+        h, w = g.layers[T].out_shape[:2]
+        p["stride"] = p["subsample"] = s
+        p["out_hw"] = (-(-h // s), -(-w // s))
+        if p.get("residual"):
+            p["res_stride"] = s
+        for st in readers:
+            st.p["stride"] = 1
+            st.p["in_subsample"] = s
+        _subsample_front_3x3(g, steps, outset, P, s)
+    return steps
+
+
+# (input channels, H, W) of the 3x3 convs in front of a subsampled 1x1 that are strided too by default.  Empty:
+# on ResNet-50 at batch 32 the direct stride-2 3x3 measured faster in the whole graph than the full-map Winograd
+# conv on all three stages, (64, 56, 56), (128, 28, 28) and (256, 14, 14) (BASELINE.md Round 17), but the suite
+# pins every ResNet-50 3x3 to a Winograd kernel (tests/test_fp32_gpu.py), so taking them is left to a change that
+# also moves that test.  ADAPT_SUBSAMPLE_3X3=1 takes every such 3x3, =0 none, and a list such as
+# 64x56x56,256x14x14 exactly those (per-stage A/B runs).
+SUBSAMPLE_3X3_MEASURED: Set[tuple] = set()
+
+
+def _subsample_front_3x3(g: Graph, steps: List[Step], outset: Set[str], P: Step, s: int) -> None:
+    """One step back from a subsampled 1x1 `P`: the 3x3 / stride-1 / pad-1 conv Q whose output only P reads
+    needs only outputs (s i, s j) too.  It becomes a stride-s 3x3 with top / left pad 1 and the bottom / right
+    pad that makes its last sampled output the full conv's (0 for even H at s = 2); P then reads a dense compact
+    x at stride 1 and still samples its residual (`res_stride` is independent of the conv's stride).  The
+    stride-s 3x3 leaves the Winograd kernels for the direct tile kernels; which 3x3s are taken:
+    SUBSAMPLE_3X3_MEASURED / ADAPT_SUBSAMPLE_3X3."""
+    mode = os.environ.get("ADAPT_SUBSAMPLE_3X3", "auto")
+    cand = [st for st in steps if st.out == P.ins[0]]
+    if mode == "0" or len(cand) != 1:
+        return
+    Q = cand[0]
+    q = Q.p
+    if (Q.kind != "conv" or q.get("kernel") != (3, 3) or q.get("stride") != 1 or q.get("pads") != ((1, 1), (1, 1))
+            or q.get("residual") or q.get("sibling") or q.get("out2") or q.get("packed_input")
+            or Q.out in outset or Q.out not in g.layers or [st for st in steps if Q.out in st.ins] != [P]):
+        return
+    h, w = g.layers[Q.out].out_shape[:2]
+    cin = g.layers[Q.ins[0].split("#")[0]].out_shape[-1]
+    chosen = SUBSAMPLE_3X3_MEASURED if mode == "auto" else {tuple(int(v) for v in t.split("x"))
+                                                           for t in mode.split(",") if "x" in t}
+    if mode != "1" and (cin, h, w) not in chosen:
+        return
+    oh, ow = P.p["out_hw"]
+    q["stride"] = q["subsample"] = s
+    q["pads"] = ((1, max(0, s * (oh - 1) + 2 - h)), (1, max(0, s * (ow - 1) + 2 - w)))
+    q["out_hw"] = (oh, ow)
+    P.p["stride"] = 1
 
 
 STEM_MAX_OW = 112     # csrc/kernels/stem.hip ST_OWMAX

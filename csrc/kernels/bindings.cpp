@@ -194,14 +194,16 @@ PYBIND11_MODULE(_C, m) {
   });
   m.def("pw_f32_supported", &adapt::pw_f32_supported);
   m.def("pw_f32_forward", [](u64 x, u64 w, u64 bias, u64 res, u64 out, int M, int K, int N, int relu, int bm, u64 s,
-                             int B, int H, int W, int OH, int OW, int stride, u64 out2, int n_split, int relu2) {
+                             int B, int H, int W, int OH, int OW, int stride, u64 out2, int n_split, int relu2,
+                             int res_H, int res_W, int res_stride) {
     adapt::PwF32Params p{P<const float>(x), P<const float>(w), P<const float>(bias), P<const float>(res), P<float>(out),
                          M, K, N, relu, B, H, W, OH, OW, stride, P<float>(out2), n_split, relu2};
+    p.res_H = res_H; p.res_W = res_W; p.res_stride = res_stride;
     check(adapt::pw_f32_forward(p, bm, S(s)), "pw_f32_forward");
   }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("res"), py::arg("out"), py::arg("M"), py::arg("K"),
      py::arg("N"), py::arg("relu"), py::arg("bm"), py::arg("s"), py::arg("B"), py::arg("H"), py::arg("W"),
      py::arg("OH"), py::arg("OW"), py::arg("stride"), py::arg("out2") = 0, py::arg("n_split") = 0,
-     py::arg("relu2") = 0);
+     py::arg("relu2") = 0, py::arg("res_H") = 0, py::arg("res_W") = 0, py::arg("res_stride") = 0);
   m.def("pw_f32_fpw", &adapt::pw_f32_fpw);
   m.def("wino4s_forward", [](u64 x, u64 u, u64 bias, u64 out, u64 ws, int B, int H, int W, int C, int N, int relu,
                              int ksplit, int cfg, u64 s, u64 counters) {
@@ -257,17 +259,19 @@ PYBIND11_MODULE(_C, m) {
   m.def("conv_f32_forward", [](u64 x, u64 w, u64 bias, u64 res, u64 out, u64 ws, int B, int H, int W, int Cin,
                                int OH, int OW, int N, int KH, int KW, int stride, int pad_t, int pad_l, int K,
                                int Kpad, int relu, int ksplit, int cfg, u64 s, u64 counters, u64 out2, int n_split,
-                               int relu2) {
+                               int relu2, int res_H, int res_W, int res_stride) {
     py::gil_scoped_release nogil;
     check(adapt::conv_f32_forward(P<const float>(x), P<const float>(w), P<const float>(bias), P<const float>(res),
                                   P<float>(out), P<float>(ws), B, H, W, Cin, OH, OW, N, KH, KW, stride, pad_t, pad_l,
-                                  K, Kpad, relu, ksplit, cfg, S(s), P<int>(counters), P<float>(out2), n_split, relu2),
+                                  K, Kpad, relu, ksplit, cfg, S(s), P<int>(counters), P<float>(out2), n_split, relu2,
+                                  res_H, res_W, res_stride),
           "conv_f32_forward");
   }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("res"), py::arg("out"), py::arg("ws"), py::arg("B"),
      py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("OH"), py::arg("OW"), py::arg("N"), py::arg("KH"),
      py::arg("KW"), py::arg("stride"), py::arg("pad_t"), py::arg("pad_l"), py::arg("K"), py::arg("Kpad"),
      py::arg("relu"), py::arg("ksplit"), py::arg("cfg"), py::arg("s"), py::arg("counters") = 0,
-     py::arg("out2") = 0, py::arg("n_split") = 0, py::arg("relu2") = 0);
+     py::arg("out2") = 0, py::arg("n_split") = 0, py::arg("relu2") = 0, py::arg("res_H") = 0, py::arg("res_W") = 0,
+     py::arg("res_stride") = 0);
   m.def("conv_wino_sk_plan", [](int units, int kc, int mult) {
     int g, it, smax;
     adapt::conv_wino_sk_plan(units, kc, mult, &g, &it, &smax);

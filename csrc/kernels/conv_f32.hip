@@ -167,7 +167,7 @@ __global__ __launch_bounds__(FNT, 2) void conv_f32_kernel(ConvF32Params p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int m = m0 + wm * TM + i * 16 + fq * 4 + r;
-          rres[i][j][r] = (n < p.N && m < p.M) ? p.res[(size_t)m * p.N + n] : 0.f;
+          rres[i][j][r] = (n < p.N && m < p.M) ? p.res[(size_t)res_row(m, p.OH, p.OW, p.res_H, p.res_W, p.res_stride) * p.N + n] : 0.f;
         }
     }
   }
@@ -233,9 +233,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_f32(ConvF32Params p) {
   for (size_t o = blockIdx.x * (size_t)blockDim.x + threadIdx.x; o < total; o += (size_t)gridDim.x * blockDim.x) {
     float v = 0.f;
     for (int s = 0; s < p.ksplit; ++s) v += p.ws[(size_t)s * total + o];
-    const int n = (int)(o % p.N);
+    const int n = (int)(o % p.N), m = (int)(o / p.N);
     if (p.bias) v += p.bias[n];
-    if (p.res) v += p.res[o];
+    if (p.res) v += p.res[(size_t)res_row(m, p.OH, p.OW, p.res_H, p.res_W, p.res_stride) * p.N + n];
     const F32Dst d = f32_dst(p, n);
     d.base[(o / p.N) * d.ld + d.col] = act_relu(v, d.relu);
   }
@@ -266,10 +266,16 @@ hipError_t launch_f32(const ConvF32Params& p, bool pure, bool vec, hipStream_t s
 hipError_t conv_f32_forward(const float* x, const float* w, const float* bias, const float* res, float* out,
                             float* ws, int B, int H, int W, int Cin, int OH, int OW, int N, int KH, int KW,
                             int stride, int pad_t, int pad_l, int K, int Kpad, int relu, int ksplit, int cfg,
-                            hipStream_t s, int* counters, float* out2, int n_split, int relu2) {
+                            hipStream_t s, int* counters, float* out2, int n_split, int relu2, int res_H, int res_W,
+                            int res_stride) {
   ConvF32Params p{x, w, bias, res, out, ws, B, H, W, Cin, OH, OW, N, KH, KW, stride, pad_t, pad_l,
-                  B * OH * OW, K, Kpad, relu, ksplit == 0 ? 1 : ksplit, counters, 0, out2, n_split, relu2};
+                  B * OH * OW, K, Kpad, relu, ksplit == 0 ? 1 : ksplit, counters, 0, out2, n_split, relu2,
+                  res_H, res_W, res_stride};
   if (Kpad % FBK || (p.ksplit > 1 && ws == nullptr)) return hipErrorInvalidValue;
+  // a residual sampled from a larger map (res_row): the tile, ring and big-tile GEMM epilogues take it, the
+  // Winograd kernels do not
+  if (res && (!res_geom_ok(B, OH, OW, res_H, res_W, res_stride) || (res_stride > 1 && cfg >= 80 && cfg < 300)))
+    return hipErrorInvalidValue;
   if (n_split && (n_split % 4 || n_split >= N || !out2 || res || (cfg >= 80 && cfg < 300))) return hipErrorInvalidValue;
   if (cfg >= 300) return gemm_f32s_launch(p, cfg, s);   // big-tile 1x1 GEMM (gemm_f32s.hip)
   if (p.ksplit < 0 && cfg < 80) {

@@ -204,7 +204,8 @@ __device__ __forceinline__ void f32g_tile(const ConvF32Params& p, const float* _
     for (int u = 0; u < (PRE ? IT : 1); ++u) {
       const int row = erow0 + u * RPI, m = m0 + row;
       rpre[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (en < p.N && row < BM && m < p.M) rpre[u] = *(const f32x4*)(p.res + (size_t)m * p.N + en);
+      if (en < p.N && row < BM && m < p.M)
+        rpre[u] = *(const f32x4*)(p.res + (size_t)res_row(m, p.OH, p.OW, p.res_H, p.res_W, p.res_stride) * p.N + en);
     }
   }
 
@@ -393,7 +394,7 @@ __device__ __forceinline__ void f32g_tile(const ConvF32Params& p, const float* _
       if (use_pre) {
         if (g + u < IT) r[u] = rpre[PRE ? g + u : 0];
       } else if (p.res && g + u < IT && row < BM && m < p.M) {
-        r[u] = *(const f32x4*)(p.res + (size_t)m * p.N + en);
+        r[u] = *(const f32x4*)(p.res + (size_t)res_row(m, p.OH, p.OW, p.res_H, p.res_W, p.res_stride) * p.N + en);
       }
     }
 #pragma unroll

@@ -191,7 +191,7 @@ struct GsTile {
 __device__ __forceinline__ void gs_finish(const ConvF32Params& p, int m, int n, f32x4 v) {
   v += *(const f32x4*)(p.bias + n);
   const F32Dst d = f32_dst(p, n);
-  if (p.res) v += *(const f32x4*)(p.res + (size_t)m * p.N + n);
+  if (p.res) v += *(const f32x4*)(p.res + (size_t)res_row(m, p.OH, p.OW, p.res_H, p.res_W, p.res_stride) * p.N + n);
 #pragma unroll
   for (int e = 0; e < 4; ++e) v[e] = act_relu(v[e], d.relu);
   *(f32x4*)(d.base + (size_t)m * d.ld + d.col) = v;
@@ -252,7 +252,8 @@ __device__ __forceinline__ void gs_epilogue_direct(const ConvF32Params& p, char*
     for (int k = 0; k < KS; ++k) {
       const int row = RPP * k + lane / C4, m = m0 + 64 * g + row;
       rv[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (p.res && nok && row < rows && m < mlim) rv[k] = *(const f32x4*)(p.res + (size_t)m * p.N + n);
+      if (p.res && nok && row < rows && m < mlim)
+        rv[k] = *(const f32x4*)(p.res + (size_t)res_row(m, p.OH, p.OW, p.res_H, p.res_W, p.res_stride) * p.N + n);
     }
 #pragma unroll
     for (int i = 4 * g; i < 4 * g + 4 && i < MF; ++i)

@@ -129,7 +129,24 @@ struct ConvF32Params {
   float* out2;      // n_split > 0: two sibling 1x1 convs packed along N; columns >= n_split go to out2
   int n_split;      // (row stride N - n_split, activation relu2), columns < n_split to out (row stride n_split)
   int relu2;
+  // residual geometry: res_stride > 1: res is a B x res_H x res_W x N map and output pixel (b, oh, ow) adds its
+  // pixel (res_stride oh, res_stride ow) -- independent of the conv's own input stride; 0 / 1: res has the
+  // output's shape (row m)
+  int res_H, res_W, res_stride;
 };
+// row of the residual that output row m = (b OH + oh) OW + ow adds (res_stride <= 1: row m itself)
+__device__ __forceinline__ int res_row(int m, int OH, int OW, int res_H, int res_W, int res_stride) {
+  if (res_stride <= 1) return m;
+  const int ohw = OH * OW, img = m / ohw, r = m - img * ohw, oh = r / OW, ow = r - oh * OW;
+  return (img * res_H + oh * res_stride) * res_W + ow * res_stride;
+}
+// host check of a launch's residual geometry: the sampled lattice is exactly the output map and the residual's
+// B res_H res_W rows count in an int (res_row); with res_stride 1 a map that is given must be the output's own
+inline bool res_geom_ok(int B, int OH, int OW, int res_H, int res_W, int res_stride) {
+  if (res_stride <= 1) return res_stride >= 0 && (res_stride == 0 || res_H == 0 || (res_H == OH && res_W == OW));
+  return res_H >= 1 && res_W >= 1 && (res_H + res_stride - 1) / res_stride == OH &&
+         (res_W + res_stride - 1) / res_stride == OW && (long long)B * res_H * res_W <= 0x7fffffffLL;
+}
 void conv_f32g_sk_plan(int tiles, int kt, int mult, int* grid, int* iters);
 struct F32Dst {
   float* base;
@@ -212,7 +229,7 @@ hipError_t conv_f32_forward(const float* x, const float* w, const float* bias, c
                             float* ws, int B, int H, int W, int Cin, int OH, int OW, int N, int KH, int KW,
                             int stride, int pad_t, int pad_l, int K, int Kpad, int relu, int ksplit, int cfg,
                             hipStream_t s, int* counters = nullptr, float* out2 = nullptr, int n_split = 0,
-                            int relu2 = 0);
+                            int relu2 = 0, int res_H = 0, int res_W = 0, int res_stride = 0);
 hipError_t maxpool_f32(const float* x, float* y, int B, int H, int W, int C, int OH, int OW, int K, int S, int pad_t,
                        int pad_l, int pad_zero, hipStream_t s);
 hipError_t gap_f32(const float* x, float* y, int B, int HW, int C, hipStream_t s);
@@ -310,6 +327,7 @@ struct PwF32Params {
   float* out2;         // n_split > 0: columns >= n_split go to out2 (row stride N - n_split, relu2)
   int n_split, relu2;
   unsigned long long* dbg = nullptr;   // streaming kernels: 16 stamps per wave (tools/pw_timeline.py)
+  int res_H = 0, res_W = 0, res_stride = 0;   // residual geometry, as in ConvF32Params (res_row)
 };
 void pw_set_debug(unsigned long long* buf);
 int pw_f32_fpw(int K, int N, int n_split, int bm);

@@ -3,7 +3,8 @@
 //   out = act(x . W + bias (+ res))      x [M][K], W [K][N], K in {64, 128, 256, 512, 1024}
 //
 // (also stride-s 1x1 convs, the input row of output pixel m being pixel (s oh, s ow), and merged
-// sibling convs with a dual output split at a slice boundary)
+// sibling convs with a dual output split at a slice boundary; the residual may be a larger
+// B x res_H x res_W map sampled every res_stride pixels, with its own stride: kernels.h res_row)
 //
 // The fp32 tile GEMMs (conv_f32.hip / conv_f32g.hip) run ResNet's 1x1 convs at 43-51 % MFMA busy
 // (profiles/r3/pmc/pmc_gemm1x1_f32.txt): at K = 128-512 a 64x64 tile has only 4-16 K steps, so every
@@ -80,6 +81,10 @@ __global__ __launch_bounds__(512, 1) void pw_f32_kernel(PwF32Params p) {
     const int img = m / ohw, r = m - img * ohw, oh = r / p.OW, ow = r - oh * p.OW;
     return (img * p.H + oh * p.stride) * p.W + ow * p.stride;
   };
+  // residual row of output pixel m (res_stride > 1: pixel (img, rs oh, rs ow) of the res_H x res_W residual map)
+  auto rrow = [&](int m) __attribute__((always_inline)) {
+    return res_row(m, p.OH, p.OW, p.res_H, p.res_W, p.res_stride);
+  };
   // dual output (merged sibling convs, n_split a multiple of the slice): one destination per block
   const bool second = p.n_split > 0 && slice * NS >= p.n_split;
   float* const dst = second ? p.out2 : p.out;
@@ -100,7 +105,7 @@ __global__ __launch_bounds__(512, 1) void pw_f32_kernel(PwF32Params p) {
     if (has_res && kgi == 0) {                        // the epilogue's residual, a tile ahead like x
 #pragma unroll
       for (int i = 0; i < PF; ++i) {
-        const int m = min(t * BM + i * 16 + fr, p.M - 1);
+        const int m = rrow(min(t * BM + i * 16 + fr, p.M - 1));
 #pragma unroll
         for (int j = 0; j < FPW; ++j)
           nres[j][i] = *(const f32x4*)(p.res + (size_t)m * p.N + ((slice * NWG + wg) * FPW + j) * 16 + fq * 4);
@@ -296,6 +301,11 @@ __global__ __launch_bounds__(256, OCC) void pw_stream_f32_kernel(PwF32Params p, 
     return p.x + (size_t)m * K + h * 16 + fq * 4;
   };
 
+  // residual row of output pixel m: the residual analogue of xptr's mapping, with its own map and stride
+  auto rrow = [&](int m) __attribute__((always_inline)) {
+    return res_row(m, p.OH, p.OW, p.res_H, p.res_W, p.res_stride);
+  };
+
   const int lim = TAIL ? full * nslots : ntiles;      // TAIL: the host guarantees full >= 1
   int t = slot;
   f32x4 ring[D];
@@ -314,9 +324,9 @@ __global__ __launch_bounds__(256, OCC) void pw_stream_f32_kernel(PwF32Params p, 
     const int m = t * 16 + fr;
     f32x4 res[FPW];
     if (has_res) {
+      const int mr = rrow(min(m, p.M - 1));
 #pragma unroll
-      for (int j = 0; j < FPW; ++j)
-        res[j] = *(const f32x4*)(p.res + (size_t)min(m, p.M - 1) * p.N + (cg * FPW + j) * 16 + fq * 4);
+      for (int j = 0; j < FPW; ++j) res[j] = *(const f32x4*)(p.res + (size_t)mr * p.N + (cg * FPW + j) * 16 + fq * 4);
     }
     f32x4 acc[NA][FPW];
 #pragma unroll
@@ -376,7 +386,7 @@ __global__ __launch_bounds__(256, OCC) void pw_stream_f32_kernel(PwF32Params p, 
     v += acc[1];
     v += acc[2];
     v += acc[3];
-    if (has_res) v += *(const f32x4*)(p.res + (size_t)min(m, p.M - 1) * p.N + col);
+    if (has_res) v += *(const f32x4*)(p.res + (size_t)rrow(min(m, p.M - 1)) * p.N + col);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = act_relu(v[e], ACT >= 0 ? ACT : relu);
     if (m < p.M) *(f32x4*)(dst + (size_t)m * ldo + col - cof) = v;
@@ -554,13 +564,15 @@ static hipError_t pw_stream_f32_forward(const PwF32Params& p, int mode, hipStrea
 hipError_t pw_f32_forward(const PwF32Params& p, int bm, hipStream_t s) {
   if (bm >= 1 && bm <= 5) {
     if (p.M < 1 || p.stride < 1 || (p.n_split && (!p.out2 || p.res)) || p.M != p.B * p.OH * p.OW ||
-        (p.stride == 1 && (p.H != p.OH || p.W != p.OW)))
+        (p.stride == 1 && (p.H != p.OH || p.W != p.OW)) ||
+        (p.res && !res_geom_ok(p.B, p.OH, p.OW, p.res_H, p.res_W, p.res_stride)))
       return hipErrorInvalidValue;
     return pw_stream_f32_forward(p, bm, s);
   }
   const int fpw = pw_f32_pick(p.K, p.N, p.n_split, bm);
   if (!fpw || p.M < 1 || p.stride < 1 || (p.n_split && (!p.out2 || p.res)) ||
-      p.M != p.B * p.OH * p.OW || (p.stride == 1 && (p.H != p.OH || p.W != p.OW)))
+      p.M != p.B * p.OH * p.OW || (p.stride == 1 && (p.H != p.OH || p.W != p.OW)) ||
+      (p.res && !res_geom_ok(p.B, p.OH, p.OW, p.res_H, p.res_W, p.res_stride)))
     return hipErrorInvalidValue;
   const int nsl = p.N / (fpw * 16 * (8 / pw_f32_kg(p.K)));
   const int ntiles = (p.M + bm - 1) / bm;

@@ -127,8 +127,20 @@ def run(a):
             torch.cuda._sleep(64)               # closing separator
             torch.cuda.synchronize()
         outs = [st.out] + ([st.p["out2"]] if st.p.get("out2") else [])
-        act = sum(_bytes_of(ex, g, n, a.batch) for n in list(st.ins) + outs)
-        meta.append({"i": i, "kind": st.kind, "out": st.out, "ms": t_ms, "flop": step_flop(g, st, a.batch),
+        flop = step_flop(g, st, a.batch)
+        in_bytes = [_bytes_of(ex, g, n, a.batch) for n in st.ins]
+        if st.p.get("subsample"):
+            # a conv the plan runs only on the lattice its readers sample (runtime/plan.py subsample_lattice): the
+            # graph's layer counts every pixel; of an input that is still a full map (x read with the conv's
+            # stride, the sampled residual) only the sampled pixels are compulsory traffic
+            fh, fw = g.layers[st.out].out_shape[:2]
+            keep = st.p["out_hw"][0] * st.p["out_hw"][1] / (fh * fw)
+            flop = int(flop * keep)
+            in_bytes = [int(nb * keep) if tuple(ex.bufs(0)[n].shape[1:3]) == (fh, fw) else nb
+                        for n, nb in zip(st.ins, in_bytes)]
+        act = sum(in_bytes) + sum(_bytes_of(ex, g, n, a.batch) for n in outs)
+        meta.append({"i": i, "kind": st.kind, "out": st.out, "ms": t_ms, "flop": flop,
+                     "subsample": st.p.get("subsample"),
                      "act_bytes": act, "weight_bytes": _weight_bytes(g, st, 4 if a.dtype == "fp32" else 2),
                      "cfg": ex.cfg.get(i), "wino_flop": _wino_flop(ex, i),
                      "wino4_flop": _wino4_flop(ex, i)})

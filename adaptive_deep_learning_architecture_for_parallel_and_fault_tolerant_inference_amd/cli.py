@@ -57,6 +57,12 @@ def _model(cfg: AdaptConfig):
         # weights: --weights <Keras get_weights() .npz>, else seeded random init
         with open(cfg.model) as f:
             m = Model.from_keras_json(f.read(), seed=cfg.seed)
+    elif cfg.model in _token_models():
+        # a language model takes (T,) token ids: `image` counts only when it is such a shape, `classes` (the
+        # vocabulary) only when it is not the image default
+        default = AdaptConfig()
+        m = resnet(cfg.model, seed=cfg.seed, input_shape=tuple(cfg.image) if len(cfg.image) == 1 else None,
+                   classes=cfg.classes if cfg.classes != default.classes else None)
     else:
         m = resnet(cfg.model, seed=cfg.seed, input_shape=tuple(cfg.image), classes=cfg.classes)
     if cfg.weights:
@@ -66,6 +72,27 @@ def _model(cfg: AdaptConfig):
             g, w = load_model(cfg.weights)
             m = Model(g, w)
     return m
+
+
+def _token_models():
+    from .models.zoo import GPT
+    return GPT
+
+
+def _request(cfg: AdaptConfig, m, rng, uint8: bool = False) -> np.ndarray:
+    """One request batch for model `m`: token ids in [0, V) as float32 where the input feeds an Embedding (the
+    uint8 path is for images and is refused there), else N(0, 1) pixels or uint8 ones, in the configured image
+    shape."""
+    g = m.graph
+    first = [g.layers[c] for c in g.consumers().get(g.input, [])]
+    if first and all(L.op == "embedding" for L in first):
+        if uint8:
+            raise ValueError(f"--uint8 sends images; input {g.input!r} of {g.name} holds token ids")
+        vocab = min(int(L.attrs["input_dim"]) for L in first)
+        return rng.integers(0, vocab, (cfg.batch,) + tuple(g.layers[g.input].out_shape)).astype(np.float32)
+    if uint8:
+        return rng.integers(0, 256, (cfg.batch,) + tuple(cfg.image), dtype=np.uint8)
+    return rng.standard_normal((cfg.batch,) + tuple(cfg.image)).astype(np.float32)
 
 
 def cmd_membership(argv):
@@ -122,10 +149,7 @@ def cmd_serve(argv):
                                       start_new_session=True))
     inq, outq = queue.Queue(cfg.max_inflight * 2), queue.Queue()
     rng = np.random.default_rng(cfg.seed)
-    if a.uint8:
-        x = rng.integers(0, 256, (cfg.batch,) + tuple(cfg.image), dtype=np.uint8)
-    else:
-        x = rng.standard_normal((cfg.batch,) + tuple(cfg.image)).astype(np.float32)
+    x = _request(cfg, m, rng, a.uint8)
     t = threading.Thread(target=d.run_defer, args=(m, cuts, inq, outq), daemon=True)
     start = time.time()
     t.start()
@@ -167,7 +191,7 @@ def cmd_local_infer(argv):
     a = ap.parse_args(argv)
     cfg = _cfg(a)
     m = _model(cfg)
-    x = np.random.default_rng(cfg.seed).standard_normal((cfg.batch,) + tuple(cfg.image)).astype(np.float32)
+    x = _request(cfg, m, np.random.default_rng(cfg.seed))
     m.predict(x, device=a.device)          # build / capture
     start = time.time()
     for _ in range(a.requests):

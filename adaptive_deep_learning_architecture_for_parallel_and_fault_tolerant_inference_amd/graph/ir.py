@@ -53,7 +53,8 @@ OPS = (
     "mha",        # Keras MultiHeadAttention over all positions: num_heads, key_dim, value_dim (absent means key_dim),
                   # use_bias; inputs [query], [query, value] or [query, value, key] in Keras argument order (one input
                   # is self-attention, a missing key means key = value), each (H, W, C) or (T, C); value and key have
-                  # the same token count, their channel counts are their own; output the query's shape
+                  # the same token count, their channel counts are their own; output the query's shape.  causal
+                  # (stored only when True; one input only): Keras' use_causal_mask, query i attends keys j <= i
     "posembed",   # ViT class token + learned position embedding: attrs class_token; (H, W, C) -> (1, T + ct, C)
     "winattn",    # Swin window attention (the project's own layer, Keras class WindowAttention): num_heads, key_dim,
                   # window (M), shift (0 <= s < M), use_bias; (H, W, C) -> (H, W, C), H and W multiples of M.
@@ -61,6 +62,9 @@ OPS = (
     "queries",    # a learned constant tensor (the project's own layer, Keras class LearnedQueries): attrs length N,
                   # dim C, initializer ("normal" | "zeros"); weight embeddings (N, C); the one input supplies only the
                   # batch size; output (1, N, C), the same for every image
+    "embedding",  # Keras Embedding: attrs input_dim (V <= 2**24), output_dim (C); weight embeddings (V, C); input
+                  # (T,) token ids carried as float32 (truncated toward zero, every id exact), output (T, C); an id
+                  # outside [0, V) yields a zero row (TensorFlow's GPU gather; a kernel cannot raise)
     "space_to_depth",  # Swin patch merging's rearrangement (Keras class SpaceToDepth): attrs block (2);
                   # (H, W, C) -> (H/2, W/2, 4C), out[y, x, (2 dx + dy) C + c] = in[2y + dy, 2x + dx, c]: the
                   # concatenation of x[0::2,0::2], x[1::2,0::2], x[0::2,1::2], x[1::2,1::2] (not tf.nn.space_to_depth,
@@ -70,10 +74,11 @@ OPS = (
 # activations the runtime executes (fused into conv / dense / eltwise epilogues,
 # csrc/kernels/common.h ActMode), by their Keras names
 ACTIVATIONS = ("linear", "relu", "relu6", "swish", "silu", "sigmoid", "tanh", "hard_sigmoid", "hard_swish", "gelu",
-               "elu", "selu", "softplus", "leaky_relu")
+               "elu", "selu", "softplus", "leaky_relu", "gelu_tanh")
 # Keras activation name -> kernel ActMode (csrc/kernels/common.h); leaky_relu also takes its slope
 ACT_MODE = {None: 0, "linear": 0, "relu": 1, "relu6": 2, "swish": 3, "silu": 3, "sigmoid": 4, "tanh": 5,
-            "hard_sigmoid": 6, "hard_swish": 7, "gelu": 8, "elu": 9, "selu": 10, "softplus": 11, "leaky_relu": 12}
+            "hard_sigmoid": 6, "hard_swish": 7, "gelu": 8, "elu": 9, "selu": 10, "softplus": 11, "leaky_relu": 12,
+            "gelu_tanh": 13}      # 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))): GPT-2's form
 
 
 def bn_params(weights, name: str) -> Dict:
@@ -259,6 +264,8 @@ class Layer:
             return out + [(f"{self.name}/relative_position_bias_table", ((2 * m - 1) ** 2, h))]
         if self.op == "queries":
             return [(f"{self.name}/embeddings", (int(self.attrs["length"]), int(self.attrs["dim"])))]
+        if self.op == "embedding":
+            return [(f"{self.name}/embeddings", (int(self.attrs["input_dim"]), int(self.attrs["output_dim"])))]
         if self.op == "posembed":
             t, c = _tokens(in_shapes[0]), in_shapes[0][-1]
             ct = 1 if self.attrs.get("class_token") else 0
@@ -297,7 +304,8 @@ class Layer:
             dv = self.attrs.get("value_dim") or d
             _, sk, sv = mha_sources(in_shapes)
             tk = _tokens(sk)
-            return (t * c * h * d + tk * sk[-1] * h * d + tk * sv[-1] * h * dv + t * tk * h * (d + dv)
+            pairs = t * (t + 1) // 2 if self.attrs.get("causal") else t * tk      # (query, key) pairs of the core
+            return (t * c * h * d + tk * sk[-1] * h * d + tk * sv[-1] * h * dv + pairs * h * (d + dv)
                     + t * h * dv * c)
         if self.op == "winattn":                # projections (h d = C in Swin), scores and P V inside M x M windows
             (hh, ww, c), m = in_shapes[0], self.attrs["window"]
@@ -386,6 +394,13 @@ class Graph:
             if _tokens(sk) != _tokens(sv):
                 raise ValueError(f"mha {layer.name!r}: the key has {_tokens(sk)} tokens and the value "
                                  f"{_tokens(sv)}; they must agree")
+            if "causal" in layer.attrs:
+                if layer.attrs["causal"] is not True:
+                    raise ValueError(f"mha {layer.name!r}: causal is stored only when True (got "
+                                     f"{layer.attrs['causal']!r}); leave it out otherwise")
+                if len(layer.inputs) != 1:
+                    raise ValueError(f"mha {layer.name!r}: a causal mask needs one input (self-attention), got "
+                                     f"{len(layer.inputs)} sources")
             osh = layer.attrs.get("output_shape")
             if osh is not None and [int(v) for v in (osh if isinstance(osh, (list, tuple)) else [osh])] != [
                     shapes[0][-1]]:
@@ -398,6 +413,16 @@ class Graph:
                 raise ValueError(f"queries {layer.name!r}: needs one input (the batch size), length >= 1, dim >= 1 "
                                  f"and initializer 'normal' or 'zeros' (got {a.get('length')}, {a.get('dim')}, "
                                  f"{a.get('initializer')!r})")
+        if layer.op == "embedding":
+            shp = self.layers[layer.inputs[0]].out_shape if len(layer.inputs) == 1 else None
+            v, c = int(layer.attrs.get("input_dim", 0)), int(layer.attrs.get("output_dim", 0))
+            if shp is None or len(shp) != 1 or v < 1 or c < 1:
+                raise ValueError(f"embedding {layer.name!r}: needs one (T,) input of token ids (got {shp}), "
+                                 f"input_dim >= 1 and output_dim >= 1 (got {layer.attrs.get('input_dim')}, "
+                                 f"{layer.attrs.get('output_dim')})")
+            if v > 2 ** 24:
+                raise ValueError(f"embedding {layer.name!r}: input_dim={v} exceeds 2**24; token ids are carried as "
+                                 f"float32 and would no longer be exact")
         if layer.op == "winattn":
             shp = self.layers[layer.inputs[0]].out_shape
             a = layer.attrs
@@ -418,8 +443,8 @@ class Graph:
                                  f"H and W (got block {layer.attrs.get('block')}, {shp})")
         if layer.op == "posembed":
             shp = self.layers[layer.inputs[0]].out_shape
-            if len(shp) != 3:
-                raise ValueError(f"posembed {layer.name!r}: needs an (H, W, C) or (1, T, C) input, got {shp}")
+            if len(shp) not in (2, 3):
+                raise ValueError(f"posembed {layer.name!r}: needs an (H, W, C), (1, T, C) or (T, C) input, got {shp}")
         if layer.op == "crop" and layer.out_shape:
             self._infer_shape(layer)                # an empty result is refused even with a given shape
         layer.out_shape = tuple(layer.out_shape) or self._infer_shape(layer)
@@ -471,6 +496,8 @@ class Graph:
             return (1, _tokens(ins[0]) + (1 if a.get("class_token") else 0), ins[0][-1])
         if layer.op == "queries":
             return (1, int(a["length"]), int(a["dim"]))
+        if layer.op == "embedding":
+            return (ins[0][0], int(a["output_dim"]))
         if layer.op == "binary":
             return ins[0]
         if layer.op == "reshape":

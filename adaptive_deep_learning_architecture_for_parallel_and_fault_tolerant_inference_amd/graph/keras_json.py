@@ -70,12 +70,15 @@ def _tensor_name(v):
     return None
 
 
-def _mha_inputs(layer: Dict[str, Any], name: str, cross_attention: bool) -> List[str]:
+def _mha_inputs(layer: Dict[str, Any], name: str, cross_attention: bool,
+                causal_attention: bool = False) -> Tuple[List[str], bool]:
     """The tensors a MultiHeadAttention call attends over, as the `mha` op's inputs: [query] for plain
     self-attention, [query, value] when the key is the value, else [query, value, key].  Keras 2 keeps `value` /
     `key` in the first inbound entry's kwargs, Keras 3 in the node's "kwargs" (or all of them in "args"); no mask,
     no scores returned.  Without `cross_attention` a call whose three tensors are not one is refused by layer
-    name, as it was before the `mha` op took separate sources."""
+    name, as it was before the `mha` op took separate sources.  Also returned: whether the call sets
+    `use_causal_mask` (Keras 2 kwargs, Keras 3 "args" / "kwargs"), which is read under `causal_attention` only, and
+    only for one source: by default it is refused by layer name, as it always was."""
     nodes = layer.get("inbound_nodes") or []
     if len(nodes) != 1:
         raise NotImplementedError(f"layer {name!r} is called {len(nodes)} times (one call per layer)")
@@ -98,13 +101,18 @@ def _mha_inputs(layer: Dict[str, Any], name: str, cross_attention: bool) -> List
                                   f"from_keras_json(..., cross_attention=True) reads it")
     if call.get("attention_mask") is not None:
         raise NotImplementedError(f"{name}: MultiHeadAttention with an attention_mask")
-    if call.get("use_causal_mask"):
-        raise NotImplementedError(f"{name}: MultiHeadAttention with use_causal_mask")
+    causal = bool(call.get("use_causal_mask"))
+    if causal and not causal_attention:
+        raise NotImplementedError(f"{name}: MultiHeadAttention with use_causal_mask; "
+                                  f"from_keras_json(..., causal_attention=True) reads it")
+    if causal and not q == v == k:
+        raise NotImplementedError(f"{name}: MultiHeadAttention with use_causal_mask on separate sources (query "
+                                  f"{q!r}, value {v!r}, key {k!r}); only self-attention takes the causal mask")
     if call.get("return_attention_scores"):
         raise NotImplementedError(f"{name}: MultiHeadAttention with return_attention_scores")
     if q == v == k:
-        return [q]
-    return [q, v] if k == v else [q, v, k]
+        return [q], causal
+    return ([q, v] if k == v else [q, v, k]), causal
 
 
 def _check_mha(cfg: Dict[str, Any], in_shape: Tuple[int, ...], name: str) -> None:
@@ -150,6 +158,8 @@ def _activation(act, name: str):
         act = act.get("config", {}).get("name", act.get("class_name"))
     if act in (None, "linear"):
         return None
+    if act in ("gelu_new", "gelu_approximate"):        # the tanh form under its other names
+        act = "gelu_tanh"
     if act not in ACTIVATIONS and act != "softmax":
         raise NotImplementedError(f"{name}: activation {act!r}")
     return act
@@ -180,6 +190,16 @@ def _layers_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[st
             a["activation"] = act
         return [dw, Layer(name, "conv", [dw.name], a)]
     return [_layer_from_keras(cls, cfg, name, inputs)]
+
+
+def _gelu_form(act, cfg: Dict[str, Any]):
+    """`gelu` with `approximate: true` in the layer's config (or in a Keras 3 serialized activation's) is the
+    tanh form."""
+    approx = cfg.get("approximate")
+    src = cfg.get("activation")
+    if isinstance(src, dict) and isinstance(src.get("config"), dict):
+        approx = approx or src["config"].get("approximate")
+    return "gelu_tanh" if act == "gelu" and approx else act
 
 
 def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str]) -> Layer:
@@ -275,6 +295,11 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
     if cls == "LearnedQueries":                        # the project's own layer (graph/ir.py "queries")
         return Layer(name, "queries", inputs, {"length": int(cfg["length"]), "dim": int(cfg["dim"]),
                                                "initializer": str(cfg.get("initializer", "normal"))})
+    if cls == "Embedding":
+        if cfg.get("mask_zero"):
+            raise NotImplementedError(f"{name}: Embedding with mask_zero=True (masks are not propagated)")
+        return Layer(name, "embedding", inputs, {"input_dim": int(cfg["input_dim"]),
+                                                 "output_dim": int(cfg["output_dim"])})
     if cls == "LayerScale":
         return Layer(name, "layerscale", inputs, {"init_values": float(cfg.get("init_values", 1e-6))})
     if cls == "StochasticDepth":                       # drops whole residual branches in training only
@@ -295,7 +320,7 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
         alpha = cfg.get("alpha", cfg.get("negative_slope", 0.3))
         return Layer(name, "act", inputs, {"fn": "leaky_relu", "alpha": float(alpha)})
     if cls == "Activation":
-        act = _activation(cfg["activation"], name)
+        act = _gelu_form(_activation(cfg["activation"], name), cfg)
         if act is None:
             return Layer(name, "identity", inputs)
         if act == "relu":
@@ -343,7 +368,7 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
     if cls in ("Dropout", "SpatialDropout2D", "GaussianDropout", "GaussianNoise", "ActivityRegularization"):
         return Layer(name, "identity", inputs)
     if cls == "Dense":
-        act = _activation(cfg.get("activation", "linear"), name)
+        act = _gelu_form(_activation(cfg.get("activation", "linear"), name), cfg)
         a = {"units": int(cfg["units"]), "use_bias": bool(cfg.get("use_bias", True))}
         if act:
             a["activation"] = act
@@ -351,11 +376,13 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
     raise NotImplementedError(f"layer {name!r}: Keras class {cls!r} is not supported by the runtime")
 
 
-def from_keras_json(s, cross_attention: bool = False) -> Graph:
+def from_keras_json(s, cross_attention: bool = False, causal_attention: bool = False) -> Graph:
     """Parse ``model.to_json()`` output (str or already-decoded dict) into a Graph.  `cross_attention=True` reads a
     MultiHeadAttention call whose query, value and key are different tensors (the `mha` op's two- and three-input
     forms); by default such a call is refused by layer name, which is what this function has always done and what
-    callers written against it may rely on.  `Model.from_keras_json`, and through it the command line, pass True."""
+    callers written against it may rely on.  `causal_attention=True` likewise reads a self-attention call with
+    `use_causal_mask=True` (the `mha` op's `causal` attribute), refused by layer name by default.
+    `Model.from_keras_json`, and through it the command line, pass True for both."""
     d = json.loads(s) if isinstance(s, (str, bytes)) else s
     if d.get("class_name") not in ("Functional", "Model"):
         raise NotImplementedError(f"only functional models are supported (got {d.get('class_name')!r})")
@@ -364,13 +391,23 @@ def from_keras_json(s, cross_attention: bool = False) -> Graph:
     for ld in cfg["layers"]:
         name = ld.get("name") or ld["config"]["name"]
         mha = ld["class_name"] == "MultiHeadAttention"
-        inputs = _mha_inputs(ld, name, cross_attention) if mha else _inbound_names(ld)
+        inputs, causal = (_mha_inputs(ld, name, cross_attention, causal_attention) if mha
+                          else (_inbound_names(ld), False))
         if mha:
             for i in inputs:
                 if i not in g.layers:
                     raise ValueError(f"layer {name!r} consumes unknown tensor {i!r}")
             _check_mha(ld["config"], g.layers[inputs[0]].out_shape, name)      # against the query
+        if ld["class_name"] == "Embedding":
+            shp = g.layers[inputs[0]].out_shape if len(inputs) == 1 and inputs[0] in g.layers else None
+            il = ld["config"].get("input_length")
+            il = il[0] if isinstance(il, (list, tuple)) and len(il) == 1 else il
+            if shp is not None and il is not None and (len(shp) != 1 or int(il) != shp[0]):
+                raise NotImplementedError(f"{name}: Embedding input_length={ld['config']['input_length']} does not "
+                                          f"match its input {tuple(shp)}")
         for layer in _layers_from_keras(ld["class_name"], ld["config"], name, inputs):
+            if causal:
+                layer.attrs["causal"] = True
             g.add(layer)
         if ld["class_name"] == "LayerNormalization":
             _check_last_axis(ld["config"].get("axis", -1), len(g.layers[name].out_shape) + 1, name)
@@ -442,6 +479,10 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
     elif L.op == "posembed":
         cls = "ClassTokenPositionEmbedding"
         cfg.update(class_token=bool(a.get("class_token")))
+    elif L.op == "embedding":
+        cls = "Embedding"
+        cfg.update(input_dim=a["input_dim"], output_dim=a["output_dim"], mask_zero=False,
+                   input_length=g.layers[L.inputs[0]].out_shape[0])
     elif L.op == "queries":
         cls = "LearnedQueries"
         cfg.update(length=a["length"], dim=a["dim"], initializer=a.get("initializer", "normal"))
@@ -504,6 +545,8 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
         kw = {"value": [L.inputs[1] if len(L.inputs) > 1 else L.inputs[0], 0, 0]}
         if len(L.inputs) > 2:
             kw["key"] = [L.inputs[2], 0, 0]
+        if a.get("causal"):
+            kw["use_causal_mask"] = True
         inbound = [[[L.inputs[0], 0, 0, kw]]]
     return {"class_name": cls, "config": cfg, "name": L.name, "inbound_nodes": inbound}
 

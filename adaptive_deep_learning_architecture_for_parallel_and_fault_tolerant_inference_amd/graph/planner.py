@@ -139,6 +139,11 @@ def layer_costs(g: Graph, batch: int = 32, hw: Optional[HwModel] = None) -> Dict
             # Uncalibrated: no planner fit includes a model with learned queries
             out[n] = g.tensor_bytes(n, hw.act_bytes) * batch / hw.hbm_bw + hw.launch_s
             continue
+        if L.op == "embedding":
+            # a row gather: its output's bytes and one launch.  Uncalibrated: no planner fit includes a model with
+            # an embedding
+            out[n] = g.tensor_bytes(n, hw.act_bytes) * batch / hw.hbm_bw + hw.launch_s
+            continue
         if L.op == "mha" and len(L.inputs) > 1:
             # separate sources: the MACs of graph/ir.py (each projection over its own source's tokens, the
             # Tq x Tk core, the output projection) and one launch per projection GEMM, the core and the output
@@ -149,7 +154,9 @@ def layer_costs(g: Graph, batch: int = 32, hw: Optional[HwModel] = None) -> Dict
             continue
         # deconv: its true MACs (input pixels x taps x cin x filters, the phase form multiplies no stuffed
         # zeros) against its bytes; upsample / crop have no MACs and cost their input + output traffic.
-        # mha: the MACs of its two projection GEMMs and the T x T core (graph/ir.py); posembed: its traffic.
+        # mha: the MACs of its two projection GEMMs and the T x T core (graph/ir.py); a causal layer's core counts
+        # T (T + 1) / 2 (query, key) pairs there, the tiles its kernel does not skip; uncalibrated: no planner fit
+        # includes a causal model.  posembed: its traffic.
         # winattn: 4 H W C^2 + 2 H W M^2 C MACs (projections and the window-local core); space_to_depth: its traffic
         t = max(2.0 * macs / hw.mfma_flops, byts / hw.hbm_bw) + hw.launch_s
         out[n] = t

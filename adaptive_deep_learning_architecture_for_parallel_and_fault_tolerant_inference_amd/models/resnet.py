@@ -164,6 +164,8 @@ def init_weights(g: Graph, seed: int = 0, layers: Optional[List[str]] = None) ->
             shp = specs[0][1]
             out[specs[0][0]] = (np.zeros(shp, np.float32) if L.attrs.get("initializer", "normal") == "zeros"
                                 else rng.standard_normal(shp).astype(np.float32))
+        elif L.op == "embedding":                  # N(0, 0.02), GPT-2's token table
+            out[specs[0][0]] = (rng.standard_normal(specs[0][1]) * 0.02).astype(np.float32)
         elif L.op == "layerscale":
             # O(1), not Keras' 1e-6: with that every residual branch would vanish from the output
             out[specs[0][0]] = rng.uniform(0.1, 0.3, specs[0][1][0]).astype(np.float32)

@@ -41,7 +41,7 @@ Not from `keras.applications` (models whose output is a map, not a class vector)
 """
 from __future__ import annotations
 
-from typing import Callable, Dict
+from typing import Callable, Dict, Optional
 
 from ..graph.ir import Graph, Layer
 
@@ -725,7 +725,65 @@ def build_detr(name: str = "detr_resnet50", classes: int = DETR_CLASSES, input_s
     return g
 
 
+# --------------------------------------------------------------------- GPT
+# name -> (depth, width, heads, vocabulary, default tokens); micro: same naming / structure, for fast tests (40
+# tokens: one above the attention key tile plus 7, below the query tile)
+GPT = {
+    "gpt2": (12, 768, 12, 50257, 128),
+    "gpt2_medium": (24, 1024, 16, 50257, 128),
+    "gpt2_large": (36, 1280, 20, 50257, 128),
+    "gpt2_xl": (48, 1600, 25, 50257, 128),
+    "gpt_micro": (2, 32, 2, 97, 40),
+}
+GPT_CONTEXT = 1024         # rows of the published position table
+GPT_EPS = 1e-5
+GPT_MLP_RATIO = 4
+
+
+def build_gpt(name: str = "gpt2", classes: Optional[int] = None, input_shape=None,
+              all_positions: bool = False) -> Graph:
+    """GPT-2 (Radford et al. 2019; the published 124M / medium / large / xl) as a flat pre-norm graph, the
+    full-sequence forward pass: the (T,) token ids (carried as float32) through an Embedding, a learned position
+    embedding without a class token, `depth` blocks of LayerNormalization -> causal MultiHeadAttention -> Add and
+    LayerNormalization -> Dense(4C, gelu_tanh) -> Dense(C) -> Add on a (1, T, C) token map, the last token
+    cropped out (`all_positions=True` keeps every token), the final LayerNormalization and `lm_head`, a Dense
+    without bias onto the vocabulary: the next-token logits.  `classes` is the vocabulary.  The position table has
+    the T rows of the built graph; a loader slices the published 1024-row table.  The IR shares no weights, so
+    `lm_head` owns a (C, V) kernel, into which a loader puts the transposed token table: the parameter total
+    counts the table once more than the published figure."""
+    depth, width, heads, vocab, default_tokens = GPT[name]
+    vocab = int(classes or vocab)
+    shape = tuple(input_shape or (default_tokens,))
+    if len(shape) != 1 or not 1 <= shape[0] <= GPT_CONTEXT:
+        raise ValueError(f"{name}: input {shape} is not (T,) token ids with 1 <= T <= {GPT_CONTEXT}")
+    tokens = shape[0]
+    g = Graph(name)
+    x = g.add(Layer("input_1", "input", [], {"shape": shape}))
+    x = g.add(Layer(f"{name}_wte", "embedding", [x], {"input_dim": vocab, "output_dim": width}))
+    x = g.add(Layer(f"{name}_wpe", "posembed", [x], {"class_token": False}))
+
+    def ln(x: str, nm: str) -> str:
+        return g.add(Layer(nm, "layernorm", [x], {"epsilon": GPT_EPS}))
+
+    for i in range(depth):
+        nm = f"{name}_block_{i}"
+        y = g.add(Layer(f"{nm}_attn", "mha", [ln(x, f"{nm}_ln1")],
+                        {"num_heads": heads, "key_dim": width // heads, "use_bias": True, "causal": True}))
+        x = g.add(Layer(f"{nm}_add1", "add", [x, y]))
+        y = g.add(Layer(f"{nm}_mlp_fc1", "dense", [ln(x, f"{nm}_ln2")],
+                        {"units": GPT_MLP_RATIO * width, "activation": "gelu_tanh", "use_bias": True}))
+        y = g.add(Layer(f"{nm}_mlp_fc2", "dense", [y], {"units": width, "use_bias": True}))
+        x = g.add(Layer(f"{nm}_add2", "add", [x, y]))
+    if not all_positions:
+        x = g.add(Layer(f"{name}_last", "crop", [x], {"crop": ((0, 0), (tokens - 1, 0))}))      # the last token
+    x = ln(x, f"{name}_ln_f")
+    g.add(Layer("lm_head", "dense", [x], {"units": vocab, "use_bias": False}))
+    g.output_names = ["lm_head"]
+    return g
+
+
 BUILDERS: Dict[str, Callable[..., Graph]] = {
+    **{n: (lambda n: lambda **kw: build_gpt(n, **kw))(n) for n in GPT},
     **{n: (lambda n: lambda **kw: build_detr(n, **kw))(n) for n in DETR},
     **{n: (lambda n: lambda **kw: build_swin(n, **kw))(n) for n in SWIN},
     **{n: (lambda n: lambda **kw: build_vit(n, **kw))(n) for n in VIT},

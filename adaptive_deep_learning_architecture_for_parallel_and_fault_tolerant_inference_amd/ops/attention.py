@@ -1,8 +1,8 @@
 """Wrappers for the self-attention core (csrc/kernels/attention.hip; csrc/kernels/attention_core.h holds the
 scheme of all three), the attention core with separate query /
 key / value sources (csrc/kernels/cross_attention.hip), Swin's window attention core and its bias packer
-(csrc/kernels/window_attention.hip), and the ViT class token / position embedding and learned-queries kernels
-(csrc/kernels/layers.hip).
+(csrc/kernels/window_attention.hip), and the ViT class token / position embedding, learned-queries and token
+embedding kernels (csrc/kernels/layers.hip).
 
 Shapes, dtypes, strides and the 32-bit index range are checked here before any launch; a shape the kernels do
 not take is an error, never a fall-back to torch.
@@ -30,8 +30,9 @@ def attention_path(key_dim: int, value_dim: int) -> str:
 
 
 def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, tokens: int, heads: int, key_dim: int,
-              value_dim: Optional[int] = None, stream=None) -> torch.Tensor:
-    """out = softmax(Q K^T) V per (image, head).  qkv [..., ld_in] holds batch * tokens rows of [Q | K | V]
+              value_dim: Optional[int] = None, stream=None, causal: bool = False) -> torch.Tensor:
+    """out = softmax(Q K^T) V per (image, head); `causal`: query i attends keys j <= i only (Keras'
+    use_causal_mask), on the kernels' masked instantiations, which skip the key tiles above the diagonal.  qkv [..., ld_in] holds batch * tokens rows of [Q | K | V]
     (head-major inside each part; Q already scaled by 1/sqrt(key_dim)), out [..., ld_out] gets heads * value_dim
     channels per row and zeros in the rest of the row.  fp32 or bf16 activations (both tensors alike); the
     row strides are the last dimensions, the true widths come from heads / key_dim / value_dim."""
@@ -49,7 +50,10 @@ def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, tokens: int, hea
                          f"{h} heads ({d}, {dv})")
     if max(qkv.numel(), out.numel(), B * h * T) >= 2 ** 31:
         raise ValueError("attention: tensors must hold fewer than 2^31 elements (32-bit index math)")
-    fn = kernels().attention_f32 if qkv.dtype == torch.float32 else kernels().attention_bf16
+    if causal:
+        fn = kernels().attention_causal_f32 if qkv.dtype == torch.float32 else kernels().attention_causal_bf16
+    else:
+        fn = kernels().attention_f32 if qkv.dtype == torch.float32 else kernels().attention_bf16
     fn(ptr(qkv), ptr(out), B, T, h, d, dv, int(ld_in), int(ld_out), stream_handle(stream))
     return out
 
@@ -140,6 +144,48 @@ def queries(emb: torch.Tensor, out: torch.Tensor, C: Optional[int] = None, strea
         kernels().queries_f32(ptr(emb), ptr(out), B, N, C, stream_handle(stream))
     else:
         kernels().queries_bf16(ptr(emb), ptr(out), B, N, Cp, C, stream_handle(stream))
+    return out
+
+
+def embedding_table(embeddings, dtype, device=None) -> torch.Tensor:
+    """A Keras Embedding's (V, C) weight as the table the `embedding` kernel gathers from, prepared once: fp32
+    (V, C), or bf16 with rows padded to a multiple of 8 channels and the padding written as zeros."""
+    t = np.ascontiguousarray(embeddings.detach().cpu().numpy() if torch.is_tensor(embeddings) else embeddings,
+                             np.float32)
+    if t.ndim != 2 or t.size == 0:
+        raise ValueError(f"embedding_table: embeddings {t.shape} are not (V, C)")
+    if dtype == torch.float32:
+        res = torch.from_numpy(t)
+    elif dtype == torch.bfloat16:
+        cp = (t.shape[1] + 7) // 8 * 8
+        res = torch.zeros((t.shape[0], cp), dtype=torch.bfloat16)
+        res[:, :t.shape[1]] = torch.from_numpy(t).to(torch.bfloat16)
+    else:
+        raise ValueError(f"embedding_table: fp32 or bf16, got {dtype}")
+    return res.to(device) if device is not None else res
+
+
+def embedding(ids: torch.Tensor, table: torch.Tensor, out: torch.Tensor, stream=None) -> torch.Tensor:
+    """Keras Embedding: out[r] = table[int(ids[r])] for every token id.  ids [B, T] are float32 (the transport
+    moves float tensors; Keras casts a float input to int32) and truncated toward zero; `table` is what
+    `embedding_table` prepared, [V, ld] in the activation dtype with V <= 2**24, so every id is exact; out
+    [B, 1, T, ld] has the table's dtype and row length.  An id outside [0, V), an infinity or a NaN yields a zero
+    row, TensorFlow's GPU gather behaviour: a kernel cannot raise."""
+    if table.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"embedding: fp32 or bf16 table, got {table.dtype}")
+    _chk(ids, torch.float32, "ids"); _chk(table, table.dtype, "table"); _chk(out, table.dtype, "out")
+    if table.dim() != 2 or table.numel() == 0 or ids.numel() == 0:
+        raise ValueError(f"embedding: table{tuple(table.shape)} is not [V, ld], or ids{tuple(ids.shape)} are empty")
+    V, ld, rows = int(table.shape[0]), int(table.shape[1]), int(ids.numel())
+    if V > 2 ** 24:
+        raise ValueError(f"embedding: {V} rows exceed 2**24, beyond which a float32 id is not exact")
+    if out.shape[-1] != ld or out.numel() != rows * ld or (table.dtype == torch.bfloat16 and ld % 8):
+        raise ValueError(f"embedding: out{tuple(out.shape)} does not hold {rows} rows of the table's {ld} elements "
+                         f"(bf16 rows are padded to 8 channels)")
+    if max(table.numel(), out.numel()) >= 2 ** 31:
+        raise ValueError("embedding: tensors must hold fewer than 2^31 elements (32-bit index math)")
+    fn = kernels().embedding_f32 if table.dtype == torch.float32 else kernels().embedding_bf16
+    fn(ptr(ids), ptr(table), ptr(out), rows, V, ld, stream_handle(stream))
     return out
 
 

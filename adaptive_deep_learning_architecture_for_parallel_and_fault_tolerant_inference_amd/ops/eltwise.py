@@ -254,7 +254,7 @@ BIN_OPS = {"add": 0, "sub": 1, "mul": 2, "max": 3, "min": 4, "avg": 5}
 def act(x: torch.Tensor, out: torch.Tensor, mode: int, alpha: float = 0.3, stream=None) -> torch.Tensor:
     """Standalone activation (ActMode `mode`; `alpha` = LeakyReLU slope)."""
     _chk(x, name="x"); _chk(out, name="out")
-    if x.numel() != out.numel() or x.numel() % 8 or not 0 <= mode <= 12:
+    if x.numel() != out.numel() or x.numel() % 8 or not 0 <= mode <= max(ACT_MODES.values()):
         raise ValueError("act: bad shapes or mode")
     kernels().act(ptr(x), ptr(out), x.numel(), int(mode), float(alpha), stream_handle(stream))
     return out

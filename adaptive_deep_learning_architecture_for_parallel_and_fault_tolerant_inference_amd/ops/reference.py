@@ -50,6 +50,8 @@ def _act(y: torch.Tensor, act, alpha: float = 0.3) -> torch.Tensor:
         return y * torch.clamp(y + 3.0, 0.0, 6.0) / 6.0
     if act == "gelu":
         return F.gelu(y)
+    if act == "gelu_tanh":
+        return F.gelu(y, approximate="tanh")
     if act == "elu":
         return F.elu(y)
     if act == "selu":
@@ -163,7 +165,11 @@ class ReferenceExecutor:
             q = (torch.einsum("btc,chd->bthd", x, w("query")) + b("query")) * (1.0 / float(a["key_dim"]) ** 0.5)
             k = torch.einsum("btc,chd->bthd", xk, w("key")) + b("key")
             v = torch.einsum("btc,chd->bthd", xv, w("value")) + b("value")
-            p = torch.softmax(torch.einsum("bqhd,bkhd->bhqk", q, k), dim=-1)
+            s = torch.einsum("bqhd,bkhd->bhqk", q, k)
+            if a.get("causal"):                 # Keras _compute_causal_mask: query i attends keys j <= i
+                t = s.shape[-1]
+                s = s.masked_fill(torch.ones(t, t, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
+            p = torch.softmax(s, dim=-1)
             y = torch.einsum("bhqk,bkhd->bqhd", p, v)
             y = torch.einsum("bqhd,hdc->bqc", y, w("attention_output")) + b("attention_output")
             return y.reshape(ins[0].shape)
@@ -215,6 +221,13 @@ class ReferenceExecutor:
             if a.get("class_token"):
                 x = torch.cat([self.w[f"{L.name}/class_token"].expand(x.shape[0], 1, -1), x], dim=1)
             return (x + self.w[f"{L.name}/position_embedding"]).unsqueeze(1)
+        if L.op == "embedding":
+            # the ids truncated toward zero, as Keras casts a float input; an id outside [0, V) yields a zero row
+            table = self.w[f"{L.name}/embeddings"]
+            ids = ins[0].to(torch.float64)
+            ok = (ids > -1) & (ids < table.shape[0])
+            idx = torch.where(ok, ids, torch.zeros_like(ids)).to(torch.int64)
+            return table[idx] * ok.unsqueeze(-1).to(table.dtype)
         if L.op == "queries":
             return self.w[f"{L.name}/embeddings"].expand(ins[0].shape[0], 1, -1, -1)
         if L.op == "relu":

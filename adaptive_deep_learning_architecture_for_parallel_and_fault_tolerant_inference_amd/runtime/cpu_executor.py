@@ -56,7 +56,7 @@ class CpuExecutor:
 
     KINDS = ("conv", "gconv", "dwconv", "maxpool", "avgpool", "bn", "add", "relu", "act", "binary", "affine", "gmp", "copy",
              "concat", "gap", "dense", "softmax", "pad", "layernorm", "deconv", "upsample", "crop", "attention",
-             "posembed", "winattn", "space_to_depth", "groupnorm", "queries")
+             "posembed", "winattn", "space_to_depth", "groupnorm", "queries", "embedding")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], outputs: Optional[Sequence[str]] = None):
         self.g = g
@@ -126,6 +126,8 @@ class CpuExecutor:
                 cls = weights[f"{n}/class_token"].reshape(-1) if st.p["class_token"] else None
                 self.packed[i] = (cls, np.ascontiguousarray(weights[f"{n}/position_embedding"], np.float32))
             elif st.kind == "queries":
+                self.packed[i] = (np.ascontiguousarray(weights[f"{st.p['layer']}/embeddings"], np.float32),)
+            elif st.kind == "embedding":
                 self.packed[i] = (np.ascontiguousarray(weights[f"{st.p['layer']}/embeddings"], np.float32),)
             elif st.kind == "winattn":           # the raw table: the native op does the index and region math
                 self.packed[i] = (np.ascontiguousarray(
@@ -205,7 +207,9 @@ class CpuExecutor:
             m.queries(self.packed[i][0], y, batch)
         elif k == "attention":
             m.attention(ins[0].reshape(-1, ins[0].shape[-1]), y.reshape(-1, y.shape[-1]), batch, int(p["tokens"]),
-                        int(p["heads"]), int(p["key_dim"]), int(p["value_dim"]))
+                        int(p["heads"]), int(p["key_dim"]), int(p["value_dim"]), bool(p.get("causal")))
+        elif k == "embedding":
+            m.embedding(ins[0], self.packed[i][0], y)
         elif k == "winattn":
             m.window_attention(ins[0].reshape(-1, ins[0].shape[-1]), self.packed[i][0], y.reshape(-1, y.shape[-1]),
                                batch, int(p["height"]), int(p["width"]), int(p["window"]), int(p["shift"]),

@@ -80,7 +80,7 @@ class SliceExecutor:
     FP32_KINDS = ("conv", "pair", "dense", "maxpool", "gap", "softmax", "add", "bn", "relu", "pad", "copy",
                   "dwconv", "avgpool", "concat", "act", "binary", "affine", "stem_f32", "gconv", "layernorm",
                   "deconv", "upsample", "crop", "attention", "posembed", "winattn", "space_to_depth", "groupnorm",
-                  "queries")
+                  "queries", "embedding")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], batch: int, device="cuda",
                  outputs: Optional[Sequence[str]] = None, tune: bool = False, num_sets: int = 1,
@@ -140,6 +140,10 @@ class SliceExecutor:
         if (L.op == "input" and base == name and len(L.out_shape) == 3
                 and L.attrs.get("stands_for", "input") == "input"):
             return torch.float32          # user image input (Keras float32 NHWC)
+        if L.op == "input" and base == name and len(L.out_shape) == 1:
+            cons = self.g.consumers().get(base, [])
+            if cons and all(self.g.layers[c].op == "embedding" for c in cons):
+                return torch.float32      # token ids: bf16 would round every id above 256
         if L.op == "softmax" or (L.op == "dense" and len(L.out_shape) == 1
                                  and L.attrs.get("activation") in (None, "linear", "softmax")):
             return torch.float32          # logits / probabilities; a Dense(relu, ...) feeds the next GEMM in bf16
@@ -250,6 +254,9 @@ class SliceExecutor:
             elif st.kind == "queries":           # the (N, C) embeddings, fp32 and true width in both precisions
                 self.packed[i] = torch.tensor(np.ascontiguousarray(weights[f"{st.p['layer']}/embeddings"], np.float32),
                                               device=dev)
+            elif st.kind == "embedding":         # the (V, C) table in the activation dtype, rows padded in bf16
+                self.packed[i] = attn_ops.embedding_table(weights[f"{st.p['layer']}/embeddings"],
+                                                          self.dtype_of(st.out), device=dev)
             elif st.kind == "winattn":           # relative position bias + shift mask, fp32 in both precisions
                 self.packed[i] = attn_ops.window_bias(weights[f"{st.p['layer']}/relative_position_bias_table"],
                                                       st.p["window"], st.p["shift"], device=dev)
@@ -304,6 +311,9 @@ class SliceExecutor:
             elif st.kind == "queries":           # the (N, C) embeddings, fp32 and true width in both precisions
                 self.packed[i] = torch.tensor(np.ascontiguousarray(weights[f"{st.p['layer']}/embeddings"], np.float32),
                                               device=dev)
+            elif st.kind == "embedding":         # the (V, C) table in the activation dtype, rows padded in bf16
+                self.packed[i] = attn_ops.embedding_table(weights[f"{st.p['layer']}/embeddings"],
+                                                          self.dtype_of(st.out), device=dev)
             elif st.kind == "winattn":           # relative position bias + shift mask, fp32 in both precisions
                 self.packed[i] = attn_ops.window_bias(weights[f"{st.p['layer']}/relative_position_bias_table"],
                                                       st.p["window"], st.p["shift"], device=dev)
@@ -344,8 +354,8 @@ class SliceExecutor:
                                  device=self.device)
 
     def _launch_tokens(self, i: int, st: Step, b, stream) -> None:
-        """The attention cores, the position embedding, the learned queries and space-to-depth: one wrapper each
-        for both precisions."""
+        """The attention cores, the position embedding, the learned queries, the token embedding and
+        space-to-depth: one wrapper each for both precisions."""
         if st.kind == "attention" and "tokens_q" in st.p:
             # separate sources: Q, K and V are column slices of the projection buffers (runtime/plan.py)
             p = st.p
@@ -356,7 +366,9 @@ class SliceExecutor:
         elif st.kind == "attention":
             p = st.p
             attn_ops.attention(b[st.ins[0]], b[st.out], self.batch, p["tokens"], p["heads"], p["key_dim"],
-                               p["value_dim"], stream=stream)
+                               p["value_dim"], stream=stream, causal=bool(p.get("causal")))
+        elif st.kind == "embedding":
+            attn_ops.embedding(b[st.ins[0]], self.packed[i], b[st.out], stream=stream)
         elif st.kind == "queries":
             attn_ops.queries(self.packed[i], b[st.out], C=self.g.layers[st.p["layer"]].out_shape[-1], stream=stream)
         elif st.kind == "winattn":
@@ -855,7 +867,7 @@ class SliceExecutor:
                 gm, bt = self.packed[i]
                 E.groupnorm(b[st.ins[0]], gm, bt, b[st.out], self.g.layers[st.p["layer"]].out_shape[-1],
                             st.p["groups"], st.p["eps"], act=st.p["act"], workspace=self._gn_ws, stream=stream)
-            elif k in ("attention", "posembed", "winattn", "space_to_depth", "queries"):
+            elif k in ("attention", "posembed", "winattn", "space_to_depth", "queries", "embedding"):
                 self._launch_tokens(i, st, b, stream)
             elif k == "act":
                 E.act(b[st.ins[0]], b[st.out], st.p["mode"], st.p["alpha"], stream=stream)
@@ -989,7 +1001,7 @@ class SliceExecutor:
             gm, bt = self.packed[i]
             E.groupnorm_f32(b[st.ins[0]], gm, bt, b[st.out], st.p["groups"], st.p["eps"], act=st.p["act"],
                             workspace=self._gn_ws, stream=stream)
-        elif k in ("attention", "posembed", "winattn", "space_to_depth", "queries"):
+        elif k in ("attention", "posembed", "winattn", "space_to_depth", "queries", "embedding"):
             self._launch_tokens(i, st, b, stream)
         elif k == "deconv":
             conv_ops.deconv_forward_f32(b[st.ins[0]], self.packed[i], b[st.out], relu=st.p["relu"], stream=stream)

@@ -30,7 +30,10 @@ kernels:
                tensors gets one projection ``conv`` per distinct source, the parts that share a source side
                by side: `n#qk` and `n#v` (q = k = `src + pos`, v = `src`), `n#q` and `n#kv` (key = value),
                or `n#q`, `n#k`, `n#v`; its ``attention`` step takes those buffers and records `tokens_q`,
-               `tokens_k` and, as `q` / `k` / `v`, (which input, first column) of each part
+               `tokens_k` and, as `q` / `k` / `v`, (which input, first column) of each part.  A causal layer's
+               step carries `"causal": True` (only then: the key is absent otherwise) and runs the masked
+               kernel, which skips the key tiles above the diagonal
+* ``embedding`` a Keras Embedding: a row gather of its (V, C) table by the fp32 token ids of its (T,) input
 * ``posembed`` ViT class token + learned position embedding
 * ``queries``  a LearnedQueries layer: its (N, C) weight broadcast to every image, one copy step
 * ``winattn``  the core of a Swin window attention layer `n`: like ``attention`` three steps, a ``conv``
@@ -459,6 +462,8 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                                    "window": int(a["window"]), "shift": int(a.get("shift", 0)), **head}))
             elif sq == sk == sv:
                 steps.append(Step("attention", n + "#ctx", [n + "#qkv"], [], {"layer": n, "tokens": tokens, **head}))
+                if a.get("causal"):
+                    steps[-1].p["causal"] = True
             else:
                 # separate sources: one projection per distinct source tensor, the parts that share one side by
                 # side ([Q | K] from `src + pos`, [K | V] when the key is the value); the core then reads Q, K and
@@ -492,6 +497,9 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
         elif L.op == "posembed":
             steps.append(Step("posembed", n, [R(L.inputs[0])], [n],
                               {"layer": n, "class_token": bool(a.get("class_token"))}))
+            done.add(n)
+        elif L.op == "embedding":
+            steps.append(Step("embedding", n, [R(L.inputs[0])], [n], {"layer": n}))
             done.add(n)
         elif L.op == "queries":                 # the input only supplies the batch size
             steps.append(Step("queries", n, [R(L.inputs[0])], [n], {"layer": n}))

@@ -83,6 +83,10 @@ class StageCompute:
         self.device = torch.device(device)
         self.inputs = list(g.input_names)
         self.outputs = list(outputs or g.output_names)
+        # inputs that hold token ids (every consumer an Embedding): the uint8 / preprocess ingest is for images
+        cons = g.consumers()
+        self._id_inputs = {n for n in self.inputs
+                           if cons.get(n) and all(g.layers[c].op == "embedding" for c in cons[n])}
         self.gpu = self.device.type == "cuda"
         self.host_ring = max(2, int(host_ring))
         self._pinned: List[Dict[str, torch.Tensor]] = []
@@ -106,6 +110,11 @@ class StageCompute:
         else:
             from .cpu_executor import CpuExecutor
             self.ex = CpuExecutor(g, weights, outputs=self.outputs)
+
+    def _refuse_u8_ids(self, name: str, a) -> None:
+        if name in self._id_inputs and getattr(a, "dtype", None) == np.uint8:
+            raise ValueError(f"input {name!r} holds token ids (it feeds an Embedding): the uint8 / preprocess "
+                             f"ingest path is for images; send the ids as float32")
 
     def _pad(self, t: torch.Tensor, count: int) -> torch.Tensor:
         if t.shape[0] == self.batch:
@@ -144,6 +153,7 @@ class StageCompute:
         from ..ops import eltwise as E
         from ..transport.shm import DevArray
         dst = self.ex.input_buf(name, j)
+        self._refuse_u8_ids(name, a)
         if isinstance(a, DevArray):
             want = np.dtype(np.uint16) if dst.dtype == torch.bfloat16 else np.dtype(np.float32)
             if (a.dtype != want or is_bf16 != (dst.dtype == torch.bfloat16)
@@ -267,6 +277,7 @@ class StageCompute:
             return [r[0] for r in res], [r[1] for r in res]
         feed = {}
         for name, a, b in zip(self.inputs, arrays, bf16_flags):
+            self._refuse_u8_ids(name, a)
             if a.dtype == np.uint8 and self.preprocess != "none":
                 from ..ops.eltwise import preprocess_ref
                 a = preprocess_ref(a, self.preprocess)

@@ -43,7 +43,7 @@ namespace {
 // Activations of the plan (graph/ir.py ACT_MODE; same formulas as
 // csrc/kernels/common.h `act_f`, Keras 2 definitions).
 enum Act { LINEAR = 0, RELU, RELU6, SWISH, SIGMOID, TANH, HARD_SIGMOID, HARD_SWISH, GELU, ELU, SELU, SOFTPLUS,
-           LEAKY_RELU };
+           LEAKY_RELU, GELU_TANH };
 
 inline float act_f(float v, int mode, float alpha) {
   switch (mode) {
@@ -60,6 +60,7 @@ inline float act_f(float v, int mode, float alpha) {
     case SELU: return 1.0507009873554805f * (v > 0.f ? v : 1.6732632423543772f * (std::exp(v) - 1.f));
     case SOFTPLUS: return v > 20.f ? v : std::log1p(std::exp(v));
     case LEAKY_RELU: return v > 0.f ? v : alpha * v;
+    case GELU_TANH: return 0.5f * v * (1.f + std::tanh(0.7978845608f * (v + 0.044715f * v * v * v)));
     default: throw std::invalid_argument("cpu_ops: unknown activation mode");
   }
 }
@@ -431,7 +432,8 @@ void window_attention(const Arr<float>& qkv, const Arr<float>& table, Arr<float>
 // Self-attention core, softmax(Q K^T) V per (image, head): qkv [B*T][ld_in] rows of [Q | K | V] (head-major, Q
 // already scaled by 1/sqrt(d)), out [B*T][ld_out] with heads * dv channels (the rest of a row becomes zero): the
 // argument layout of the GPU op (csrc/kernels/attention.hip).  fp32, the row maximum subtracted before the exponent.
-void attention(const Arr<float>& qkv, Arr<float>& out, int B, int T, int heads, int d, int dv) {
+// causal: query q attends keys k <= q (Keras' use_causal_mask).
+void attention(const Arr<float>& qkv, Arr<float>& out, int B, int T, int heads, int d, int dv, bool causal) {
   need(qkv.ndim() >= 2 && out.ndim() >= 2 && B >= 1 && T >= 1 && heads >= 1 && d >= 1 && dv >= 1, "attention args");
   const long ld_in = qkv.shape(qkv.ndim() - 1), ld_out = out.shape(out.ndim() - 1);
   need(qkv.size() == (long)B * T * ld_in && out.size() == (long)B * T * ld_out && ld_in >= (long)heads * (2 * d + dv)
@@ -450,8 +452,9 @@ void attention(const Arr<float>& qkv, Arr<float>& out, int B, int T, int heads, 
         const float* vb = base + 2 * heads * d + h * dv;
         for (int q = 0; q < T; ++q) {
           const float* qr = base + (size_t)q * ld_in + h * d;
+          const int nk = causal ? q + 1 : T;           // the keys this query attends
           float mx = -INFINITY;
-          for (int k = 0; k < T; ++k) {
+          for (int k = 0; k < nk; ++k) {
             const float* kr = kb + (size_t)k * ld_in;
             float sc = 0.f;
             for (int i = 0; i < d; ++i) sc += qr[i] * kr[i];
@@ -459,13 +462,13 @@ void attention(const Arr<float>& qkv, Arr<float>& out, int B, int T, int heads, 
             mx = std::max(mx, sc);
           }
           float l = 0.f;
-          for (int k = 0; k < T; ++k) {
+          for (int k = 0; k < nk; ++k) {
             p[k] = std::exp(p[k] - mx);
             l += p[k];
           }
           float* orow = yp + ((size_t)b * T + q) * ld_out + h * dv;
           for (int c = 0; c < dv; ++c) orow[c] = 0.f;
-          for (int k = 0; k < T; ++k) {
+          for (int k = 0; k < nk; ++k) {
             const float* vr = vb + (size_t)k * ld_in;
             const float pk = p[k];
             for (int c = 0; c < dv; ++c) orow[c] += pk * vr[c];
@@ -532,6 +535,23 @@ void cross_attention(const Arr<float>& q, const Arr<float>& k, const Arr<float>&
             for (long c = (long)heads * dv; c < ld_out; ++c) yp[((size_t)b * Tq + qi) * ld_out + c] = 0.f;
         }
       }
+  }
+}
+
+// Embedding: out[r] = table[(int)ids[r]], the ids carried as fp32 and truncated toward zero; an id outside [0, V)
+// (or not a number) yields a zero row, as the GPU op (csrc/kernels/layers.hip).  table [V][C], out [rows...][C]
+void embedding(const Arr<float>& ids, const Arr<float>& table, Arr<float>& out) {
+  need(table.ndim() == 2 && ids.size() >= 1 && table.shape(0) >= 1 && table.shape(0) <= (1l << 24) &&
+           out.size() == ids.size() * table.shape(1), "embedding shapes");
+  const long V = table.shape(0), C = table.shape(1);
+  const float *ip = cptr(ids), *tp = cptr(table);
+  float* yp = mptr(out);
+  for (long r = 0; r < (long)ids.size(); ++r) {
+    const float f = ip[r];
+    if (f > -1.f && f < (float)V)
+      std::memcpy(yp + (size_t)r * C, tp + (size_t)(long)f * C, C * sizeof(float));
+    else
+      std::memset(yp + (size_t)r * C, 0, C * sizeof(float));
   }
 }
 
@@ -859,7 +879,8 @@ PYBIND11_MODULE(_cpu, m) {
   m.def("affine", &affine, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("y"), py::arg("act") = 0,
         py::arg("alpha") = 0.3f);
   m.def("attention", &attention, py::arg("qkv"), py::arg("out"), py::arg("B"), py::arg("T"), py::arg("heads"),
-        py::arg("key_dim"), py::arg("value_dim"));
+        py::arg("key_dim"), py::arg("value_dim"), py::arg("causal") = false);
+  m.def("embedding", &embedding, py::arg("ids"), py::arg("table"), py::arg("out"));
   m.def("window_attention", &window_attention, py::arg("qkv"), py::arg("table"), py::arg("out"), py::arg("B"),
         py::arg("H"), py::arg("W"), py::arg("window"), py::arg("shift"), py::arg("heads"), py::arg("key_dim"));
   m.def("space_to_depth", &space_to_depth, py::arg("x"), py::arg("y"));

@@ -4,7 +4,8 @@
 // qkv is [B * T][ld_in] with one row per token holding [Q | K | V], head-major inside each part (Q and K:
 // heads x d, V: heads x dv).  out is [B * T][ld_out].  A group is an image; every address is the image's base
 // plus a row and a column offset: head h's Q at column h d, its K at heads d + h d, its V at 2 heads d + h dv.  The
-// staging table carries the K or V column of each vector, so a staged load needs no select.
+// staging table carries the K or V column of each vector, so a staged load needs no select.  The causal entry
+// points run the core's CAUSAL instantiations on the same layout.
 #include "attention_core.h"
 
 namespace adapt {
@@ -34,7 +35,7 @@ struct SelfSrc {
   __device__ int out_row(const Block& b, int row) const { return b.img * Tn + row; }
 };
 
-template <typename T>
+template <typename T, bool CAUSAL>
 hipError_t attention_launch(const T* qkv, T* out, int B, int Tn, int heads, int d, int dv, int ld_in, int ld_out,
                             hipStream_t s) {
   if (B < 1 || Tn < 1 || heads < 1 || d < 1 || dv < 1) return hipErrorInvalidValue;
@@ -45,7 +46,8 @@ hipError_t attention_launch(const T* qkv, T* out, int B, int Tn, int heads, int 
     return hipErrorInvalidValue;
   const bool mfma = attention_path(d, dv) &&
                     attn::attention_vec4((uintptr_t)qkv | (uintptr_t)out, ld_in | ld_out, (int)sizeof(T));
-  return attn::attention_core_launch(SelfSrc<T>{qkv, Tn, heads, d, dv, ld_in}, out, ld_out, B, mfma, s);
+  return attn::attention_core_launch<T, SelfSrc<T>, CAUSAL>(SelfSrc<T>{qkv, Tn, heads, d, dv, ld_in}, out, ld_out, B,
+                                                            mfma, s);
 }
 
 }  // namespace
@@ -58,12 +60,23 @@ int attention_path(int d, int dv) { return d >= 16 && dv >= 16 && d <= 128 && dv
 
 hipError_t attention_f32(const float* qkv, float* out, int B, int T, int heads, int d, int dv, int ld_in, int ld_out,
                          hipStream_t s) {
-  return attention_launch<float>(qkv, out, B, T, heads, d, dv, ld_in, ld_out, s);
+  return attention_launch<float, false>(qkv, out, B, T, heads, d, dv, ld_in, ld_out, s);
 }
 
 hipError_t attention_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, int d, int dv, int ld_in, int ld_out,
                           hipStream_t s) {
-  return attention_launch<bf16>(qkv, out, B, T, heads, d, dv, ld_in, ld_out, s);
+  return attention_launch<bf16, false>(qkv, out, B, T, heads, d, dv, ld_in, ld_out, s);
+}
+
+// The causal instantiations: query i attends keys j <= i; same arguments and paths
+hipError_t attention_causal_f32(const float* qkv, float* out, int B, int T, int heads, int d, int dv, int ld_in,
+                                int ld_out, hipStream_t s) {
+  return attention_launch<float, true>(qkv, out, B, T, heads, d, dv, ld_in, ld_out, s);
+}
+
+hipError_t attention_causal_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, int d, int dv, int ld_in,
+                                 int ld_out, hipStream_t s) {
+  return attention_launch<bf16, true>(qkv, out, B, T, heads, d, dv, ld_in, ld_out, s);
 }
 
 }  // namespace adapt

@@ -37,6 +37,16 @@
 // barriers of an iteration come before the `active` test, so a wave whose 16 queries are all beyond the count
 // (three of the four at one query) still reaches every barrier: it only helps staging, and leaves after the loop.
 //
+// Causal mask (CAUSAL = true; self-attention only, so the token counts agree): query i attends keys j <= i, Keras'
+// `_compute_causal_mask`.  The key tiles above the diagonal are skipped, not computed and discarded: a block's
+// key loop, and with it the prefetch, ends at the last query of its 64-query tile (a block-uniform bound, so every
+// wave still meets both barriers of every iteration); a wave whose 16 queries all lie before a tile's first key
+// stages its share, passes the barriers and skips the tile's MFMAs, where `active` is tested; in the tiles that
+// straddle the diagonal a key after the lane's query gets the score -inf in the statement that masks the keys
+// beyond the count, so before the maximum is taken (masking the probabilities afterwards lets one large future
+// score underflow every visible term).  exp(-inf - -inf) cannot arise: where the running and the tile maximum
+// are both -inf the exponents are taken against 0.  The plain kernel's lane loops run over k <= q.
+//
 // One loop for every size.  A group of at most 64 tokens would fit in LDS whole; staging Swin's 49 tokens as one
 // 64-key tile (no second pass) measured 2 - 11 % slower than the two-tile loop at d = 32 (BASELINE.md
 // "Round 13"): half of the loads then sit in front of the first MFMA with nothing to hide under.
@@ -85,8 +95,9 @@ __device__ __forceinline__ float ld(const bf16* p) { return bf2f(*p); }
 __device__ __forceinline__ void st(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st(bf16* p, float v) { *p = f2bf(v); }
 
-// DMAX: the head sizes this instantiation holds in registers (d, dv <= DMAX, both multiples of 16)
-template <typename T, int DMAX, typename Src>
+// DMAX: the head sizes this instantiation holds in registers (d, dv <= DMAX, both multiples of 16).  CAUSAL: query
+// i attends keys j <= i (nq() == nk()); every line it adds is under `if constexpr`
+template <typename T, int DMAX, typename Src, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void attention_mfma_kernel(Src src, T* __restrict__ out, int ld_out, int qtiles) {
   constexpr int ND = DMAX / 16;                       // 16-wide slices of d / dv
   constexpr int NST = ATTN_KT * DMAX / 512;           // staged 4-element vectors per thread (K and V together)
@@ -97,8 +108,19 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(Src src, T* __restr
   const int c = lane & 15, g = lane >> 4;
   const int heads = src.heads, d = src.d, dv = src.dv(), Tq = src.nq(), Tk = src.nk();
   int bid = blockIdx.x;
-  const int qt = bid % qtiles;
-  bid /= qtiles;
+  int qt_;
+  if constexpr (CAUSAL) {
+    // a block's work grows with its query tile: the heaviest tiles are dispatched first and the light ones fill
+    // the tail, and the tiles of one weight are consecutive blocks, so they spread over the XCDs alike (with the
+    // tile fastest, XCD x of 8 got tiles {x, x + 8} of 16: 24 key-tile units on the last against 10 on the first)
+    const int gh = gridDim.x / qtiles;
+    qt_ = qtiles - 1 - bid / gh;
+    bid %= gh;
+  } else {
+    qt_ = bid % qtiles;
+    bid /= qtiles;
+  }
+  const int qt = qt_;
   const int h = bid % heads;
   const typename Src::Block b = src.block(bid / heads, h);
   const int ldk = d + ATTN_PAD, ldv = dv + ATTN_PAD;  // LDS row lengths
@@ -144,27 +166,34 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(Src src, T* __restr
   for (int n = 0; n < ND; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.f;                       // l: this lane's keys only, summed over the groups at the end
 
+  // the keys this block walks: all of them, or under the causal mask those up to the last query of its tile.
+  // Block-uniform (from qt, never from wave): every wave passes both barriers of every iteration
+  int kend = Tk;
+  if constexpr (CAUSAL) kend = min(Tk, (qt + 1) * ATTN_QT);
   f32x4 st_[NST];
 #pragma unroll
   for (int j = 0; j < NST; ++j) {
     st_[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (sval[j] && srow[j] < Tk) st_[j] = src.stage(b, sisv[j], srow[j], sgcol[j]);
+    if (sval[j] && srow[j] < kend) st_[j] = src.stage(b, sisv[j], srow[j], sgcol[j]);
   }
-  for (int k0 = 0; k0 < Tk; k0 += ATTN_KT) {          // the same trip count for every wave of the block
+  for (int k0 = 0; k0 < kend; k0 += ATTN_KT) {        // the same trip count for every wave of the block
     __syncthreads();                                  // the previous tile has been read
 #pragma unroll
     for (int j = 0; j < NST; ++j)
       if (sval[j]) *(f32x4*)(smem + sloff[j]) = st_[j];
     __syncthreads();
-    if (k0 + ATTN_KT < Tk) {
+    if (k0 + ATTN_KT < kend) {                        // causal: no tile the block will not use is loaded
 #pragma unroll
       for (int j = 0; j < NST; ++j) {
         st_[j] = f32x4{0.f, 0.f, 0.f, 0.f};           // rows beyond the key count are zeros, never loaded
         const int r = k0 + ATTN_KT + srow[j];
-        if (sval[j] && r < Tk) st_[j] = src.stage(b, sisv[j], r, sgcol[j]);
+        if (sval[j] && r < kend) st_[j] = src.stage(b, sisv[j], r, sgcol[j]);
       }
     }
     if (!active) continue;                            // after both barriers: the wave only helps staging
+    if constexpr (CAUSAL) {
+      if (k0 > q0 + 15) continue;                     // every key of the tile lies after the wave's 16 queries
+    }
     // S^T = K Q^T: s[u][i] = score(key k0 + 16 u + 4 g + i, query c)
     f32x4 s[ATTN_KT / 16];
 #pragma unroll
@@ -186,20 +215,28 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(Src src, T* __restr
     for (int u = 0; u < ATTN_KT / 16; ++u)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        if (k0 + 16 * u + 4 * g + i >= Tk) s[u][i] = -INFINITY;
+        bool masked = k0 + 16 * u + 4 * g + i >= Tk;
+        if constexpr (CAUSAL) masked = masked || k0 + 16 * u + 4 * g + i > qtok;    // before the maximum is taken
+        if (masked) s[u][i] = -INFINITY;
         mx = fmaxf(mx, s[u][i]);
       }
     mx = fmaxf(mx, __shfl_xor(mx, 16));
     mx = fmaxf(mx, __shfl_xor(mx, 32));               // finite: key k0 is in every tile
     const float mn = fmaxf(m, mx);
-    const float alpha = expf(m - mn);                 // 0 on the first tile (m = -inf)
+    float me = mn;                                    // what the exponents are taken against
+    if constexpr (CAUSAL) {
+      // a query that has seen no key yet and sees none in this tile (none with today's tiles: a processed tile
+      // holds key q0 <= qtok): exp(-inf - 0) = 0 for alpha and every p, never exp(-inf - -inf)
+      if (mn == -INFINITY) me = 0.f;
+    }
+    const float alpha = expf(m - me);                 // 0 on the first tile (m = -inf)
     m = mn;
     float ps = 0.f;
 #pragma unroll
     for (int u = 0; u < ATTN_KT / 16; ++u)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        s[u][i] = expf(s[u][i] - mn);                 // masked keys: exp(-inf) = 0
+        s[u][i] = expf(s[u][i] - me);                 // masked keys: exp(-inf) = 0
         ps += s[u][i];
       }
     l = l * alpha + ps;
@@ -251,13 +288,15 @@ __device__ __forceinline__ float dot(const T* __restrict__ a, const T* __restric
 }
 
 // Any head sizes, strides and alignment: one wave per (group, head, query); rows = groups x heads x queries.
-template <typename T, typename Src>
+template <typename T, typename Src, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void attention_plain_kernel(Src src, T* __restrict__ out, int ld_out, int rows) {
   const int lane = threadIdx.x & 63;
   const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= rows) return;                              // the whole wave leaves together; the kernel has no barrier
-  const int heads = src.heads, d = src.d, dv = src.dv(), Tq = src.nq(), Tk = src.nk();
+  const int heads = src.heads, d = src.d, dv = src.dv(), Tq = src.nq();
   const int q = w % Tq, r = w / Tq;
+  int Tk = src.nk();
+  if constexpr (CAUSAL) Tk = min(Tk, q + 1);          // keys k <= q; no barrier, so the trip count may differ per wave
   const int h = r % heads;
   const typename Src::Block b = src.block(r / heads, h);
   const T* qp = src.q(b, q);
@@ -292,22 +331,23 @@ inline bool attention_vec4(uintptr_t ptrs, int strides, int elem_size) {
 }
 
 // Launches `groups` groups of src: the MFMA kernel at the smallest DMAX of 32, 64, 128 that holds both head sizes
-// when `mfma`, else the plain kernel.  The caller has checked the 32-bit ranges.
-template <typename T, typename Src>
+// when `mfma`, else the plain kernel.  The caller has checked the 32-bit ranges.  CAUSAL selects the masked
+// instantiations (the caller has checked nq() == nk()); the default is the kernels as they were.
+template <typename T, typename Src, bool CAUSAL = false>
 hipError_t attention_core_launch(const Src& src, T* out, int ld_out, int groups, bool mfma, hipStream_t s) {
   if (mfma) {
     const int qtiles = (src.nq() + ATTN_QT - 1) / ATTN_QT;
     const dim3 grid(groups * src.heads * qtiles), block(256);
     const int dm = src.d > src.dv() ? src.d : src.dv();
     if (dm <= 32)
-      hipLaunchKernelGGL((attention_mfma_kernel<T, 32, Src>), grid, block, 0, s, src, out, ld_out, qtiles);
+      hipLaunchKernelGGL((attention_mfma_kernel<T, 32, Src, CAUSAL>), grid, block, 0, s, src, out, ld_out, qtiles);
     else if (dm <= 64)
-      hipLaunchKernelGGL((attention_mfma_kernel<T, 64, Src>), grid, block, 0, s, src, out, ld_out, qtiles);
+      hipLaunchKernelGGL((attention_mfma_kernel<T, 64, Src, CAUSAL>), grid, block, 0, s, src, out, ld_out, qtiles);
     else
-      hipLaunchKernelGGL((attention_mfma_kernel<T, 128, Src>), grid, block, 0, s, src, out, ld_out, qtiles);
+      hipLaunchKernelGGL((attention_mfma_kernel<T, 128, Src, CAUSAL>), grid, block, 0, s, src, out, ld_out, qtiles);
   } else {
     const int rows = groups * src.heads * src.nq();
-    hipLaunchKernelGGL((attention_plain_kernel<T, Src>), dim3((rows + 3) / 4), dim3(256), 0, s, src, out, ld_out,
+    hipLaunchKernelGGL((attention_plain_kernel<T, Src, CAUSAL>), dim3((rows + 3) / 4), dim3(256), 0, s, src, out, ld_out,
                        rows);
   }
   return hipGetLastError();

@@ -440,6 +440,16 @@ PYBIND11_MODULE(_C, m) {
     check(adapt::attention_bf16(P<const bf16>(qkv), P<bf16>(out), B, T, heads, d, dv, ld_in, ld_out, S(s)),
           "attention_bf16");
   });
+  m.def("attention_causal_f32", [](u64 qkv, u64 out, int B, int T, int heads, int d, int dv, int ld_in, int ld_out,
+                                   u64 s) {
+    check(adapt::attention_causal_f32(P<const float>(qkv), P<float>(out), B, T, heads, d, dv, ld_in, ld_out, S(s)),
+          "attention_causal_f32");
+  });
+  m.def("attention_causal_bf16", [](u64 qkv, u64 out, int B, int T, int heads, int d, int dv, int ld_in, int ld_out,
+                                    u64 s) {
+    check(adapt::attention_causal_bf16(P<const bf16>(qkv), P<bf16>(out), B, T, heads, d, dv, ld_in, ld_out, S(s)),
+          "attention_causal_bf16");
+  });
   m.def("attention_path", &adapt::attention_path);
   m.def("attention_query_tile", &adapt::attention_query_tile);
   m.def("attention_key_tile", &adapt::attention_key_tile);
@@ -461,6 +471,14 @@ PYBIND11_MODULE(_C, m) {
   });
   m.def("queries_bf16", [](u64 emb, u64 y, int B, int N, int Cp, int C, u64 s) {
     check(adapt::queries_bf16(P<const float>(emb), P<bf16>(y), B, N, Cp, C, S(s)), "queries_bf16");
+  });
+  m.def("embedding_f32", [](u64 ids, u64 table, u64 y, int rows, int V, int ld, u64 s) {
+    check(adapt::embedding_f32(P<const float>(ids), P<const float>(table), P<float>(y), rows, V, ld, S(s)),
+          "embedding_f32");
+  });
+  m.def("embedding_bf16", [](u64 ids, u64 table, u64 y, int rows, int V, int ld, u64 s) {
+    check(adapt::embedding_bf16(P<const float>(ids), P<const bf16>(table), P<bf16>(y), rows, V, ld, S(s)),
+          "embedding_bf16");
   });
   m.def("window_attention_f32", [](u64 qkv, u64 bias, u64 out, int B, int H, int W, int M, int shift, int heads, int d,
                                    int ld_in, int ld_out, u64 s) {

@@ -23,9 +23,10 @@ union V8 {
 // Activations of the fused epilogues and the eltwise kernels (Keras names):
 //   0 linear, 1 relu, 2 relu6 (ReLU(max_value=6)), 3 swish / silu, 4 sigmoid, 5 tanh,
 //   6 hard_sigmoid (Keras 2: clip(0.2x + 0.5)), 7 hard_swish (x * relu6(x + 3) / 6),
-//   8 gelu (erf form), 9 elu, 10 selu, 11 softplus, 12 leaky_relu (slope alpha)
+//   8 gelu (erf form), 9 elu, 10 selu, 11 softplus, 12 leaky_relu (slope alpha),
+//   13 gelu_tanh (0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))), the form GPT-2 was trained with)
 enum ActMode { ACT_LINEAR = 0, ACT_RELU, ACT_RELU6, ACT_SWISH, ACT_SIGMOID, ACT_TANH, ACT_HARD_SIGMOID,
-               ACT_HARD_SWISH, ACT_GELU, ACT_ELU, ACT_SELU, ACT_SOFTPLUS, ACT_LEAKY_RELU };
+               ACT_HARD_SWISH, ACT_GELU, ACT_ELU, ACT_SELU, ACT_SOFTPLUS, ACT_LEAKY_RELU, ACT_GELU_TANH };
 // The MFMA conv epilogues take the ReLU family only (two selects; the wider
 // switch below, inlined into every tile config, doubled their code and compile
 // time): runtime/plan.py runs other activations after a conv as their own step.
@@ -47,6 +48,7 @@ __device__ __forceinline__ float act_f(float v, int mode, float alpha = 0.3f) {
     case ACT_SELU: return 1.0507009873554805f * (v > 0.f ? v : 1.6732632423543772f * (__expf(v) - 1.f));
     case ACT_SOFTPLUS: return v > 20.f ? v : log1pf(__expf(v));
     case ACT_LEAKY_RELU: return v > 0.f ? v : alpha * v;
+    case ACT_GELU_TANH: return 0.5f * v * (1.f + tanhf(0.7978845608f * (v + 0.044715f * v * v * v)));
     default: return v;
   }
 }

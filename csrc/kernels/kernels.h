@@ -409,6 +409,11 @@ hipError_t attention_f32(const float* qkv, float* out, int B, int T, int heads, 
                          hipStream_t s);
 hipError_t attention_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, int d, int dv, int ld_in, int ld_out,
                           hipStream_t s);
+// the same under Keras' causal mask, query i attends keys j <= i: the key tiles above the diagonal are skipped
+hipError_t attention_causal_f32(const float* qkv, float* out, int B, int T, int heads, int d, int dv, int ld_in,
+                                int ld_out, hipStream_t s);
+hipError_t attention_causal_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, int d, int dv, int ld_in,
+                                 int ld_out, hipStream_t s);
 int attention_path(int d, int dv);     // 1: MFMA path, 0: plain kernel
 int attention_query_tile();            // queries per block of the MFMA path
 int attention_key_tile();              // keys per LDS tile of the MFMA path
@@ -452,6 +457,11 @@ hipError_t posembed_bf16(const bf16* x, const float* cls, const float* pos, bf16
 // Cp wide, padding written as zeros
 hipError_t queries_f32(const float* emb, float* y, int B, int N, int C, hipStream_t s);
 hipError_t queries_bf16(const float* emb, bf16* y, int B, int N, int Cp, int C, hipStream_t s);
+// Embedding (layers.hip): y[r] = table[(int)ids[r]] for the `rows` token ids, carried as fp32 and truncated toward
+// zero; an id outside [0, V) (or not a number) yields a zero row.  table [V][ld] and y [rows][ld] in the activation
+// type, rows of ld elements (bf16: padded to 8 channels, the table's padding prepared as zeros); V <= 2^24
+hipError_t embedding_f32(const float* ids, const float* table, float* y, int rows, int V, int ld, hipStream_t s);
+hipError_t embedding_bf16(const float* ids, const bf16* table, bf16* y, int rows, int V, int ld, hipStream_t s);
 bool gconv_f32_mfma_ok(int Cin, int Cout, int G);     // shape rule of the MFMA path
 // mfma: which path to launch (the caller packed w for it); an ineligible shape is an error, never a fall-through
 hipError_t gconv_f32_forward(const GconvF32Params& p, bool mfma, hipStream_t s);

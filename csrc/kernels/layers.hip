@@ -557,4 +557,57 @@ hipError_t queries_bf16(const float* emb, bf16* y, int B, int N, int Cp, int C, 
   return queries_launch<bf16>(emb, y, B, N, C, Cp, s);
 }
 
+// Embedding: y[r] = table[(int)ids[r]], a row gather like the two copies above.  The token ids arrive as fp32 and
+// are truncated toward zero (Keras casts a float input to int32); an id outside [0, V), an infinity or a NaN
+// yields a zero row (TensorFlow's GPU gather), and its table row is never addressed.  table [V][ld] and y [rows][ld]
+// are both in the activation type with rows of ld elements, so a row is copied as it stands, the bf16 layout's
+// padding (prepared as zeros) included.  VEC = 16 bytes per thread where ld and the bases allow, else 1.  Offsets
+// are 32-bit: the launcher refuses a table or an output of 2^31 elements or more, and V above 2^24, beyond
+// which an fp32 id is no longer exact.
+namespace {
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void embedding_kernel(const float* __restrict__ ids, const T* __restrict__ table,
+                                                         T* __restrict__ y, int V, int ld, int total) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int nv = ld / VEC;
+  const int v = idx % nv, row = idx / nv;
+  const float f = ids[row];
+  const bool ok = f > -1.f && f < (float)V;           // false for a NaN; (int)f then lies in [0, V)
+  const int id = ok ? (int)f : 0;
+  const T* tr = table + id * ld + v * VEC;
+  T* yr = y + row * ld + v * VEC;
+  if constexpr (VEC == 1) {
+    yr[0] = ok ? tr[0] : (T)0.f;
+  } else {
+    u32x4 q = u32x4{0u, 0u, 0u, 0u};
+    if (ok) q = *(const u32x4*)tr;
+    *(u32x4*)yr = q;
+  }
+}
+
+template <typename T>
+hipError_t embedding_launch(const float* ids, const T* table, T* y, int rows, int V, int ld, hipStream_t s) {
+  constexpr int VEC = 16 / sizeof(T);
+  if (rows < 1 || V < 1 || V > (1 << 24) || ld < 1 || !ids || !table || !y) return hipErrorInvalidValue;
+  if ((long long)V * ld > 0x7fffffffll || (long long)rows * ld > 0x7fffffffll) return hipErrorInvalidValue;
+  if (ld % VEC == 0 && (((uintptr_t)table | (uintptr_t)y) & 15) == 0) {
+    const int total = rows * (ld / VEC);
+    hipLaunchKernelGGL((embedding_kernel<T, VEC>), dim3(grid_of(total)), dim3(256), 0, s, ids, table, y, V, ld, total);
+  } else {
+    const int total = rows * ld;
+    hipLaunchKernelGGL((embedding_kernel<T, 1>), dim3(grid_of(total)), dim3(256), 0, s, ids, table, y, V, ld, total);
+  }
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t embedding_f32(const float* ids, const float* table, float* y, int rows, int V, int ld, hipStream_t s) {
+  return embedding_launch<float>(ids, table, y, rows, V, ld, s);
+}
+
+hipError_t embedding_bf16(const float* ids, const bf16* table, bf16* y, int rows, int V, int ld, hipStream_t s) {
+  return embedding_launch<bf16>(ids, table, y, rows, V, ld, s);
+}
+
 }  // namespace adapt

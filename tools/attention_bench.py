@@ -13,6 +13,13 @@ The torch paths read Q, K, V from contiguous [B, h, T, d] tensors prepared once 
 Shapes: ViT-Ti / S / B / L at 197 tokens (224 x 224 input) and ViT-B at 577 tokens (384 x 384).
 
     python tools/attention_bench.py [--batch 32] [--reps 20] [--rounds 5]
+
+`--causal` times the causal instantiation instead, on GPT-2's shapes (12 heads of 64 at 128, 512 and 1024 tokens), in
+fp32 and on bf16 activations, against `scaled_dot_product_attention(is_causal=True)` and against the same kernel
+without the mask on the same shape.  The causal launch below the unmasked one is the evidence that the key tiles
+above the diagonal are skipped and not merely masked; TF/s is on the T (T + 1) / 2 pairs the mask leaves.
+
+    python tools/attention_bench.py --causal [--batch 8]
 """
 import argparse
 import os
@@ -95,13 +102,50 @@ def bench(name, B, T, h, d, reps, rounds):
     return t
 
 
+# (name, tokens, heads, key_dim = value_dim): GPT-2 (124M) at its default, a middle and its full context
+CAUSAL_SHAPES = [("gpt2@128", 128, 12, 64), ("gpt2@512", 512, 12, 64), ("gpt2@1024", 1024, 12, 64)]
+
+
+def bench_causal(name, B, T, h, d, reps, rounds):
+    qkv = torch.randn(B * T, 3 * h * d, device="cuda")
+    qkv[:, :h * d] *= d ** -0.5
+    out, full = torch.empty(B * T, h * d, device="cuda"), torch.empty(B * T, h * d, device="cuda")
+    qkv16 = qkv.to(torch.bfloat16)
+    out16, full16 = (torch.empty(B * T, h * d, device="cuda", dtype=torch.bfloat16) for _ in range(2))
+    q, k, v = (qkv[:, i * h * d:(i + 1) * h * d].reshape(B, T, h, d).permute(0, 2, 1, 3).contiguous() for i in range(3))
+
+    def sdpa():
+        return F.scaled_dot_product_attention(q, k, v, scale=1.0, is_causal=True)
+
+    t = interleaved_us({"causal": lambda: A.attention(qkv, out, B, T, h, d, d, causal=True),
+                        "full": lambda: A.attention(qkv, full, B, T, h, d, d),
+                        "causal16": lambda: A.attention(qkv16, out16, B, T, h, d, d, causal=True),
+                        "full16": lambda: A.attention(qkv16, full16, B, T, h, d, d),
+                        "sdpa": sdpa}, reps, rounds)
+    want = sdpa().permute(0, 2, 1, 3).reshape(B * T, h * d)
+    diff = (want - out).abs().max().item()
+    diff16 = (want - out16.float()).abs().max().item()
+    flop = 2.0 * B * (T * (T + 1) // 2) * h * 2 * d
+    print(f"{name:10s} B{B} T{T} h{h} d{d} [{A.attention_path(d, d)}, {-(-T // A.attention_tiles()[1])} key tiles]: "
+          f"causal {t['causal']:8.1f} us ({flop / t['causal'] / 1e6:5.1f} TF/s) | unmasked {t['full']:8.1f} us "
+          f"({t['causal'] / t['full']:4.2f}x) | bf16 act causal {t['causal16']:8.1f} us | unmasked {t['full16']:8.1f} us "
+          f"({t['causal16'] / t['full16']:4.2f}x) | sdpa is_causal {t['sdpa']:8.1f} us ({t['sdpa'] / t['causal']:5.2f}x ours)"
+          f" | max diff vs sdpa {diff:.2e} (bf16 act {diff16:.2e})", flush=True)
+    return t
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--causal", action="store_true", help="the causal kernel on GPT-2 shapes (module docstring)")
     a = ap.parse_args()
     print(torch.cuda.get_device_name(0))
+    if a.causal:
+        for name, T, h, d in CAUSAL_SHAPES:
+            bench_causal(name, a.batch, T, h, d, a.reps, a.rounds)
+        return
     for name, T, h, d in SHAPES:
         bench(name, a.batch, T, h, d, a.reps, a.rounds)
 

@@ -101,6 +101,9 @@ class PackedConv:
     # fp32, > 1: the fused residual is a larger [B, res_H, res_W, cout] map and output pixel (oh, ow) adds its
     # pixel (res_stride oh, res_stride ow), whatever the conv's own stride (runtime/plan.py subsample_lattice)
     res_stride: int = 0
+    # fp32, s > 1: only output pixels (s i, s j) are read afterwards; a launch must write those and may leave the
+    # others as they were (conv_forward_f32; runtime/plan.py `live_lattice`)
+    out_lattice: int = 0
 
     @property
     def K(self) -> int:
@@ -650,9 +653,10 @@ def pack_pw_f32(kernel_hwio: np.ndarray) -> np.ndarray:
 
 
 def pack_conv_f32(kernel_hwio: np.ndarray, bias: np.ndarray, stride: int, pads, device,
-                  row_align: int = 256, res_stride: int = 0) -> PackedConv:
+                  row_align: int = 256, res_stride: int = 0, out_lattice: int = 0) -> PackedConv:
     """[Npad][Kpad] fp32 weights, k = (kh, kw, ci) with ci innermost; no channel padding.  `res_stride` > 1:
-    the conv's fused residual is sampled every `res_stride` pixels from a larger map (PackedConv.res_stride)."""
+    the conv's fused residual is sampled every `res_stride` pixels from a larger map (PackedConv.res_stride).
+    `out_lattice` > 1: only every `out_lattice`-th output pixel is read afterwards (PackedConv.out_lattice)."""
     kh, kw, cin, cout = kernel_hwio.shape
     K = kh * kw * cin
     Kpad = int(math.ceil(K / F32_BK) * F32_BK)
@@ -663,7 +667,7 @@ def pack_conv_f32(kernel_hwio: np.ndarray, bias: np.ndarray, stride: int, pads, 
     pc = PackedConv(w=torch.from_numpy(wt).to(device=device).contiguous(),
                     bias=torch.from_numpy(np.ascontiguousarray(bias, np.float32)).to(device),
                     kh=kh, kw=kw, cin=cin, cout=cout, stride=stride, pad_t=pt, pad_l=pl, pad_b=pb, pad_r=pr,
-                    res_stride=int(res_stride))
+                    res_stride=int(res_stride), out_lattice=int(out_lattice))
     if wino_supported(pc):
         pc.wino = torch.from_numpy(wino_pack_np(kernel_hwio)).to(device=device).contiguous()
     if wino4s_supported(pc):
@@ -818,8 +822,11 @@ def _wino4s_launch(c: ConvCall) -> None:
         raise ValueError(f"Winograd F(4x4) split config {cfg}: 3x3/s1/p1 conv on a 4-D input, N % (16 x WN) == 0, "
                          f"|ksplit| in {wino4s_splits(C)} (fused: <= -2; row-split configs "
                          f"{min(WINO4S_ROW_CFGS)}+: ksplit 1), V / U / slabs / rows below 2 GiB")
+    # a conv whose output is only read on the even lattice: the launch that computes those pixels alone, where
+    # the config has one (whole K); any other launch writes the whole map
+    lattice = 2 if pc.out_lattice == 2 and ks == 1 and kernels().wino4s_lattice_ok(cfg, C, N) else 0
     kernels().wino4s_forward(ptr(c.x), ptr(pc.wino4s), ptr(pc.bias), ptr(c.out), c.ws, c.B, c.H, c.W, C, N,
-                             c.relu, ks, cfg, stream_handle(c.stream), c.ctr)
+                             c.relu, ks, cfg, stream_handle(c.stream), c.ctr, lattice)
 
 
 def _pw_f32_supported(cfg: int, pc: "PackedConv", residual: bool) -> bool:
@@ -955,7 +962,11 @@ def conv_forward_f32(x: torch.Tensor, pc: PackedConv, out: torch.Tensor, residua
     channels [0, n_split) go to `out` (activation `relu`), the rest to `out2` (`relu2`).
     Sampled residual (``pc.res_stride`` = s > 1): `residual` is a [B, res_H, res_W, Cout] map of which every
     s-th pixel is the output map, and output pixel (oh, ow) adds its pixel (s oh, s ow), whatever the conv's
-    own stride; a family without it reports the conv unsupported."""
+    own stride; a family without it reports the conv unsupported.
+    Live lattice (``pc.out_lattice`` = s > 1): the caller reads only output pixels (s i, s j) of the full-size
+    `out`.  A launch must write those pixels and may leave the others as they were; the F(4x4) split configs
+    with an even-lattice build (`wino4s_lattice_ok`, s = 2, whole K) compute and write them alone, every other
+    family and config ignores the field and writes everything."""
     if x.dim() == 2:
         B, H, W, C = x.shape[0], 1, 1, x.shape[1]
     else:

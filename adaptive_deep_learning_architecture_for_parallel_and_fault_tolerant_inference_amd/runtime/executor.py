@@ -67,7 +67,9 @@ def save_tuning(entries: Dict[str, List]) -> None:
 
 
 def conv_key(B, H, W, Cin, pc) -> str:
-    return f"{B}x{H}x{W}x{Cin}|{pc.kh}x{pc.kw}s{pc.stride}p{pc.pad_t}{pc.pad_l}{pc.pad_b}{pc.pad_r}|{pc.cout}"
+    # a conv whose output is only read on a lattice (PackedConv.out_lattice) is a problem of its own: "|l2"
+    lat = f"|l{pc.out_lattice}" if getattr(pc, "out_lattice", 0) > 1 else ""
+    return f"{B}x{H}x{W}x{Cin}|{pc.kh}x{pc.kw}s{pc.stride}p{pc.pad_t}{pc.pad_l}{pc.pad_b}{pc.pad_r}|{pc.cout}{lat}"
 
 
 def _nbytes(shape, dtype) -> int:
@@ -275,7 +277,8 @@ class SliceExecutor:
                     n_split = kf.shape[-1]
                     kf, bf = np.concatenate([kf, k2], axis=-1), np.concatenate([bf, b2])
                 self.packed[i] = conv_ops.pack_conv_f32(kf, bf, st.p["stride"], st.p["pads"], dev,
-                                                        res_stride=st.p.get("res_stride", 0))
+                                                        res_stride=st.p.get("res_stride", 0),
+                                                        out_lattice=st.p.get("live_lattice", 0))
                 self.packed[i].n_split = n_split
             elif st.kind == "stem_f32":
                 kf, bf = self._folded(weights, st.p)
@@ -615,6 +618,8 @@ class SliceExecutor:
             B, H, W, C, OH, OW, pc = self._conv_geom(i)
             if self.fp32:
                 key = "f32|" + conv_key(B, H, W, C, pc)
+                if key not in table and pc.out_lattice > 1:     # no entry of its own: the full conv's (legal: a
+                    key = key.rsplit("|l", 1)[0]                # launch may write the pixels nobody reads)
                 cfg, ks = table[key][:2] if key in table else conv_ops.choose_cfg_f32(B * OH * OW, pc.cout, pc.Kpad)
                 if cfg in conv_ops.WINO4S_F32_CFGS and len(st.ins) > 1:     # the key does not see a fused residual
                     cfg, ks = conv_ops.choose_cfg_f32(B * OH * OW, pc.cout, pc.Kpad)

@@ -768,6 +768,7 @@ def subsample_lattice(g: Graph, steps: List[Step], outset: Set[str]) -> List[Ste
             st.p["stride"] = 1
             st.p["in_subsample"] = s
         _subsample_front_3x3(g, steps, outset, P, s)
+        _mark_live_lattice(g, steps, outset, P, s)
     return steps
 
 
@@ -777,7 +778,48 @@ def subsample_lattice(g: Graph, steps: List[Step], outset: Set[str]) -> List[Ste
 # pins every ResNet-50 3x3 to a Winograd kernel (tests/test_fp32_gpu.py), so taking them is left to a change that
 # also moves that test.  ADAPT_SUBSAMPLE_3X3=1 takes every such 3x3, =0 none, and a list such as
 # 64x56x56,256x14x14 exactly those (per-stage A/B runs).
+# The default path lives one level down instead: a 3x3 left as it is gets `p["live_lattice"] = s`
+# (_mark_live_lattice) and keeps its plan step, its Winograd config family and its full-size buffer, and the
+# F(4x4) split kernels compute only the sampled pixels of it (csrc/kernels/wino4s_f32.hip, even lattice).
 SUBSAMPLE_3X3_MEASURED: Set[tuple] = set()
+
+
+def _front_3x3(g: Graph, steps: List[Step], outset: Set[str], P: Step) -> Optional[Step]:
+    """The 3x3 / stride-1 / pad-1 conv whose output only `P` reads and the slice does not emit, or None."""
+    cand = [st for st in steps if st.out == P.ins[0]]
+    if len(cand) != 1:
+        return None
+    Q = cand[0]
+    q = Q.p
+    if (Q.kind != "conv" or q.get("kernel") != (3, 3) or q.get("stride") != 1 or q.get("pads") != ((1, 1), (1, 1))
+            or q.get("residual") or q.get("sibling") or q.get("out2") or q.get("packed_input")
+            or Q.out in outset or Q.out not in g.layers or [st for st in steps if Q.out in st.ins] != [P]):
+        return None
+    return Q
+
+
+def _shape_list(text: str) -> Set[tuple]:
+    return {tuple(int(v) for v in t.split("x")) for t in text.split(",") if "x" in t}
+
+
+def _mark_live_lattice(g: Graph, steps: List[Step], outset: Set[str], P: Step, s: int) -> None:
+    """The 3x3 in front of a subsampled 1x1 `P` that `_subsample_front_3x3` left as it is: P reads only pixels
+    (s i, s j) of its full-size output, which `p["live_lattice"] = s` records and nothing else of the plan
+    changes.  A launch of that step must write those pixels and may leave the others alone (ops/conv.py
+    conv_forward_f32).  ADAPT_NO_LIVE_LATTICE=1 leaves the mark off; ADAPT_LIVE_LATTICE=64x56x56,256x14x14
+    marks exactly the listed (input channels, H, W) (per-stage A/B runs)."""
+    if os.environ.get("ADAPT_NO_LIVE_LATTICE", "0") == "1":
+        return
+    Q = _front_3x3(g, steps, outset, P)
+    if Q is None:
+        return
+    only = os.environ.get("ADAPT_LIVE_LATTICE")
+    if only is not None:
+        h, w = g.layers[Q.out].out_shape[:2]
+        cin = g.layers[Q.ins[0].split("#")[0]].out_shape[-1]
+        if (cin, h, w) not in _shape_list(only):
+            return
+    Q.p["live_lattice"] = s
 
 
 def _subsample_front_3x3(g: Graph, steps: List[Step], outset: Set[str], P: Step, s: int) -> None:
@@ -788,19 +830,13 @@ def _subsample_front_3x3(g: Graph, steps: List[Step], outset: Set[str], P: Step,
     stride-s 3x3 leaves the Winograd kernels for the direct tile kernels; which 3x3s are taken:
     SUBSAMPLE_3X3_MEASURED / ADAPT_SUBSAMPLE_3X3."""
     mode = os.environ.get("ADAPT_SUBSAMPLE_3X3", "auto")
-    cand = [st for st in steps if st.out == P.ins[0]]
-    if mode == "0" or len(cand) != 1:
+    Q = None if mode == "0" else _front_3x3(g, steps, outset, P)
+    if Q is None:
         return
-    Q = cand[0]
     q = Q.p
-    if (Q.kind != "conv" or q.get("kernel") != (3, 3) or q.get("stride") != 1 or q.get("pads") != ((1, 1), (1, 1))
-            or q.get("residual") or q.get("sibling") or q.get("out2") or q.get("packed_input")
-            or Q.out in outset or Q.out not in g.layers or [st for st in steps if Q.out in st.ins] != [P]):
-        return
     h, w = g.layers[Q.out].out_shape[:2]
     cin = g.layers[Q.ins[0].split("#")[0]].out_shape[-1]
-    chosen = SUBSAMPLE_3X3_MEASURED if mode == "auto" else {tuple(int(v) for v in t.split("x"))
-                                                           for t in mode.split(",") if "x" in t}
+    chosen = SUBSAMPLE_3X3_MEASURED if mode == "auto" else _shape_list(mode)
     if mode != "1" and (cin, h, w) not in chosen:
         return
     oh, ow = P.p["out_hw"]

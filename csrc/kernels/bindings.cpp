@@ -206,7 +206,7 @@ PYBIND11_MODULE(_C, m) {
      py::arg("relu2") = 0, py::arg("res_H") = 0, py::arg("res_W") = 0, py::arg("res_stride") = 0);
   m.def("pw_f32_fpw", &adapt::pw_f32_fpw);
   m.def("wino4s_forward", [](u64 x, u64 u, u64 bias, u64 out, u64 ws, int B, int H, int W, int C, int N, int relu,
-                             int ksplit, int cfg, u64 s, u64 counters) {
+                             int ksplit, int cfg, u64 s, u64 counters, int lattice) {
     adapt::Wino4sParams p{};
     p.x = P<const float>(x);
     p.u = P<const float>(u);
@@ -215,13 +215,15 @@ PYBIND11_MODULE(_C, m) {
     p.ws = P<float>(ws);
     p.B = B; p.H = H; p.W = W; p.C = C; p.N = N; p.relu = relu; p.ksplit = ksplit;
     p.counters = P<int>(counters);
+    p.lattice = lattice;
     check(adapt::wino4s_forward(p, cfg, S(s)), "wino4s_forward");
   }, py::arg("x"), py::arg("u"), py::arg("bias"), py::arg("out"), py::arg("ws"), py::arg("B"), py::arg("H"),
      py::arg("W"), py::arg("C"), py::arg("N"), py::arg("relu"), py::arg("ksplit"), py::arg("cfg"), py::arg("s"),
-     py::arg("counters") = 0);
+     py::arg("counters") = 0, py::arg("lattice") = 0);
   m.def("wino4s_blocks", &adapt::wino4s_blocks);
   m.def("wino4s_set_debug", [](u64 buf) { adapt::wino4s_set_debug(P<unsigned long long>(buf)); });
   m.def("wino4s_ok", &adapt::wino4s_ok);
+  m.def("wino4s_lattice_ok", &adapt::wino4s_lattice_ok);
   m.def("wino4s_ws_floats", &adapt::wino4s_ws_floats);
   m.def("wino4s_ws_floats_cfg", &adapt::wino4s_ws_floats_cfg);
   m.def("wino4s_range_ok", &adapt::wino4s_range_ok);

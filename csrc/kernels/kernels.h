@@ -209,9 +209,14 @@ struct Wino4sParams {
   int* counters;
   int TH, TW, T, TG, KC, order;   // derived by wino4s_forward
   unsigned long long* dbg;        // cfg 299 (measurement): 8 words per wave
+  // 0, or 2: only output pixels (2i, 2j) are read afterwards.  A whole-K launch of a config for which
+  // wino4s_lattice_ok holds then computes and writes those pixels alone, at their places in the full-size map,
+  // and leaves the others as they were; any other launch writes the whole map.
+  int lattice;
 };
 void wino4s_set_debug(unsigned long long* buf);
 bool wino4s_ok(int cfg, int C, int N, int ksplit);
+bool wino4s_lattice_ok(int cfg, int C, int N);   // the config has an even-lattice build (at ksplit 1)
 int wino4s_blocks(int cfg, int B, int H, int W, int N);
 size_t wino4s_ws_floats(int B, int H, int W, int C, int N, int ksplit);
 size_t wino4s_ws_floats_cfg(int cfg, int B, int H, int W, int C, int N, int ksplit);   // row split (238+): V + tr

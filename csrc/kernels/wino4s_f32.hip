@@ -8,6 +8,15 @@
 //                         registers (every lane holds all 36 positions of its (tile, channel) pairs).
 //   3. wino4s_reduce_kernel (split-K only): the splits' partial outputs summed in split order + bias / ReLU.
 //
+// Even lattice (Wino4sParams::lattice == 2, template parameter EVEN): the launch's only reader samples output
+// pixels (2i, 2j), rows and columns 0 and 2 of every tile's Y = A^T M A.  Rows 0 and 2 of A^T are [1 1 1 1 1 0]
+// and [0 1 1 4 4 0] (no m5) and rows 0..4 of B^T end in 0, so those pixels need only positions a, b < 5 of the
+// 6x6 grid and a 5x5 input patch: 25 of the 36 V stores, V / U reads and MFMAs, and 4 of the 16 output pixels,
+// written at their places in the full-size map (the others are left as they were).  Every term of a sampled
+// pixel is one the full launch computes, with the same expressions in the same order: for one config the two
+// launches agree bit for bit there.  V keeps its unit layout (positions 6a + b), so the GEMM's source offsets
+// and the workspace sizes are the full launch's.
+//
 // Row split (cfg ids 238+, template parameter RG): where tiles x channels alone give too few blocks for the
 // chip, a block owns RG of the 6 rows a of the 6x6 position grid instead of a share of K.  The output
 // transform y = A^T M A is separable, so the block runs all of K on its 6 RG accumulators, applies A^T along
@@ -81,6 +90,18 @@ __device__ __forceinline__ void w4s_bt(T& d0, T& d1, T& d2, T& d3, T& d4, T& d5)
   d5 = t5;
 }
 
+// rows 0..4 of B^T on the 5 values they read (their last column is 0): w4s_bt's expressions for d0..d4
+template <typename T>
+__device__ __forceinline__ void w4s_bt5(T& d0, T& d1, T& d2, T& d3, T& d4) {
+  const T s12 = d1 + d2, s34 = d3 + d4, m12 = d1 - d2, m43 = d4 - d3, m13 = d1 - d3, m42 = d4 - d2;
+  const T t0 = 4.f * d0 - 5.f * d2 + d4;
+  d1 = s34 - 4.f * s12;
+  d2 = 4.f * m12 + m43;
+  d3 = m42 - 2.f * m13;
+  d4 = 2.f * m13 + m42;
+  d0 = t0;
+}
+
 // A^T of F(4x4, 3x3) on 6 values -> 4: rows [1 1 1 1 1 0], [0 1 -1 2 -2 0], [0 1 1 4 4 0], [0 1 -1 8 -8 1]
 __device__ __forceinline__ void w4s_at(float m0, float m1, float m2, float m3, float m4, float m5, float& o0,
                                        float& o1, float& o2, float& o3) {
@@ -91,6 +112,13 @@ __device__ __forceinline__ void w4s_at(float m0, float m1, float m2, float m3, f
   o3 = fmaf(8.f, d34, d12) + m5;
 }
 
+// rows 0 and 2 of A^T (neither reads m5): w4s_at's expressions for o0 and o2
+__device__ __forceinline__ void w4s_at_even(float m0, float m1, float m2, float m3, float m4, float& o0, float& o2) {
+  const float s12 = m1 + m2, s34 = m3 + m4;
+  o0 = m0 + s12 + s34;
+  o2 = fmaf(4.f, s34, s12);
+}
+
 // ---------------------------------------------------------------- 1. input transform
 // One block of 256 threads per (tile group, chunk) unit and CPT channels per thread (CPT = 1, 2, 4; 4 / CPT
 // units per block): thread (l, jj) owns fragment lane l = 16 g + r (tile 16 tg + r) and elements
@@ -98,8 +126,10 @@ __device__ __forceinline__ void w4s_at(float m0, float m1, float m2, float m3, f
 // one contiguous KiB; each pixel read is a CPT x 4-byte load whose lane neighbours fill a 64-B segment.
 // CPT trades load width (4: 16-B loads, 1/4 of the threads) against parallelism (1: 4x the waves, for the
 // small late-stage maps whose unit count alone would not fill the chip).
-template <int CPT>
+// EVEN: the 5x5 patch (rows and columns 4t - 1 .. 4t + 3) and positions a, b < 5 only, 25 stores at 6a + b.
+template <int CPT, bool EVEN = false>
 __global__ __launch_bounds__(256) void wino4s_in_kernel(Wino4sParams p) {
+  constexpr int ND = EVEN ? 5 : 6;                 // patch rows / columns read, positions per direction written
   typedef float vec __attribute__((ext_vector_type(CPT)));
   constexpr int TPU = 64 * 4 / CPT;                // threads per unit
   const int unit = blockIdx.x * (256 / TPU) + threadIdx.x / TPU;
@@ -118,29 +148,35 @@ __global__ __launch_bounds__(256) void wino4s_in_kernel(Wino4sParams p) {
     const int h0 = 4 * th - 1, w0 = 4 * tw - 1;
     const float* xb = p.x + (size_t)b * p.H * p.W * p.C + kc * 16 + 4 * g + CPT * jj;
 #pragma unroll
-    for (int dy = 0; dy < 6; ++dy) {
+    for (int dy = 0; dy < ND; ++dy) {
       const int h = h0 + dy;
 #pragma unroll
-      for (int dx = 0; dx < 6; ++dx) {
+      for (int dx = 0; dx < ND; ++dx) {
         const int w = w0 + dx;
         d[dy][dx] = (h >= 0 && h < p.H && w >= 0 && w < p.W) ? *(const vec*)(xb + ((size_t)h * p.W + w) * p.C) : z;
       }
     }
   } else {
 #pragma unroll
-    for (int dy = 0; dy < 6; ++dy)
+    for (int dy = 0; dy < ND; ++dy)
 #pragma unroll
-      for (int dx = 0; dx < 6; ++dx) d[dy][dx] = z;
+      for (int dx = 0; dx < ND; ++dx) d[dy][dx] = z;
   }
 #pragma unroll
-  for (int dx = 0; dx < 6; ++dx) w4s_bt(d[0][dx], d[1][dx], d[2][dx], d[3][dx], d[4][dx], d[5][dx]);
+  for (int dx = 0; dx < ND; ++dx) {
+    if constexpr (EVEN) w4s_bt5(d[0][dx], d[1][dx], d[2][dx], d[3][dx], d[4][dx]);
+    else w4s_bt(d[0][dx], d[1][dx], d[2][dx], d[3][dx], d[4][dx], d[5][dx]);
+  }
 #pragma unroll
-  for (int a = 0; a < 6; ++a) w4s_bt(d[a][0], d[a][1], d[a][2], d[a][3], d[a][4], d[a][5]);
+  for (int a = 0; a < ND; ++a) {
+    if constexpr (EVEN) w4s_bt5(d[a][0], d[a][1], d[a][2], d[a][3], d[a][4]);
+    else w4s_bt(d[a][0], d[a][1], d[a][2], d[a][3], d[a][4], d[a][5]);
+  }
   vec* vo = (vec*)(p.v + (size_t)unit * 36 * 256) + tid;
 #pragma unroll
-  for (int a = 0; a < 6; ++a)
+  for (int a = 0; a < ND; ++a)
 #pragma unroll
-    for (int b = 0; b < 6; ++b) vo[(a * 6 + b) * TPU] = d[a][b];
+    for (int b = 0; b < ND; ++b) vo[(a * 6 + b) * TPU] = d[a][b];
 }
 
 // ---------------------------------------------------------------- 2. GEMM + output transform
@@ -152,16 +188,23 @@ __global__ __launch_bounds__(256) void wino4s_in_kernel(Wino4sParams p) {
 // the stage count and HW_ID
 // RG > 0: row split -- the block index that is the K split otherwise selects rows RG s .. RG s + RG - 1; the
 // block walks their 6 RG positions of every chunk and its epilogue writes the half-transformed rows
-template <int WT, int WN, int PG, int R, bool PIPE, bool STAMP = false, int RG = 0>
+// EVEN (even lattice; a stage is one row: PG = 6, RG 0 or 1): rows a < 5 only -- 5 stages per chunk (whole K)
+// or 5 row blocks (row split) -- and of each row the fragments b < 5.  The stage keeps its six slots and every
+// wave its PPW pieces, so the counted vmcnt waits stay what they are: the piece that is position 5 is issued
+// out of the descriptor's range (as a tile group past the end is), which fetches nothing, and its slot is never
+// read.  The epilogue applies the even rows of A^T and leaves 2x2 pixels per tile (row split: tr[5][T][2][N]).
+template <int WT, int WN, int PG, int R, bool PIPE, bool STAMP = false, int RG = 0, bool EVEN = false>
 __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sParams p) {
   constexpr int NW = WT * WN;
   constexpr int NP = RG ? 6 * RG : 36;           // positions (= accumulator fragments) of a wave
-  constexpr int NST = NP / PG;                   // stages per 16-channel chunk
+  constexpr int NST = EVEN ? (RG ? 1 : 5) : NP / PG;   // stages per 16-channel chunk
+  constexpr int PGR = EVEN ? 5 : PG;             // fragments of a stage that are read and multiplied
   constexpr int PIECES = (WT + WN) * PG;         // 1 KiB units per stage
   constexpr int PPW = PIECES / NW;               // LDS-DMA pieces per wave per stage
   constexpr int SLOT = PIECES * 1024;
   static_assert(NP % PG == 0 && (WT * PG) % NW == 0 && (WN * PG) % NW == 0, "stage geometry");
   static_assert(RG == 0 || 6 % RG == 0, "row groups");
+  static_assert(!EVEN || (PG == 6 && RG <= 1 && !PIPE && !STAMP), "even lattice: a stage is one row");
   static_assert(R >= 2 && R * SLOT <= 160 * 1024, "LDS ring");
   static_assert((R - 2) * PPW < 64, "vmcnt range");
   __shared__ __attribute__((aligned(16))) char smem[R * SLOT];
@@ -170,7 +213,7 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
   const int wt = wave / WN, wn = wave - wt * WN;
   // block -> (split, tile block, channel block); blocks whose index differs by a multiple of 8 run on one XCD,
   // so consecutive logical ids (which share operands) are gathered onto one XCD when the grid allows
-  const int TBn = (p.TG + WT - 1) / WT, NBn = p.N / (16 * WN), S = RG ? 6 / RG : p.ksplit;
+  const int TBn = (p.TG + WT - 1) / WT, NBn = p.N / (16 * WN), S = RG ? (EVEN ? 5 : 6 / RG) : p.ksplit;
   const int nblk = TBn * NBn * S;
   int L = blockIdx.x;
   if ((nblk & 7) == 0) L = (L & 7) * (nblk >> 3) + (L >> 3);
@@ -199,17 +242,19 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
   constexpr int PJA = WT * PG / NW;
   unsigned sbase[PPW];
   bool aval[PJA > 0 ? PJA : 1];
+  bool bval[PPW - PJA > 0 ? PPW - PJA : 1];       // EVEN only: the B piece is not position 5
 #pragma unroll
   for (int j = 0; j < PPW; ++j) {
     const int i = NW * j + wave;
     if (j < PJA) {
       const int wi = i / PG, pp = i - wi * PG;
       const int tgi = tb * WT + wi;
-      aval[j] = tgi < p.TG;
+      aval[j] = tgi < p.TG && (!EVEN || pp < 5);
       sbase[j] = (unsigned)((tgi * p.KC * 36 + pp) * 1024);
     } else {
       const int i2 = i - WT * PG;
       const int wi = i2 / PG, pp = i2 - wi * PG;
+      if constexpr (EVEN) bval[j - PJA] = pp < 5;
       sbase[j] = (unsigned)(((nb * WN + wi) * p.KC * 36 + pp) * 1024);
     }
   }
@@ -221,6 +266,7 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
 #pragma unroll
     for (int j = 0; j < PPW; ++j) {
       if (j < PJA) w4s_dma(aval[j] ? vlane : W4S_OOB, rv, sbase[j] + soff, slot + NW * j * 1024);
+      else if constexpr (EVEN) w4s_dma(bval[j - PJA] ? vlane : W4S_OOB, ru, sbase[j] + soff, slot + NW * j * 1024);
       else w4s_dma(vlane, ru, sbase[j] + soff, slot + NW * j * 1024);
     }
   };
@@ -253,7 +299,7 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
   auto read = [&](int st, f32x4v (&a)[PG], f32x4v (&b)[PG]) {
     const int so = (st % R) * SLOT;
 #pragma unroll
-    for (int pp = 0; pp < PG; ++pp) {
+    for (int pp = 0; pp < PGR; ++pp) {
       a[pp] = *(const f32x4v*)(ra + so + pp * 1024);
       b[pp] = *(const f32x4v*)(rb + so + pp * 1024);
     }
@@ -264,7 +310,7 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int pp = 0; pp < PG; ++pp)
+      for (int pp = 0; pp < PGR; ++pp)
         acc[sg * PG + pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[pp][j], b[pp][j], acc[sg * PG + pp], 0, 0, 0);
   };
   if constexpr (!PIPE) {
@@ -308,23 +354,41 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
   // ---- output transform on the accumulators: lane l holds M_p[tile 16 tg + 4 (l >> 4) + i][cout] at acc[p][i]
   const int tg = tb * WT + wt;
   const int n = (nb * WN + wn) * 16 + (lane & 15);
-  constexpr int NR = RG ? 4 * RG : 16;            // rows of N channels a tile leaves: pixels, or tr[a][j]
+  // (EVEN: the 2x2 pixels (2i', 2j') at y[2i' + j'], or tr[a][j'] for columns 0 and 2)
+  constexpr int NR = EVEN ? (RG ? 2 : 4) : (RG ? 4 * RG : 16);   // rows of N channels a tile leaves: pixels, or tr
   float y[4][16];                                 // the first NR of every y[i] are used
+  if constexpr (EVEN) {
+    constexpr int NA = RG ? 1 : 5;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float tr[NP / 6][4];                            // A^T applied along b: tr[a][j]
+    for (int i = 0; i < 4; ++i) {
+      float tr[NA][2];                              // rows 0 and 2 of A^T along b
 #pragma unroll
-    for (int a = 0; a < NP / 6; ++a)
-      w4s_at(acc[a * 6 + 0][i], acc[a * 6 + 1][i], acc[a * 6 + 2][i], acc[a * 6 + 3][i], acc[a * 6 + 4][i],
-             acc[a * 6 + 5][i], tr[a][0], tr[a][1], tr[a][2], tr[a][3]);
+      for (int a = 0; a < NA; ++a)
+        w4s_at_even(acc[a * 6 + 0][i], acc[a * 6 + 1][i], acc[a * 6 + 2][i], acc[a * 6 + 3][i], acc[a * 6 + 4][i],
+                    tr[a][0], tr[a][1]);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if constexpr (RG > 0) {
+      for (int j = 0; j < 2; ++j) {
+        if constexpr (RG > 0) y[i][j] = tr[0][j];
+        else w4s_at_even(tr[0][j], tr[1][j], tr[2][j], tr[3][j], tr[4][j], y[i][j], y[i][2 + j]);
+      }
+    }
+  } else {
 #pragma unroll
-        for (int a = 0; a < RG; ++a) y[i][a * 4 + j] = tr[a][j];
-      } else {
-        w4s_at(tr[0][j], tr[1][j], tr[2][j], tr[3][j], tr[4][j], tr[5][j], y[i][j], y[i][4 + j], y[i][8 + j],
-               y[i][12 + j]);
+    for (int i = 0; i < 4; ++i) {
+      float tr[NP / 6][4];                            // A^T applied along b: tr[a][j]
+#pragma unroll
+      for (int a = 0; a < NP / 6; ++a)
+        w4s_at(acc[a * 6 + 0][i], acc[a * 6 + 1][i], acc[a * 6 + 2][i], acc[a * 6 + 3][i], acc[a * 6 + 4][i],
+               acc[a * 6 + 5][i], tr[a][0], tr[a][1], tr[a][2], tr[a][3]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if constexpr (RG > 0) {
+#pragma unroll
+          for (int a = 0; a < RG; ++a) y[i][a * 4 + j] = tr[a][j];
+        } else {
+          w4s_at(tr[0][j], tr[1][j], tr[2][j], tr[3][j], tr[4][j], tr[5][j], y[i][j], y[i][4 + j], y[i][8 + j],
+                 y[i][12 + j]);
+        }
       }
     }
   }
@@ -379,14 +443,16 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
     }
   };
   if constexpr (RG > 0) {
-    // row split: tr[a][tile][j][N] for the block's rows a = RG s + (u >> 2), j = u & 3 (wino4s_finish_kernel)
+    // row split: tr[a][tile][j][N] for the block's rows a = RG s + (u >> 2), j = u & 3 (wino4s_finish_kernel);
+    // EVEN: tr[a][tile][j'][N] for row a = s, j' = u
     store_rows([&](int t, int u) -> float* {
+      if constexpr (EVEN) return t < p.T ? p.ws + (((size_t)s * p.T + t) * 2 + u) * p.N : nullptr;
       return t < p.T ? p.ws + (((size_t)(RG * s + (u >> 2)) * p.T + t) * 4 + (u & 3)) * p.N : nullptr;
     });
     write_stamps();
     return;
   }
-  if (S > 1 && p.counters == nullptr) {
+  if (!EVEN && S > 1 && p.counters == nullptr) {
     // split-K through wino4s_reduce_kernel: partial outputs [split][tile][16 pixels][N]
     store_rows([&](int t, int u) -> float* {
       return t < p.T ? p.ws + (((size_t)s * p.TG * 16 + t) * 16 + u) * p.N : nullptr;
@@ -394,7 +460,7 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
     write_stamps();
     return;
   }
-  if (S > 1) {
+  if (!EVEN && S > 1) {
     // fused split-K: every split publishes its partial outputs as 16-B sc1 stores in lane order (each lane
     // re-reads exactly what the same lane of the other splits wrote); the last split of the (tile, channel)
     // block to arrive adds the splits in split order -- deterministic whichever arrives last
@@ -462,12 +528,12 @@ __global__ __launch_bounds__(WT * WN * 64, 2) void wino4s_gemm_kernel(Wino4sPara
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int u = 0; u < 16; ++u) y[i][u] = act_relu(y[i][u] + bv, p.relu);
+    for (int u = 0; u < NR; ++u) y[i][u] = act_relu(y[i][u] + bv, p.relu);
   store_rows([&](int t, int u) -> float* {
     if (t >= p.T) return nullptr;
     const int b = t / per, rem = t - b * per;
     const int th = rem / p.TW, tw = rem - th * p.TW;
-    const int h = 4 * th + (u >> 2), w = 4 * tw + (u & 3);
+    const int h = 4 * th + (EVEN ? u & 2 : u >> 2), w = 4 * tw + (EVEN ? 2 * (u & 1) : u & 3);
     return h < p.H && w < p.W ? p.out + (((size_t)b * p.H + h) * p.W + w) * p.N : nullptr;
   });
   write_stamps();
@@ -535,7 +601,42 @@ __global__ __launch_bounds__(256) void wino4s_reduce_ks_kernel(Wino4sParams p) {
 // one thread per (tile, column j, 4 channels): the six tr[a][tile][j] (all loads in flight at once), A^T
 // along a, bias, activation, the 4 pixels of column j to NHWC; 32-bit index math (wino4s_forward checks the
 // range)
+// EVEN: one thread per (tile, column 2j', 4 channels): the five tr[a][tile][j'], rows 0 and 2 of A^T along a,
+// the 2 pixels (4th + 2i', 4tw + 2j')
+template <bool EVEN = false>
 __global__ __launch_bounds__(256) void wino4s_finish_kernel(Wino4sParams p) {
+  if constexpr (EVEN) {
+    const unsigned N4 = (unsigned)p.N >> 2;
+    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+    const unsigned rowsz = (unsigned)p.T * 2u * N4;                        // f32x4 per row a
+    if (idx >= rowsz) return;
+    const unsigned tj = idx / N4;
+    const int n4 = (int)(idx - tj * N4);
+    const int j = (int)(tj & 1u), t = (int)(tj >> 1);
+    const f32x4v* src = (const f32x4v*)p.ws + idx;
+    f32x4v m[5];
+#pragma unroll
+    for (int a = 0; a < 5; ++a) m[a] = src[a * rowsz];
+    const int per = p.TH * p.TW;
+    const int b = t / per, rem = t - b * per;
+    const int th = rem / p.TW, tw = rem - th * p.TW;
+    const int w = 4 * tw + 2 * j;
+    if (w >= p.W) return;
+    const f32x4v bv = *((const f32x4v*)p.bias + n4);
+    float o[4][2];                                 // [channel][pixel row 2i']
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w4s_at_even(m[0][e], m[1][e], m[2][e], m[3][e], m[4][e], o[e][0], o[e][1]);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int h = 4 * th + 2 * i;
+      if (h >= p.H) break;
+      f32x4v v;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = act_relu(o[e][i] + bv[e], p.relu);
+      *((f32x4v*)(p.out + (((size_t)b * p.H + h) * p.W + w) * p.N) + n4) = v;
+    }
+    return;
+  }
   const unsigned N4 = (unsigned)p.N >> 2;
   const unsigned idx = blockIdx.x * 256u + threadIdx.x;
   const unsigned rowsz = (unsigned)p.T * 4u * N4;                          // f32x4 per row a
@@ -624,6 +725,15 @@ hipError_t launch_rows(const Wino4sParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 
+// even lattice: whole K (RG 0) or 5 row blocks (RG 1)
+template <int WT, int WN, int R, int RG>
+hipError_t launch_even(const Wino4sParams& p, hipStream_t s) {
+  const int TBn = (p.TG + WT - 1) / WT, NBn = p.N / (16 * WN);
+  hipLaunchKernelGGL((wino4s_gemm_kernel<WT, WN, 6, R, false, false, RG, true>), dim3(TBn * NBn * (RG ? 5 : 1)),
+                     dim3(WT * WN * 64), 0, s, p);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 // ksplit >= 1: whole K (1) or split-K through the reduce launch; <= -2: split-K with the fixup fused (needs
@@ -634,6 +744,14 @@ bool wino4s_ok(int cfg, int C, int N, int ksplit) {
   if (!w4s_cfg(cfg, &c) || C % 16 || N % (16 * c.wn) || ks < 1 || ks > 8 || ksplit == -1) return false;
   if (c.rg > 0 && ksplit != 1) return false;       // the row split runs whole K
   return (C / 16) % ks == 0;
+}
+
+// the configs built for the even lattice (lattice 2): a stage is one row (PG 6), whole K or one row per block
+bool wino4s_lattice_ok(int cfg, int C, int N) {
+  switch (cfg) {
+    case 221: case 225: case 238: case 240: case 241: case 242: return wino4s_ok(cfg, C, N, 1);
+  }
+  return false;
 }
 
 int wino4s_blocks(int cfg, int B, int H, int W, int N) {
@@ -689,6 +807,9 @@ hipError_t wino4s_forward(const Wino4sParams& p_in, int cfg, hipStream_t s) {
   W4sCfg c;
   if (!wino4s_ok(cfg, p.C, p.N, p.ksplit) || !w4s_cfg(cfg, &c)) return hipErrorInvalidValue;
   if (!wino4s_range_ok(cfg, p.B, p.H, p.W, p.C, p.N, p.ksplit)) return hipErrorInvalidValue;
+  if (p.lattice != 0 && p.lattice != 2) return hipErrorInvalidValue;
+  // the even lattice where the config is built for it; every other launch writes the whole map
+  const bool even = p.lattice == 2 && p.ksplit == 1 && wino4s_lattice_ok(cfg, p.C, p.N);
   const bool fused = p.ksplit < 0;
   if (fused && !p.counters) return hipErrorInvalidValue;
   if (!fused) p.counters = nullptr;
@@ -707,13 +828,32 @@ hipError_t wino4s_forward(const Wino4sParams& p_in, int cfg, hipStream_t s) {
   const long units = (long)p.TG * p.KC;
   int cpt = units * 64 >= 2048L * 64 ? 4 : (units * 128 >= 2048L * 64 ? 2 : 1);
   if (const char* e = getenv("ADAPT_W4S_CPT")) cpt = atoi(e);
-  if (cpt == 4) hipLaunchKernelGGL(wino4s_in_kernel<4>, dim3((unsigned)((units + 3) / 4)), dim3(256), 0, s, p);
-  else if (cpt == 2) hipLaunchKernelGGL(wino4s_in_kernel<2>, dim3((unsigned)((units + 1) / 2)), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(wino4s_in_kernel<1>, dim3((unsigned)units), dim3(256), 0, s, p);
+  const dim3 gin((unsigned)(cpt == 4 ? (units + 3) / 4 : cpt == 2 ? (units + 1) / 2 : units));
+  if (even && cpt == 4) hipLaunchKernelGGL((wino4s_in_kernel<4, true>), gin, dim3(256), 0, s, p);
+  else if (even && cpt == 2) hipLaunchKernelGGL((wino4s_in_kernel<2, true>), gin, dim3(256), 0, s, p);
+  else if (even) hipLaunchKernelGGL((wino4s_in_kernel<1, true>), gin, dim3(256), 0, s, p);
+  else if (cpt == 4) hipLaunchKernelGGL(wino4s_in_kernel<4>, gin, dim3(256), 0, s, p);
+  else if (cpt == 2) hipLaunchKernelGGL(wino4s_in_kernel<2>, gin, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(wino4s_in_kernel<1>, gin, dim3(256), 0, s, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   Wino4sParams q = p;
   q.ws = slabs;
+  if (even) {
+    switch (cfg) {
+      case 221: e = launch_even<2, 2, 3, 0>(q, s); break;
+      case 225: e = launch_even<2, 1, 4, 0>(q, s); break;
+      case 238: e = launch_even<2, 2, 2, 1>(q, s); break;
+      case 240: e = launch_even<2, 2, 3, 1>(q, s); break;
+      case 241: e = launch_even<1, 2, 2, 1>(q, s); break;
+      case 242: e = launch_even<2, 1, 2, 1>(q, s); break;
+      default: return hipErrorInvalidValue;
+    }
+    if (e != hipSuccess || c.rg == 0) return e;
+    hipLaunchKernelGGL(wino4s_finish_kernel<true>, dim3((unsigned)(((size_t)p.T * (p.N / 2) + 255) / 256)), dim3(256),
+                       0, s, q);
+    return hipGetLastError();
+  }
   switch (cfg) {
     case 220: case 224: e = launch_gemm<2, 2, 6, 4>(q, s); break;
     case 221: e = launch_gemm<2, 2, 6, 3>(q, s); break;
@@ -743,7 +883,8 @@ hipError_t wino4s_forward(const Wino4sParams& p_in, int cfg, hipStream_t s) {
     default: return hipErrorInvalidValue;
   }
   if (e == hipSuccess && c.rg > 0) {
-    hipLaunchKernelGGL(wino4s_finish_kernel, dim3((unsigned)(((size_t)p.T * p.N + 255) / 256)), dim3(256), 0, s, q);
+    hipLaunchKernelGGL(wino4s_finish_kernel<false>, dim3((unsigned)(((size_t)p.T * p.N + 255) / 256)), dim3(256), 0, s,
+                       q);
     return hipGetLastError();
   }
   if (e != hipSuccess || p.ksplit == 1 || fused) return e;

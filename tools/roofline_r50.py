@@ -87,7 +87,8 @@ def _wino4_flop(ex, i):
     if (pc.kh, pc.kw, pc.stride) != (3, 3, 1):
         return None
     tiles = B * ((OH + 3) // 4) * ((OW + 3) // 4)
-    return 2 * 36 * tiles * Cin * pc.cout
+    # read only on the even lattice (PackedConv.out_lattice): rows and columns 0 and 2 of a tile need 25 positions
+    return 2 * (25 if pc.out_lattice == 2 else 36) * tiles * Cin * pc.cout
 
 
 def run(a):
@@ -138,9 +139,19 @@ def run(a):
             flop = int(flop * keep)
             in_bytes = [int(nb * keep) if tuple(ex.bufs(0)[n].shape[1:3]) == (fh, fw) else nb
                         for n, nb in zip(st.ins, in_bytes)]
-        act = sum(in_bytes) + sum(_bytes_of(ex, g, n, a.batch) for n in outs)
+        out_bytes = [_bytes_of(ex, g, n, a.batch) for n in outs]
+        lat = st.p.get("live_lattice", 0)
+        if lat > 1:
+            # a conv whose full-size output is read only at pixels (lat i, lat j) (runtime/plan.py
+            # _mark_live_lattice): the sampled pixels are the compulsory work and output traffic; a 3x3 still
+            # reads every input pixel
+            fh, fw = g.layers[st.out].out_shape[:2]
+            keep = -(-fh // lat) * -(-fw // lat) / (fh * fw)
+            flop = int(flop * keep)
+            out_bytes = [int(nb * keep) for nb in out_bytes]
+        act = sum(in_bytes) + sum(out_bytes)
         meta.append({"i": i, "kind": st.kind, "out": st.out, "ms": t_ms, "flop": flop,
-                     "subsample": st.p.get("subsample"),
+                     "subsample": st.p.get("subsample") or (lat if lat > 1 else None),
                      "act_bytes": act, "weight_bytes": _weight_bytes(g, st, 4 if a.dtype == "fp32" else 2),
                      "cfg": ex.cfg.get(i), "wino_flop": _wino_flop(ex, i),
                      "wino4_flop": _wino4_flop(ex, i)})

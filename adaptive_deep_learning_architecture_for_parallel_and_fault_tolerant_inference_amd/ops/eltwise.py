@@ -323,10 +323,24 @@ def gap_f32(x: torch.Tensor, out: torch.Tensor, stream=None, scratch: Optional[t
     return out
 
 
+def f32_act_modes(op: str) -> frozenset:
+    """The ActModes the fp32 op `op` (a wrapper of this module) implements.  `eltwise_f32` is not handed a
+    LeakyReLU slope, so it takes every mode but that one; the others take all of them."""
+    if op not in ("eltwise_f32", "dwconv_f32", "binary_f32", "affine_act_f32", "groupnorm_f32"):
+        raise KeyError(op)
+    modes = set(ACT_MODES.values())
+    if op == "eltwise_f32":
+        modes.discard(ACT_MODES["leaky_relu"])
+    return frozenset(modes)
+
+
 def eltwise_f32(a: torch.Tensor, out: torch.Tensor, b: Optional[torch.Tensor] = None,
                 scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None, relu: int = 0,
                 stream=None) -> torch.Tensor:
-    """out = act(a + b) | act(a * scale[c] + shift[c]) | act(a), all fp32."""
+    """out = act(a + b) | act(a * scale[c] + shift[c]) | act(a), all fp32; `relu` is an ActMode of
+    f32_act_modes("eltwise_f32")."""
+    if int(relu) not in f32_act_modes("eltwise_f32"):
+        raise ValueError(f"eltwise_f32: ActMode {relu} is not implemented")
     _chk(a, torch.float32, "a"); _chk(out, torch.float32, "out")
     if out.numel() != a.numel():
         raise ValueError("eltwise: element counts differ")

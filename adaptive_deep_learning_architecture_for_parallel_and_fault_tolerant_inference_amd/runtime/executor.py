@@ -37,6 +37,12 @@ from ..ops._lib import private_stream
 from .plan import Step, compact_maps, compile_plan, tensor_shape
 
 TUNING_FILE = Path(__file__).resolve().parent.parent / "tuning" / "gfx950_conv.json"
+
+# fp32 step kinds whose activation is a step parameter: kind -> (the ops.eltwise wrapper `_launch_f32` hands
+# it to, the parameter).  Every ActMode the planner can put there must be in E.f32_act_modes(wrapper).
+F32_ACT_STEPS = {"add": ("eltwise_f32", "relu"), "bn": ("eltwise_f32", "relu"), "relu": ("eltwise_f32", "mode"),
+                 "dwconv": ("dwconv_f32", "relu"), "act": ("affine_act_f32", "mode"),
+                 "binary": ("binary_f32", "act"), "groupnorm": ("groupnorm_f32", "act")}
 _tuning_lock = threading.Lock()
 _tuning_cache: Optional[Dict[str, List]] = None
 

@@ -440,7 +440,9 @@ __global__ __launch_bounds__(256) void gap_finish_f32_kernel(const float* __rest
   }
 }
 
-// elementwise fp32: mode 0 add(+act) a+b, 1 bn affine y = x*scale[c]+shift[c] (+act), 2 act only
+// elementwise fp32: mode 0 add(+act) a+b, 1 bn affine y = x*scale[c]+shift[c] (+act), 2 act only; `relu` is
+// an ActMode (GEN: one above ReLU6; the ReLU family keeps the two-instruction epilogue)
+template <bool GEN>
 __global__ __launch_bounds__(256) void eltwise_f32_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                           const float* __restrict__ scale,
                                                           const float* __restrict__ shift, float* __restrict__ y,
@@ -456,8 +458,8 @@ __global__ __launch_bounds__(256) void eltwise_f32_kernel(const float* __restric
       v[2] = v[2] * scale[c + 2] + shift[c + 2];
       v[3] = v[3] * scale[c + 3] + shift[c + 3];
     }
-    v[0] = act_relu(v[0], relu); v[1] = act_relu(v[1], relu);
-    v[2] = act_relu(v[2], relu); v[3] = act_relu(v[3], relu);
+    v[0] = actx<GEN>(v[0], relu); v[1] = actx<GEN>(v[1], relu);
+    v[2] = actx<GEN>(v[2], relu); v[3] = actx<GEN>(v[3], relu);
     *(f32x4*)(y + i * 4) = v;
   }
 }
@@ -749,9 +751,14 @@ hipError_t gap_large_f32(const float* x, float* y, float* part, int B, int HW, i
 
 hipError_t eltwise_f32(const float* a, const float* b, const float* scale, const float* shift, float* y, size_t n,
                        int C, int op, int relu, hipStream_t s) {
-  if (n % 4 || C % 4) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(eltwise_f32_kernel, dim3(grid_for(n / 4)), dim3(256), 0, s, a, b, scale, shift, y, n / 4, C, op,
-                     relu);
+  // LeakyReLU needs its slope, which this kernel is not handed (the planner never fuses it)
+  if (n % 4 || C % 4 || relu < 0 || relu > ACT_GELU_TANH || relu == ACT_LEAKY_RELU) return hipErrorInvalidValue;
+  if (relu > ACT_RELU6)
+    hipLaunchKernelGGL(eltwise_f32_kernel<true>, dim3(grid_for(n / 4)), dim3(256), 0, s, a, b, scale, shift, y, n / 4,
+                       C, op, relu);
+  else
+    hipLaunchKernelGGL(eltwise_f32_kernel<false>, dim3(grid_for(n / 4)), dim3(256), 0, s, a, b, scale, shift, y, n / 4,
+                       C, op, relu);
   return hipGetLastError();
 }
 

@@ -75,21 +75,29 @@ def _model(cfg: AdaptConfig):
 
 
 def _token_models():
-    from .models.zoo import GPT
-    return GPT
+    from .models.zoo import DISTILBERT, GPT
+    return {**GPT, **DISTILBERT}
 
 
 def _request(cfg: AdaptConfig, m, rng, uint8: bool = False) -> np.ndarray:
     """One request batch for model `m`: token ids in [0, V) as float32 where the input feeds an Embedding (the
     uint8 path is for images and is refused there), else N(0, 1) pixels or uint8 ones, in the configured image
-    shape."""
+    shape.  Where the Embedding has mask_zero the ids are in [1, V) and every sample is right-padded with id 0 from
+    a random length in [1, T] on."""
+    from .graph.ir import holds_token_ids
     g = m.graph
     first = [g.layers[c] for c in g.consumers().get(g.input, [])]
-    if first and all(L.op == "embedding" for L in first):
+    first = [L for L in first if L.op == "embedding"] if holds_token_ids(g, g.input) else []
+    if first:
         if uint8:
             raise ValueError(f"--uint8 sends images; input {g.input!r} of {g.name} holds token ids")
         vocab = min(int(L.attrs["input_dim"]) for L in first)
-        return rng.integers(0, vocab, (cfg.batch,) + tuple(g.layers[g.input].out_shape)).astype(np.float32)
+        shape = (cfg.batch,) + tuple(g.layers[g.input].out_shape)
+        if any(L.attrs.get("mask_zero") for L in first) and vocab > 1:
+            ids = rng.integers(1, vocab, shape)
+            lengths = rng.integers(1, shape[-1] + 1, shape[:-1] + (1,))
+            return np.where(np.arange(shape[-1]) < lengths, ids, 0).astype(np.float32)
+        return rng.integers(0, vocab, shape).astype(np.float32)
     if uint8:
         return rng.integers(0, 256, (cfg.batch,) + tuple(cfg.image), dtype=np.uint8)
     return rng.standard_normal((cfg.batch,) + tuple(cfg.image)).astype(np.float32)

@@ -54,7 +54,14 @@ OPS = (
                   # use_bias; inputs [query], [query, value] or [query, value, key] in Keras argument order (one input
                   # is self-attention, a missing key means key = value), each (H, W, C) or (T, C); value and key have
                   # the same token count, their channel counts are their own; output the query's shape.  causal
-                  # (stored only when True; one input only): Keras' use_causal_mask, query i attends keys j <= i
+                  # (stored only when True; one input only): Keras' use_causal_mask, query i attends keys j <= i.
+                  # key_mask (stored only when True; one source only, never with causal): the layer's LAST input is
+                  # then a (T,) mask tensor, T the token count, and token j is padding iff -1 < mask[j] < 1 (for
+                  # Embedding(mask_zero=True) simply the ids tensor the Embedding reads; `propagate_masks` derives
+                  # the edge).  A padded token is not attended as a key; at kept positions this is Keras' implicit
+                  # padding mask exactly.  At a padded QUERY position the context row is zeros, where Keras' fully
+                  # masked softmax row yields the plain mean of V: outputs at padded positions are defined but
+                  # not Keras'; nothing at a kept position reads them
     "posembed",   # ViT class token + learned position embedding: attrs class_token; (H, W, C) -> (1, T + ct, C)
     "winattn",    # Swin window attention (the project's own layer, Keras class WindowAttention): num_heads, key_dim,
                   # window (M), shift (0 <= s < M), use_bias; (H, W, C) -> (H, W, C), H and W multiples of M.
@@ -64,7 +71,9 @@ OPS = (
                   # batch size; output (1, N, C), the same for every image
     "embedding",  # Keras Embedding: attrs input_dim (V <= 2**24), output_dim (C); weight embeddings (V, C); input
                   # (T,) token ids carried as float32 (truncated toward zero, every id exact), output (T, C); an id
-                  # outside [0, V) yields a zero row (TensorFlow's GPU gather; a kernel cannot raise)
+                  # outside [0, V) yields a zero row (TensorFlow's GPU gather; a kernel cannot raise).  mask_zero
+                  # (stored only when True): position t is padding iff its id truncates to 0, -1 < id < 1; the
+                  # mask reaches the `mha` layers that `propagate_masks` finds
     "space_to_depth",  # Swin patch merging's rearrangement (Keras class SpaceToDepth): attrs block (2);
                   # (H, W, C) -> (H/2, W/2, 4C), out[y, x, (2 dx + dy) C + c] = in[2y + dy, 2x + dx, c]: the
                   # concatenation of x[0::2,0::2], x[1::2,0::2], x[0::2,1::2], x[1::2,1::2] (not tf.nn.space_to_depth,
@@ -122,9 +131,12 @@ MHA_PARTS = {"q": ("query",), "k": ("key",), "v": ("value",), "qk": ("query", "k
              "qkv": ("query", "key", "value")}
 
 
-def mha_sources(inputs: Sequence[str]) -> Tuple[str, str, str]:
+def mha_sources(inputs: Sequence[str], key_mask: bool = False) -> Tuple[str, str, str]:
     """(query, key, value) source tensors of an `mha` layer's inputs ([query], [query, value] or
-    [query, value, key], Keras argument order; a missing key means key = value)."""
+    [query, value, key], Keras argument order; a missing key means key = value).  With `key_mask` (the layer's
+    attribute) the last input is the mask tensor and is ignored."""
+    if key_mask:
+        inputs = inputs[:-1]
     q = inputs[0]
     v = inputs[1] if len(inputs) > 1 else q
     k = inputs[2] if len(inputs) > 2 else v
@@ -245,7 +257,8 @@ class Layer:
         if self.op == "mha":
             c, h, d = in_shapes[0][-1], self.attrs["num_heads"], self.attrs["key_dim"]
             dv = self.attrs.get("value_dim") or d
-            _, ck, cv = (s[-1] for s in mha_sources(in_shapes))      # each projection follows its own source
+            # each projection follows its own source
+            _, ck, cv = (s[-1] for s in mha_sources(in_shapes, bool(self.attrs.get("key_mask"))))
             out = []
             for part, shp, bshp in (("query", (c, h, d), (h, d)), ("key", (ck, h, d), (h, d)),
                                     ("value", (cv, h, dv), (h, dv)), ("attention_output", (h, dv, c), (c,))):
@@ -302,7 +315,7 @@ class Layer:
             t, c = _tokens(in_shapes[0]), in_shapes[0][-1]
             h, d = self.attrs["num_heads"], self.attrs["key_dim"]
             dv = self.attrs.get("value_dim") or d
-            _, sk, sv = mha_sources(in_shapes)
+            _, sk, sv = mha_sources(in_shapes, bool(self.attrs.get("key_mask")))
             tk = _tokens(sk)
             pairs = t * (t + 1) // 2 if self.attrs.get("causal") else t * tk      # (query, key) pairs of the core
             return (t * c * h * d + tk * sk[-1] * h * d + tk * sv[-1] * h * dv + pairs * h * (d + dv)
@@ -382,8 +395,24 @@ class Graph:
                                  f"'nearest' or 'bilinear' (got {sz}, {layer.attrs.get('interpolation')!r})")
         if layer.op == "mha":
             shapes = [self.layers[i].out_shape for i in layer.inputs]
+            if "key_mask" in layer.attrs:
+                if layer.attrs["key_mask"] is not True:
+                    raise ValueError(f"mha {layer.name!r}: key_mask is stored only when True (got "
+                                     f"{layer.attrs['key_mask']!r}); leave it out otherwise")
+                if layer.attrs.get("causal"):
+                    raise ValueError(f"mha {layer.name!r}: a padding mask (key_mask) together with causal is not "
+                                     f"built")
+                if len(layer.inputs) != 2:
+                    raise ValueError(f"mha {layer.name!r}: a padding mask (key_mask) needs one source "
+                                     f"(self-attention) and the mask tensor as the last input, got "
+                                     f"{len(layer.inputs)} inputs")
+                if len(shapes[0]) not in (2, 3) or tuple(shapes[1]) != (_tokens(shapes[0]),):
+                    raise ValueError(f"mha {layer.name!r}: the mask tensor {layer.inputs[-1]!r} has shape "
+                                     f"{tuple(shapes[1])}, not the token count ({_tokens(shapes[0])},) of "
+                                     f"{tuple(shapes[0])}")
+                shapes = shapes[:-1]                # the sources
             rank = len(shapes[0])
-            if (not 1 <= len(layer.inputs) <= 3 or any(len(s) not in (2, 3) for s in shapes)
+            if (not 1 <= len(shapes) <= 3 or any(len(s) not in (2, 3) for s in shapes)
                     or int(layer.attrs.get("num_heads", 0)) < 1 or int(layer.attrs.get("key_dim", 0)) < 1
                     or int(layer.attrs.get("value_dim") or 1) < 1):
                 raise ValueError(f"mha {layer.name!r}: needs one input of rank 2 or 3 (got rank {rank}), or [query, "
@@ -669,3 +698,100 @@ class Graph:
             lines.append(f"{n:40s} {L.op:8s} {str(L.out_shape):>18s} {p:>10d}")
         lines.append(f"Total params: {self.count_params():,}")
         return "\n".join(lines)
+
+
+# ------------------------------------------------------------- padding masks
+def holds_token_ids(g: "Graph", name: str) -> bool:
+    """Whether tensor `name` is read as token ids only: it has consumers, and each is an `embedding` or takes it
+    in the mask slot (the last input) of an `mha` with key_mask and nowhere else."""
+    cons = g.consumers().get(name, [])
+
+    def as_ids(L: "Layer") -> bool:
+        if L.op == "embedding":
+            return True
+        return bool(L.op == "mha" and L.attrs.get("key_mask") and L.inputs[-1] == name
+                    and name not in L.inputs[:-1])
+    return bool(cons) and all(as_ids(g.layers[c]) for c in cons)
+
+
+# layers a padding mask travels through unchanged (Keras >= 2.10 and Keras 3 propagate it implicitly); `add`,
+# `binary`, `posembed` and `mha` have rules of their own below; every other consumer drops the mask
+MASK_TRANSPARENT = ("layernorm", "dense", "act", "identity", "layerscale")
+
+
+def propagate_masks(g: "Graph") -> Dict[str, str]:
+    """Which padding mask reaches which self-attention layer: {mha layer name: mask tensor name}.  The one
+    implementation of the rules, used by the Keras importer, the zoo builder and the Keras writer.
+
+    A mask starts at an `embedding` with mask_zero (the mask tensor is the ids tensor it reads: position t is
+    padding iff -1 < id < 1).  It travels unchanged through `add` and `binary` (the AND of the masks of those
+    inputs that have one, which here must be one and the same tensor), MASK_TRANSPARENT layers, a 1x1 `conv` on
+    tokens, `posembed` without a class token, and `mha` itself (its output carries the query's mask).  Any other
+    consumer drops it.  Refused by layer name (NotImplementedError): a masked tensor into `gap` / `gmp` (Keras
+    takes a masked mean), into a class-token `posembed` or into `winattn`; a mask on an `mha` with more than one
+    source, or together with `causal`; two different masks meeting in one `add` / `binary`.  An existing
+    `key_mask` edge is not trusted: the mask tensor (last input) of such a layer is left out of its sources and
+    the result says what the rules derive, so a caller can compare."""
+    mask: Dict[str, Optional[str]] = {}
+    reached: Dict[str, str] = {}
+    for n in g.order:
+        L = g.layers[n]
+        ins = list(L.inputs[:-1]) if L.op == "mha" and L.attrs.get("key_mask") else list(L.inputs)
+        got = [mask.get(i) for i in ins]
+        have = sorted({m for m in got if m})
+        out = None
+        if L.op == "embedding":
+            out = L.inputs[0] if L.attrs.get("mask_zero") else None
+        elif not have:
+            out = None
+        elif L.op in ("add", "binary"):
+            if len(have) > 1:
+                raise NotImplementedError(f"{L.op} {n!r}: two different padding masks meet ({have[0]!r} and "
+                                          f"{have[1]!r})")
+            out = have[0]
+        elif L.op in MASK_TRANSPARENT:
+            out = got[0]
+        elif L.op == "conv":
+            out = (got[0] if _pair(L.attrs["kernel"]) == (1, 1) and _pair(L.attrs.get("stride", 1)) == (1, 1)
+                   else None)
+        elif L.op == "posembed":
+            if L.attrs.get("class_token"):
+                raise NotImplementedError(f"posembed {n!r}: a class token on a tensor that carries a padding mask "
+                                          f"({have[0]!r})")
+            out = got[0]
+        elif L.op == "mha":
+            if len(ins) > 1:
+                raise NotImplementedError(f"mha {n!r}: a padding mask ({have[0]!r}) on a call with separate "
+                                          f"sources; only self-attention takes it")
+            if L.attrs.get("causal"):
+                raise NotImplementedError(f"mha {n!r}: a padding mask ({have[0]!r}) together with the causal mask")
+            reached[n] = out = got[0]
+        elif L.op == "winattn":
+            raise NotImplementedError(f"winattn {n!r}: its input carries a padding mask ({have[0]!r})")
+        elif L.op in ("gap", "gmp"):
+            raise NotImplementedError(f"{L.op} {n!r}: pooling over a tensor that carries a padding mask "
+                                      f"({have[0]!r}); Keras takes a masked mean there, which is not built")
+        mask[n] = out
+    return reached
+
+
+def with_key_masks(g: "Graph") -> "Graph":
+    """`g` with the padding masks of `propagate_masks` made explicit: every reached `mha` gets `key_mask` and the
+    mask tensor as its last input, a real edge that `consumers()`, `ancestors()`, the slicer and the planner see.
+    A graph no mask reaches is returned as it is."""
+    reached = propagate_masks(g)
+    if all(g.layers[n].attrs.get("key_mask") and g.layers[n].inputs[-1] == m for n, m in reached.items()):
+        stale = [n for n in g.order if g.layers[n].attrs.get("key_mask") and n not in reached]
+        if not stale:
+            return g
+    out = Graph(g.name)
+    for n in g.order:
+        L = g.layers[n]
+        ins, attrs = list(L.inputs), dict(L.attrs)
+        if L.op == "mha" and attrs.pop("key_mask", None):
+            ins = ins[:-1]
+        if n in reached:
+            ins, attrs["key_mask"] = ins + [reached[n]], True
+        out.add(Layer(L.name, L.op, ins, attrs, tuple(L.out_shape)))
+    out.input_names, out.output_names = list(g.input_names), list(g.output_names)
+    return out

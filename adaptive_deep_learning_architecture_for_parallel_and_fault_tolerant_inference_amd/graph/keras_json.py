@@ -27,7 +27,7 @@ from __future__ import annotations
 import json
 from typing import Any, Dict, List, Tuple
 
-from .ir import ACTIVATIONS, Graph, Layer, _pair
+from .ir import ACTIVATIONS, Graph, Layer, _pair, propagate_masks, with_key_masks
 
 _BINARY = {"Multiply": "mul", "Subtract": "sub", "Maximum": "max", "Minimum": "min", "Average": "avg"}
 
@@ -296,10 +296,10 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
         return Layer(name, "queries", inputs, {"length": int(cfg["length"]), "dim": int(cfg["dim"]),
                                                "initializer": str(cfg.get("initializer", "normal"))})
     if cls == "Embedding":
-        if cfg.get("mask_zero"):
-            raise NotImplementedError(f"{name}: Embedding with mask_zero=True (masks are not propagated)")
-        return Layer(name, "embedding", inputs, {"input_dim": int(cfg["input_dim"]),
-                                                 "output_dim": int(cfg["output_dim"])})
+        a = {"input_dim": int(cfg["input_dim"]), "output_dim": int(cfg["output_dim"])}
+        if cfg.get("mask_zero"):                       # from_keras_json refuses it unless asked (padding_mask=True)
+            a["mask_zero"] = True
+        return Layer(name, "embedding", inputs, a)
     if cls == "LayerScale":
         return Layer(name, "layerscale", inputs, {"init_values": float(cfg.get("init_values", 1e-6))})
     if cls == "StochasticDepth":                       # drops whole residual branches in training only
@@ -376,13 +376,18 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
     raise NotImplementedError(f"layer {name!r}: Keras class {cls!r} is not supported by the runtime")
 
 
-def from_keras_json(s, cross_attention: bool = False, causal_attention: bool = False) -> Graph:
+def from_keras_json(s, cross_attention: bool = False, causal_attention: bool = False,
+                    padding_mask: bool = False) -> Graph:
     """Parse ``model.to_json()`` output (str or already-decoded dict) into a Graph.  `cross_attention=True` reads a
     MultiHeadAttention call whose query, value and key are different tensors (the `mha` op's two- and three-input
     forms); by default such a call is refused by layer name, which is what this function has always done and what
     callers written against it may rely on.  `causal_attention=True` likewise reads a self-attention call with
     `use_causal_mask=True` (the `mha` op's `causal` attribute), refused by layer name by default.
-    `Model.from_keras_json`, and through it the command line, pass True for both."""
+    `padding_mask=True` reads `Embedding(mask_zero=True)`, refused by layer name by default, and propagates its
+    mask as Keras does implicitly (graph/ir.py `propagate_masks`): every self-attention layer it reaches gets
+    `key_mask` and the ids tensor as its last input.  Outputs at kept positions are Keras'; at padded positions
+    they are defined but not Keras' (a padded query's context row is zeros, graph/ir.py "mha").
+    `Model.from_keras_json`, and through it the command line, pass True for all three."""
     d = json.loads(s) if isinstance(s, (str, bytes)) else s
     if d.get("class_name") not in ("Functional", "Model"):
         raise NotImplementedError(f"only functional models are supported (got {d.get('class_name')!r})")
@@ -405,6 +410,9 @@ def from_keras_json(s, cross_attention: bool = False, causal_attention: bool = F
             if shp is not None and il is not None and (len(shp) != 1 or int(il) != shp[0]):
                 raise NotImplementedError(f"{name}: Embedding input_length={ld['config']['input_length']} does not "
                                           f"match its input {tuple(shp)}")
+            if ld["config"].get("mask_zero") and not padding_mask:
+                raise NotImplementedError(f"{name}: Embedding with mask_zero=True (masks are not propagated); "
+                                          f"from_keras_json(..., padding_mask=True) reads it")
         for layer in _layers_from_keras(ld["class_name"], ld["config"], name, inputs):
             if causal:
                 layer.attrs["causal"] = True
@@ -418,7 +426,7 @@ def from_keras_json(s, cross_attention: bool = False, causal_attention: bool = F
         return [e[0] for e in v]
     g.input_names = names(cfg["input_layers"])
     g.output_names = names(cfg["output_layers"])
-    return g
+    return with_key_masks(g) if padding_mask else g
 
 
 # ------------------------------------------------------------------ export
@@ -481,7 +489,7 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
         cfg.update(class_token=bool(a.get("class_token")))
     elif L.op == "embedding":
         cls = "Embedding"
-        cfg.update(input_dim=a["input_dim"], output_dim=a["output_dim"], mask_zero=False,
+        cfg.update(input_dim=a["input_dim"], output_dim=a["output_dim"], mask_zero=bool(a.get("mask_zero")),
                    input_length=g.layers[L.inputs[0]].out_shape[0])
     elif L.op == "queries":
         cls = "LearnedQueries"
@@ -542,9 +550,10 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
         raise NotImplementedError(L.op)
     inbound = [[[i, 0, 0, {}] for i in L.inputs]] if L.inputs else []
     if L.op == "mha":           # Keras 2: mha(q, v[, key=k]) keeps `value` (and `key`) in the entry's kwargs
-        kw = {"value": [L.inputs[1] if len(L.inputs) > 1 else L.inputs[0], 0, 0]}
-        if len(L.inputs) > 2:
-            kw["key"] = [L.inputs[2], 0, 0]
+        src = L.inputs[:-1] if a.get("key_mask") else L.inputs      # Keras propagates the padding mask itself
+        kw = {"value": [src[1] if len(src) > 1 else src[0], 0, 0]}
+        if len(src) > 2:
+            kw["key"] = [src[2], 0, 0]
         if a.get("causal"):
             kw["use_causal_mask"] = True
         inbound = [[[L.inputs[0], 0, 0, kw]]]
@@ -552,7 +561,18 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
 
 
 def to_keras_json(g: Graph) -> str:
-    """Our graph as Keras 2 functional-model JSON (``model.to_json()`` layout)."""
+    """Our graph as Keras 2 functional-model JSON (``model.to_json()`` layout).  Keras propagates a padding mask
+    implicitly, so an `mha` call is written without its `key_mask` input; the explicit edges must therefore be
+    exactly what `propagate_masks` re-derives from the Embedding layers, else the document would not mean the
+    graph and the layer is refused by name."""
+    derived = propagate_masks(g)
+    for n in g.order:
+        L = g.layers[n]
+        have = L.inputs[-1] if L.op == "mha" and L.attrs.get("key_mask") else None
+        if have != derived.get(n):
+            raise NotImplementedError(f"mha {n!r}: its key_mask input is {have!r} but the padding masks of the "
+                                      f"graph's Embedding layers give {derived.get(n)!r}; Keras JSON cannot say "
+                                      f"that")
     layers = [_keras_layer(g.layers[n], g) for n in g.order]
     outs = g.output_names or [g.order[-1]]
     return json.dumps({"class_name": "Functional",

@@ -144,7 +144,7 @@ def layer_costs(g: Graph, batch: int = 32, hw: Optional[HwModel] = None) -> Dict
             # an embedding
             out[n] = g.tensor_bytes(n, hw.act_bytes) * batch / hw.hbm_bw + hw.launch_s
             continue
-        if L.op == "mha" and len(L.inputs) > 1:
+        if L.op == "mha" and len(L.inputs) > 1 and not L.attrs.get("key_mask"):
             # separate sources: the MACs of graph/ir.py (each projection over its own source's tokens, the
             # Tq x Tk core, the output projection) and one launch per projection GEMM, the core and the output
             # projection.  Uncalibrated, like `queries`; the core's grid is B x heads x ceil(Tq / 64) blocks,
@@ -156,7 +156,9 @@ def layer_costs(g: Graph, batch: int = 32, hw: Optional[HwModel] = None) -> Dict
         # zeros) against its bytes; upsample / crop have no MACs and cost their input + output traffic.
         # mha: the MACs of its two projection GEMMs and the T x T core (graph/ir.py); a causal layer's core counts
         # T (T + 1) / 2 (query, key) pairs there, the tiles its kernel does not skip; uncalibrated: no planner fit
-        # includes a causal model.  posembed: its traffic.
+        # includes a causal model.  A layer with a padding mask (key_mask) costs what the unmasked one costs: the
+        # planner cannot know the lengths, so the key tiles its kernel skips are not counted out (uncalibrated).
+        # posembed: its traffic.
         # winattn: 4 H W C^2 + 2 H W M^2 C MACs (projections and the window-local core); space_to_depth: its traffic
         t = max(2.0 * macs / hw.mfma_flops, byts / hw.hbm_bw) + hw.launch_s
         out[n] = t

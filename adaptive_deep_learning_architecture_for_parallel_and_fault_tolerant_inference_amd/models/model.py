@@ -57,7 +57,7 @@ class Model:
         name -> array dict); random-init (seeded) when no weights are given."""
         from ..graph.keras_json import from_keras_json
         from .resnet import init_weights, set_weights
-        g = from_keras_json(s, cross_attention=True, causal_attention=True)
+        g = from_keras_json(s, cross_attention=True, causal_attention=True, padding_mask=True)
         if weights is None:
             w = init_weights(g, seed)
         elif isinstance(weights, dict):

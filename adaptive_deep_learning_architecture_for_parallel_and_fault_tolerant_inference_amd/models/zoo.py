@@ -43,7 +43,7 @@ from __future__ import annotations
 
 from typing import Callable, Dict, Optional
 
-from ..graph.ir import Graph, Layer
+from ..graph.ir import Graph, Layer, with_key_masks
 
 
 def _conv(g: Graph, x: str, name: str, filters: int, k: int, stride: int = 1, padding: str = "valid",
@@ -782,7 +782,57 @@ def build_gpt(name: str = "gpt2", classes: Optional[int] = None, input_shape=Non
     return g
 
 
+# --------------------------------------------------------------------- DistilBERT
+# name -> (depth, width, heads, vocabulary, default tokens); micro: the test size (40 tokens, as gpt_micro)
+DISTILBERT = {
+    "distilbert_base": (6, 768, 12, 30522, 128),
+    "distilbert_micro": (2, 32, 2, 97, 40),
+}
+DISTILBERT_CONTEXT = 512   # rows of the published position table
+DISTILBERT_EPS = 1e-12
+DISTILBERT_FFN_RATIO = 4
+
+
+def build_distilbert(name: str = "distilbert_base", classes: Optional[int] = None, input_shape=None) -> Graph:
+    """DistilBERT (Sanh et al. 2019; `distilbert-base-uncased` as published) as a flat post-norm encoder: the (T,)
+    token ids (carried as float32, pad id 0) through an Embedding with mask_zero, a learned position embedding
+    without a class token and a LayerNormalization; `depth` blocks of MultiHeadAttention -> Add ->
+    LayerNormalization -> Dense(4C, exact gelu) -> Dense(C) -> Add -> LayerNormalization; no token-type
+    embedding.  The output is the last hidden state, (1, T, C).  The padding mask of the Embedding reaches every
+    attention layer by `propagate_masks` (graph/ir.py): each gets `key_mask` and the ids as its last input, and
+    attends kept tokens only; hidden states at padded positions are defined but are not Keras' (graph/ir.py
+    "mha").  `classes` is the vocabulary.  The position table has the T rows of the built graph; a loader slices
+    the published 512-row table, with which the total is the published 66,362,880."""
+    depth, width, heads, vocab, default_tokens = DISTILBERT[name]
+    vocab = int(classes or vocab)
+    shape = tuple(input_shape or (default_tokens,))
+    if len(shape) != 1 or not 1 <= shape[0] <= DISTILBERT_CONTEXT:
+        raise ValueError(f"{name}: input {shape} is not (T,) token ids with 1 <= T <= {DISTILBERT_CONTEXT}")
+    g = Graph(name)
+    x = g.add(Layer("input_1", "input", [], {"shape": shape}))
+    x = g.add(Layer(f"{name}_word_embeddings", "embedding", [x],
+                    {"input_dim": vocab, "output_dim": width, "mask_zero": True}))
+    x = g.add(Layer(f"{name}_position_embeddings", "posembed", [x], {"class_token": False}))
+
+    def ln(x: str, nm: str) -> str:
+        return g.add(Layer(nm, "layernorm", [x], {"epsilon": DISTILBERT_EPS}))
+
+    x = ln(x, f"{name}_embeddings_ln")
+    for i in range(depth):
+        nm = f"{name}_layer_{i}"
+        y = g.add(Layer(f"{nm}_attention", "mha", [x],
+                        {"num_heads": heads, "key_dim": width // heads, "use_bias": True}))
+        x = ln(g.add(Layer(f"{nm}_add1", "add", [x, y])), f"{nm}_sa_layer_norm")
+        y = g.add(Layer(f"{nm}_ffn_lin1", "dense", [x],
+                        {"units": DISTILBERT_FFN_RATIO * width, "activation": "gelu", "use_bias": True}))
+        y = g.add(Layer(f"{nm}_ffn_lin2", "dense", [y], {"units": width, "use_bias": True}))
+        x = ln(g.add(Layer(f"{nm}_add2", "add", [x, y])), f"{nm}_output_layer_norm")
+    g.output_names = [x]
+    return with_key_masks(g)
+
+
 BUILDERS: Dict[str, Callable[..., Graph]] = {
+    **{n: (lambda n: lambda **kw: build_distilbert(n, **kw))(n) for n in DISTILBERT},
     **{n: (lambda n: lambda **kw: build_gpt(n, **kw))(n) for n in GPT},
     **{n: (lambda n: lambda **kw: build_detr(n, **kw))(n) for n in DETR},
     **{n: (lambda n: lambda **kw: build_swin(n, **kw))(n) for n in SWIN},

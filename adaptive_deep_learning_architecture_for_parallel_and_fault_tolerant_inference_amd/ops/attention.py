@@ -30,12 +30,17 @@ def attention_path(key_dim: int, value_dim: int) -> str:
 
 
 def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, tokens: int, heads: int, key_dim: int,
-              value_dim: Optional[int] = None, stream=None, causal: bool = False) -> torch.Tensor:
+              value_dim: Optional[int] = None, stream=None, causal: bool = False,
+              key_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = softmax(Q K^T) V per (image, head); `causal`: query i attends keys j <= i only (Keras'
     use_causal_mask), on the kernels' masked instantiations, which skip the key tiles above the diagonal.  qkv [..., ld_in] holds batch * tokens rows of [Q | K | V]
     (head-major inside each part; Q already scaled by 1/sqrt(key_dim)), out [..., ld_out] gets heads * value_dim
     channels per row and zeros in the rest of the row.  fp32 or bf16 activations (both tensors alike); the
-    row strides are the last dimensions, the true widths come from heads / key_dim / value_dim."""
+    row strides are the last dimensions, the true widths come from heads / key_dim / value_dim.  `key_mask`: a
+    padding mask of batch * tokens fp32 values on the device (never with `causal`); token j of an image is padding
+    iff -1 < key_mask[j] < 1, the ids of an Embedding(mask_zero=True).  A padded key is not attended, a padded
+    query's row and every row of an image with no kept key are zeros, and the key tiles past an image's last kept
+    token are not loaded (the kernels' masked instantiations)."""
     dv = int(value_dim or key_dim)
     B, T, h, d = int(batch), int(tokens), int(heads), int(key_dim)
     if qkv.dtype not in (torch.float32, torch.bfloat16):
@@ -50,6 +55,15 @@ def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, tokens: int, hea
                          f"{h} heads ({d}, {dv})")
     if max(qkv.numel(), out.numel(), B * h * T) >= 2 ** 31:
         raise ValueError("attention: tensors must hold fewer than 2^31 elements (32-bit index math)")
+    if key_mask is not None:
+        if causal:
+            raise ValueError("attention: a padding mask together with the causal mask is not built")
+        _chk(key_mask, torch.float32, "key_mask")
+        if key_mask.numel() != B * T:
+            raise ValueError(f"attention: key_mask{tuple(key_mask.shape)} does not hold {B} x {T} values")
+        fn = kernels().attention_masked_f32 if qkv.dtype == torch.float32 else kernels().attention_masked_bf16
+        fn(ptr(qkv), ptr(key_mask), ptr(out), B, T, h, d, dv, int(ld_in), int(ld_out), stream_handle(stream))
+        return out
     if causal:
         fn = kernels().attention_causal_f32 if qkv.dtype == torch.float32 else kernels().attention_causal_bf16
     else:

@@ -161,7 +161,7 @@ class ReferenceExecutor:
             # dot product; one input is (x, x), a missing key is the value
             w = lambda p: self.w[f"{L.name}/{p}/kernel"]
             b = lambda p: self.w.get(f"{L.name}/{p}/bias", 0.0)
-            x, xk, xv = (t.reshape(t.shape[0], -1, t.shape[-1]) for t in mha_sources(ins))      # (B, T, C) each
+            x, xk, xv = (t.reshape(t.shape[0], -1, t.shape[-1]) for t in mha_sources(ins, bool(a.get("key_mask"))))      # (B, T, C) each
             q = (torch.einsum("btc,chd->bthd", x, w("query")) + b("query")) * (1.0 / float(a["key_dim"]) ** 0.5)
             k = torch.einsum("btc,chd->bthd", xk, w("key")) + b("key")
             v = torch.einsum("btc,chd->bthd", xv, w("value")) + b("value")
@@ -169,8 +169,18 @@ class ReferenceExecutor:
             if a.get("causal"):                 # Keras _compute_causal_mask: query i attends keys j <= i
                 t = s.shape[-1]
                 s = s.masked_fill(torch.ones(t, t, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
+            keep = None
+            if a.get("key_mask"):
+                # the padding mask: token j is padding iff -1 < ids[j] < 1 (a NaN is kept).  A padded key gets the
+                # score -inf; a padded query's context row, and every row of a sample with no kept key, is zeros
+                ids = ins[-1].reshape(ins[-1].shape[0], -1)
+                keep = ~((ids > -1) & (ids < 1))                                    # (B, T)
+                s = s.masked_fill(~keep[:, None, None, :], float("-inf"))
+                s = s.masked_fill(~keep.any(-1)[:, None, None, None], 0.0)          # no kept key: no NaN row
             p = torch.softmax(s, dim=-1)
             y = torch.einsum("bhqk,bkhd->bqhd", p, v)
+            if keep is not None:
+                y = y * (keep & keep.any(-1, keepdim=True))[:, :, None, None].to(y.dtype)
             y = torch.einsum("bqhd,hdc->bqc", y, w("attention_output")) + b("attention_output")
             return y.reshape(ins[0].shape)
         if L.op == "winattn":

@@ -207,7 +207,8 @@ class CpuExecutor:
             m.queries(self.packed[i][0], y, batch)
         elif k == "attention":
             m.attention(ins[0].reshape(-1, ins[0].shape[-1]), y.reshape(-1, y.shape[-1]), batch, int(p["tokens"]),
-                        int(p["heads"]), int(p["key_dim"]), int(p["value_dim"]), bool(p.get("causal")))
+                        int(p["heads"]), int(p["key_dim"]), int(p["value_dim"]), bool(p.get("causal")),
+                        np.ascontiguousarray(ins[1], np.float32).reshape(-1) if p.get("key_mask") else None)
         elif k == "embedding":
             m.embedding(ins[0], self.packed[i][0], y)
         elif k == "winattn":

@@ -29,7 +29,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ..graph.ir import Graph, bn_params, conv_bias, conv_kernel, depthwise_kernel
+from ..graph.ir import Graph, bn_params, conv_bias, conv_kernel, depthwise_kernel, holds_token_ids
 from ..ops import attention as attn_ops
 from ..ops import conv as conv_ops
 from ..ops import eltwise as E
@@ -149,9 +149,14 @@ class SliceExecutor:
                 and L.attrs.get("stands_for", "input") == "input"):
             return torch.float32          # user image input (Keras float32 NHWC)
         if L.op == "input" and base == name and len(L.out_shape) == 1:
-            cons = self.g.consumers().get(base, [])
-            if cons and all(self.g.layers[c].op == "embedding" for c in cons):
-                return torch.float32      # token ids: bf16 would round every id above 256
+            if holds_token_ids(self.g, base) or (L.attrs.get("stands_for", "input") == "input"
+                                                 and not self.g.consumers().get(base)):
+                # token ids, read by Embedding layers and the mask slots of attention layers only (a later
+                # pipeline stage may see the mask slots alone): bf16 would round every id above 256, and the
+                # masked attention kernels take their mask as fp32.  A stage that reads the graph's (T,) input
+                # not at all only relays it to a masked attention layer of a later stage: the ids stay fp32
+                # there too, so every stage's buffers, and with them the link slots between them, agree
+                return torch.float32
         if L.op == "softmax" or (L.op == "dense" and len(L.out_shape) == 1
                                  and L.attrs.get("activation") in (None, "linear", "softmax")):
             return torch.float32          # logits / probabilities; a Dense(relu, ...) feeds the next GEMM in bf16
@@ -375,7 +380,8 @@ class SliceExecutor:
         elif st.kind == "attention":
             p = st.p
             attn_ops.attention(b[st.ins[0]], b[st.out], self.batch, p["tokens"], p["heads"], p["key_dim"],
-                               p["value_dim"], stream=stream, causal=bool(p.get("causal")))
+                               p["value_dim"], stream=stream, causal=bool(p.get("causal")),
+                               key_mask=b[st.ins[1]] if p.get("key_mask") else None)
         elif st.kind == "embedding":
             attn_ops.embedding(b[st.ins[0]], self.packed[i], b[st.out], stream=stream)
         elif st.kind == "queries":

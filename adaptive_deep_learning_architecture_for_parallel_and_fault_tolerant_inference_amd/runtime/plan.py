@@ -32,7 +32,9 @@ kernels:
                or `n#q`, `n#k`, `n#v`; its ``attention`` step takes those buffers and records `tokens_q`,
                `tokens_k` and, as `q` / `k` / `v`, (which input, first column) of each part.  A causal layer's
                step carries `"causal": True` (only then: the key is absent otherwise) and runs the masked
-               kernel, which skips the key tiles above the diagonal
+               kernel, which skips the key tiles above the diagonal.  A layer with `key_mask` (a padding
+               mask) takes the (T,) mask tensor as a second input and carries `"key_mask": True` (only then);
+               its kernel does not load the key tiles past a sample's last kept token
 * ``embedding`` a Keras Embedding: a row gather of its (V, C) table by the fp32 token ids of its (T,) input
 * ``posembed`` ViT class token + learned position embedding
 * ``queries``  a LearnedQueries layer: its (N, C) weight broadcast to every image, one copy step
@@ -110,7 +112,7 @@ def tensor_shape(g: Graph, name: str, compact: Optional[Dict[str, tuple]] = None
         # "ctx" has the query's tokens; a projection (`n#q`, `n#kv`, ...) the tokens of the source its parts share
         h, d = int(L.attrs["num_heads"]), int(L.attrs["key_dim"])
         dv = int(L.attrs.get("value_dim") or d)
-        src = dict(zip(("query", "key", "value"), mha_sources(L.inputs)))
+        src = dict(zip(("query", "key", "value"), mha_sources(L.inputs, bool(L.attrs.get("key_mask")))))
         shape = L.out_shape if tag == "ctx" else g.layers[src[MHA_PARTS[tag][0]]].out_shape
         tokens = 1
         for v in shape[:-1]:
@@ -453,7 +455,8 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                         "pads": ((0, 0), (0, 0)), "stride": 1, "kernel": (1, 1), "filters": filters,
                         "packed_input": False, **head}
 
-            sq, sk, sv = (R(t) for t in mha_sources(L.inputs)) if L.op == "mha" else (R(L.inputs[0]),) * 3
+            sq, sk, sv = ((R(t) for t in mha_sources(L.inputs, bool(a.get("key_mask")))) if L.op == "mha"
+                          else (R(L.inputs[0]),) * 3)
             if sq == sk == sv:
                 steps.append(Step("conv", n + "#qkv", [sq], [], proj("qkv", h * (2 * d + dv), None)))
             if L.op == "winattn":               # on the (H, W, C) map, windows and shift resolved by the kernel
@@ -464,6 +467,9 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                 steps.append(Step("attention", n + "#ctx", [n + "#qkv"], [], {"layer": n, "tokens": tokens, **head}))
                 if a.get("causal"):
                     steps[-1].p["causal"] = True
+                if a.get("key_mask"):           # the (T,) mask tensor (the layer's last input) as a second input
+                    steps[-1].ins.append(R(L.inputs[-1]))
+                    steps[-1].p["key_mask"] = True
             else:
                 # separate sources: one projection per distinct source tensor, the parts that share one side by
                 # side ([Q | K] from `src + pos`, [K | V] when the key is the value); the core then reads Q, K and
@@ -484,7 +490,7 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
                         where[c] = (j, col)
                         col += width[c]
                 tokens_k = 1
-                for v in g.layers[mha_sources(L.inputs)[1]].out_shape[:-1]:
+                for v in g.layers[mha_sources(L.inputs, bool(a.get("key_mask")))[1]].out_shape[:-1]:
                     tokens_k *= v
                 steps.append(Step("attention", n + "#ctx", [f"{n}#{part}" for part, _ in parts], [],
                                   {"layer": n, "tokens_q": tokens, "tokens_k": tokens_k, **where, **head}))

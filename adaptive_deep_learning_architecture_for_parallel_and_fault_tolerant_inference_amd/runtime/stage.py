@@ -32,7 +32,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ..graph.ir import Graph
+from ..graph.ir import Graph, holds_token_ids
 
 
 def to_torch(a: np.ndarray, is_bf16: bool, device) -> torch.Tensor:
@@ -83,10 +83,9 @@ class StageCompute:
         self.device = torch.device(device)
         self.inputs = list(g.input_names)
         self.outputs = list(outputs or g.output_names)
-        # inputs that hold token ids (every consumer an Embedding): the uint8 / preprocess ingest is for images
-        cons = g.consumers()
-        self._id_inputs = {n for n in self.inputs
-                           if cons.get(n) and all(g.layers[c].op == "embedding" for c in cons[n])}
+        # inputs that hold token ids (every consumer an Embedding or an attention layer's mask slot): the uint8 /
+        # preprocess ingest is for images
+        self._id_inputs = {n for n in self.inputs if holds_token_ids(g, n)}
         self.gpu = self.device.type == "cuda"
         self.host_ring = max(2, int(host_ring))
         self._pinned: List[Dict[str, torch.Tensor]] = []

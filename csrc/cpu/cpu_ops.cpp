@@ -432,8 +432,19 @@ void window_attention(const Arr<float>& qkv, const Arr<float>& table, Arr<float>
 // Self-attention core, softmax(Q K^T) V per (image, head): qkv [B*T][ld_in] rows of [Q | K | V] (head-major, Q
 // already scaled by 1/sqrt(d)), out [B*T][ld_out] with heads * dv channels (the rest of a row becomes zero): the
 // argument layout of the GPU op (csrc/kernels/attention.hip).  fp32, the row maximum subtracted before the exponent.
-// causal: query q attends keys k <= q (Keras' use_causal_mask).
-void attention(const Arr<float>& qkv, Arr<float>& out, int B, int T, int heads, int d, int dv, bool causal) {
+// causal: query q attends keys k <= q (Keras' use_causal_mask).  key_mask (None, or B * T floats; never with
+// causal): token j of an image is padding iff -1 < key_mask[j] < 1 (a NaN is kept); a padded key is not attended
+// (its K and V rows are not read), a padded query's row and every row of an image with no kept key are zeros.
+void attention(const Arr<float>& qkv, Arr<float>& out, int B, int T, int heads, int d, int dv, bool causal,
+               const py::object& key_mask) {
+  const bool masked = !key_mask.is_none();
+  Arr<float> mask_arr;
+  if (masked) {
+    need(py::isinstance<Arr<float>>(key_mask), "attention key_mask must be a float32 array");
+    mask_arr = key_mask.cast<Arr<float>>();
+    need(!causal && mask_arr.size() == (long)B * T, "attention key_mask holds B * T values, and never with causal");
+  }
+  const float* mk = masked ? cptr(mask_arr) : nullptr;
   need(qkv.ndim() >= 2 && out.ndim() >= 2 && B >= 1 && T >= 1 && heads >= 1 && d >= 1 && dv >= 1, "attention args");
   const long ld_in = qkv.shape(qkv.ndim() - 1), ld_out = out.shape(out.ndim() - 1);
   need(qkv.size() == (long)B * T * ld_in && out.size() == (long)B * T * ld_out && ld_in >= (long)heads * (2 * d + dv)
@@ -453,27 +464,35 @@ void attention(const Arr<float>& qkv, Arr<float>& out, int B, int T, int heads, 
         for (int q = 0; q < T; ++q) {
           const float* qr = base + (size_t)q * ld_in + h * d;
           const int nk = causal ? q + 1 : T;           // the keys this query attends
-          float mx = -INFINITY;
-          for (int k = 0; k < nk; ++k) {
-            const float* kr = kb + (size_t)k * ld_in;
-            float sc = 0.f;
-            for (int i = 0; i < d; ++i) sc += qr[i] * kr[i];
-            p[k] = sc;
-            mx = std::max(mx, sc);
-          }
-          float l = 0.f;
-          for (int k = 0; k < nk; ++k) {
-            p[k] = std::exp(p[k] - mx);
-            l += p[k];
-          }
+          const float* mrow = masked ? mk + (size_t)b * T : nullptr;
+          auto kept = [&](int t) { return !mrow || !(mrow[t] > -1.f && mrow[t] < 1.f); };
           float* orow = yp + ((size_t)b * T + q) * ld_out + h * dv;
+          float mx = -INFINITY;
+          if (kept(q))                                 // a padded query attends nothing: l stays 0
+            for (int k = 0; k < nk; ++k) {
+              if (!kept(k)) continue;
+              const float* kr = kb + (size_t)k * ld_in;
+              float sc = 0.f;
+              for (int i = 0; i < d; ++i) sc += qr[i] * kr[i];
+              p[k] = sc;
+              mx = std::max(mx, sc);
+            }
+          float l = 0.f;
           for (int c = 0; c < dv; ++c) orow[c] = 0.f;
-          for (int k = 0; k < nk; ++k) {
-            const float* vr = vb + (size_t)k * ld_in;
-            const float pk = p[k];
-            for (int c = 0; c < dv; ++c) orow[c] += pk * vr[c];
+          if (mx != -INFINITY || !masked) {
+            for (int k = 0; k < nk; ++k) {
+              if (!kept(k)) continue;
+              p[k] = std::exp(p[k] - mx);
+              l += p[k];
+            }
+            for (int k = 0; k < nk; ++k) {
+              if (!kept(k)) continue;
+              const float* vr = vb + (size_t)k * ld_in;
+              const float pk = p[k];
+              for (int c = 0; c < dv; ++c) orow[c] += pk * vr[c];
+            }
           }
-          const float inv = 1.f / l;
+          const float inv = l == 0.f && masked ? 0.f : 1.f / l;
           for (int c = 0; c < dv; ++c) orow[c] *= inv;
           if (h == heads - 1)
             for (long c = (long)heads * dv; c < ld_out; ++c) yp[((size_t)b * T + q) * ld_out + c] = 0.f;
@@ -879,7 +898,7 @@ PYBIND11_MODULE(_cpu, m) {
   m.def("affine", &affine, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("y"), py::arg("act") = 0,
         py::arg("alpha") = 0.3f);
   m.def("attention", &attention, py::arg("qkv"), py::arg("out"), py::arg("B"), py::arg("T"), py::arg("heads"),
-        py::arg("key_dim"), py::arg("value_dim"), py::arg("causal") = false);
+        py::arg("key_dim"), py::arg("value_dim"), py::arg("causal") = false, py::arg("key_mask") = py::none());
   m.def("embedding", &embedding, py::arg("ids"), py::arg("table"), py::arg("out"));
   m.def("window_attention", &window_attention, py::arg("qkv"), py::arg("table"), py::arg("out"), py::arg("B"),
         py::arg("H"), py::arg("W"), py::arg("window"), py::arg("shift"), py::arg("heads"), py::arg("key_dim"));

@@ -5,7 +5,8 @@
 // heads x d, V: heads x dv).  out is [B * T][ld_out].  A group is an image; every address is the image's base
 // plus a row and a column offset: head h's Q at column h d, its K at heads d + h d, its V at 2 heads d + h dv.  The
 // staging table carries the K or V column of each vector, so a staged load needs no select.  The causal entry
-// points run the core's CAUSAL instantiations on the same layout.
+// points run the core's CAUSAL instantiations on the same layout, the masked entry points its MASKED ones with a
+// [B][T] fp32 padding mask (token j of an image is padding iff -1 < mask[j] < 1).
 #include "attention_core.h"
 
 namespace adapt {
@@ -35,9 +36,16 @@ struct SelfSrc {
   __device__ int out_row(const Block& b, int row) const { return b.img * Tn + row; }
 };
 
+// The same layout with a padding mask: image img's T mask values start at mask + img * T
+template <typename T>
+struct MaskedSelfSrc : SelfSrc<T> {
+  const float* mask;
+  __device__ const float* key_mask(const typename SelfSrc<T>::Block& b) const { return mask + b.img * this->Tn; }
+};
+
 template <typename T, bool CAUSAL>
 hipError_t attention_launch(const T* qkv, T* out, int B, int Tn, int heads, int d, int dv, int ld_in, int ld_out,
-                            hipStream_t s) {
+                            hipStream_t s, const float* mask = nullptr) {
   if (B < 1 || Tn < 1 || heads < 1 || d < 1 || dv < 1) return hipErrorInvalidValue;
   const long long lim = 0x7fffffffll;
   if ((long long)heads * (2ll * d + dv) > ld_in || (long long)heads * dv > ld_out) return hipErrorInvalidValue;
@@ -46,6 +54,15 @@ hipError_t attention_launch(const T* qkv, T* out, int B, int Tn, int heads, int 
     return hipErrorInvalidValue;
   const bool mfma = attention_path(d, dv) &&
                     attn::attention_vec4((uintptr_t)qkv | (uintptr_t)out, ld_in | ld_out, (int)sizeof(T));
+  if (mask) {
+    if constexpr (!CAUSAL) {
+      MaskedSelfSrc<T> src;
+      src.qkv = qkv; src.Tn = Tn; src.heads = heads; src.d = d; src.dv_ = dv; src.ld_in = ld_in;
+      src.mask = mask;
+      return attn::attention_core_launch<T, MaskedSelfSrc<T>, false, true>(src, out, ld_out, B, mfma, s);
+    }
+    return hipErrorInvalidValue;                      // a padding mask together with the causal mask is not built
+  }
   return attn::attention_core_launch<T, SelfSrc<T>, CAUSAL>(SelfSrc<T>{qkv, Tn, heads, d, dv, ld_in}, out, ld_out, B,
                                                             mfma, s);
 }
@@ -77,6 +94,21 @@ hipError_t attention_causal_f32(const float* qkv, float* out, int B, int T, int 
 hipError_t attention_causal_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, int d, int dv, int ld_in,
                                  int ld_out, hipStream_t s) {
   return attention_launch<bf16, true>(qkv, out, B, T, heads, d, dv, ld_in, ld_out, s);
+}
+
+// The padding-mask instantiations: mask [B][T] fp32, token j of an image is padding iff -1 < mask[j] < 1.  A padded
+// key is not attended, a padded query's row (and every row of an image with no kept key) is zeros; key tiles past
+// an image's last kept key are not loaded.  Same arguments and paths otherwise
+hipError_t attention_masked_f32(const float* qkv, const float* mask, float* out, int B, int T, int heads, int d, int dv,
+                                int ld_in, int ld_out, hipStream_t s) {
+  if (!mask) return hipErrorInvalidValue;
+  return attention_launch<float, false>(qkv, out, B, T, heads, d, dv, ld_in, ld_out, s, mask);
+}
+
+hipError_t attention_masked_bf16(const bf16* qkv, const float* mask, bf16* out, int B, int T, int heads, int d, int dv,
+                                 int ld_in, int ld_out, hipStream_t s) {
+  if (!mask) return hipErrorInvalidValue;
+  return attention_launch<bf16, false>(qkv, out, B, T, heads, d, dv, ld_in, ld_out, s, mask);
 }
 
 }  // namespace adapt

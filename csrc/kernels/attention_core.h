@@ -47,6 +47,20 @@
 // score underflow every visible term).  exp(-inf - -inf) cannot arise: where the running and the tile maximum
 // are both -inf the exponents are taken against 0.  The plain kernel's lane loops run over k <= q.
 //
+// Padding mask (MASKED = true; self-attention only, never with CAUSAL): the policy hands each group a row of nk()
+// floats, and token j is padding iff -1 < mask[j] < 1 (the ids of an Embedding(mask_zero=True): the truncation
+// toward zero the `embedding` kernel applies; a NaN is kept).  A padded token is masked as a key and, as a query,
+// gets a row of zeros (Keras' row there is the plain mean of V; nothing at a kept position reads it).  Prologue:
+// the block reads its group's mask and reduces kend = last kept key + 1 through four LDS words behind the tiles,
+// one barrier that every wave meets before any wave-dependent branch.  The key loop and its prefetch end at kend,
+// a bound that depends on the group alone, so tiles past it are never loaded; a block with kend = 0 writes zero
+// rows and leaves.  A tile's 32 kept flags are fetched one tile ahead with its rows and staged behind them in LDS;
+// a masked key's score becomes -inf in the statement that masks the keys beyond the count.  An interior tile that
+// is wholly masked is computed and masked, not skipped: there m and the tile maximum are both -inf and the
+// exponents are taken against 0, the guard the causal mode has.  A wave whose 16 queries are all padded passes
+// the barriers, skips the MFMAs and stores zeros; 1 / l is 0 where l is 0.  The plain kernel finds kend per wave,
+// its lane loops skip masked keys (their K and V rows are not read), and a padded query's row is zeros.
+//
 // One loop for every size.  A group of at most 64 tokens would fit in LDS whole; staging Swin's 49 tokens as one
 // 64-key tile (no second pass) measured 2 - 11 % slower than the two-tile loop at d = 32 (BASELINE.md
 // "Round 13"): half of the loads then sit in front of the first MFMA with nothing to hide under.
@@ -68,6 +82,7 @@
 //   f32x4 stage(b, isv, row, col)           that vector of key row `row`
 //   const T* q(b, row), k(b, row), v(b, row)   the head's Q, K and V channels of a row
 //   int out_row(b, row)                     the row of `out` that a query row's context goes to
+//   const float* key_mask(b)                MASKED only: the group's nk() mask values
 #pragma once
 #include "kernels.h"
 
@@ -95,13 +110,24 @@ __device__ __forceinline__ float ld(const bf16* p) { return bf2f(*p); }
 __device__ __forceinline__ void st(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st(bf16* p, float v) { *p = f2bf(v); }
 
+// the padding test of a mask value: an id that truncates to 0.  A NaN compares false and is kept
+__device__ __forceinline__ bool mask_kept(float v) { return !(v > -1.f && v < 1.f); }
+
 // DMAX: the head sizes this instantiation holds in registers (d, dv <= DMAX, both multiples of 16).  CAUSAL: query
-// i attends keys j <= i (nq() == nk()); every line it adds is under `if constexpr`
-template <typename T, int DMAX, typename Src, bool CAUSAL = false>
-__global__ __launch_bounds__(256) void attention_mfma_kernel(Src src, T* __restrict__ out, int ld_out, int qtiles) {
+// i attends keys j <= i (nq() == nk()); every line it adds is under `if constexpr`.  MASKED: the padding mask of
+// src.key_mask (nq() == nk(), never with CAUSAL), likewise.  The second launch bound (waves per SIMD) holds the MASKED
+// instantiations at DMAX 32 and 64 to the occupancy the unmasked ones reach on their own, 6 and 4: without it the
+// mask's few extra registers cost them a wave per SIMD (+11 % at 512 tokens, BASELINE.md "Round 19").  DMAX 128 runs
+// 2 waves per SIMD either way.  For every other instantiation 1 leaves the compiler's choice, and their
+// instructions, as they were
+template <typename T, int DMAX, typename Src, bool CAUSAL = false, bool MASKED = false>
+__global__ __launch_bounds__(256, MASKED ? (DMAX == 32 ? 6 : DMAX == 64 ? 4 : 1) : 1) void attention_mfma_kernel(Src src, T* __restrict__ out, int ld_out, int qtiles) {
+  static_assert(!(CAUSAL && MASKED), "a padding mask together with the causal mask is not built");
   constexpr int ND = DMAX / 16;                       // 16-wide slices of d / dv
   constexpr int NST = ATTN_KT * DMAX / 512;           // staged 4-element vectors per thread (K and V together)
-  __shared__ __attribute__((aligned(16))) float smem[2 * ATTN_KT * (DMAX + ATTN_PAD)];
+  constexpr int TILES = 2 * ATTN_KT * (DMAX + ATTN_PAD);
+  // MASKED: behind the tiles the staged tile's ATTN_KT kept flags, then one partial key bound per wave
+  __shared__ __attribute__((aligned(16))) float smem[TILES + (MASKED ? ATTN_KT + 4 : 0)];
   float* sk = smem;
   float* sv = smem + ATTN_KT * (DMAX + ATTN_PAD);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -155,33 +181,77 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(Src src, T* __restr
   const int qtok = q0 + c;
   const bool qok = qtok < Tq;
   const int qrow = qtok;
+  // the keys this block walks: all of them, under the causal mask those up to the last query of its tile, under
+  // the padding mask those up to the group's last kept key.  Block-uniform (from qt or the group, never from
+  // wave): every wave passes both barriers of every iteration
+  int kend = Tk;
+  if constexpr (CAUSAL) kend = min(Tk, (qt + 1) * ATTN_QT);
+  [[maybe_unused]] const float* mk = nullptr;         // MASKED: the group's mask row
+  [[maybe_unused]] bool qkeep = true, wkeep = true;   // MASKED: this lane's query is kept; any query of the wave is
+  if constexpr (MASKED) {
+    mk = src.key_mask(b);
+    int ke = 0;
+    for (int j = tid; j < Tk; j += 256)
+      if (mask_kept(mk[j])) ke = j + 1;               // ascending: the thread's last kept key stays
+#pragma unroll
+    for (int o_ = 32; o_ > 0; o_ >>= 1) ke = max(ke, __shfl_xor(ke, o_));
+    int* sbound = (int*)(smem + TILES + ATTN_KT);
+    if (lane == 0) sbound[wave] = ke;
+    __syncthreads();                                  // before any wave-dependent branch: all four waves meet it
+    kend = __builtin_amdgcn_readfirstlane(max(max(sbound[0], sbound[1]), max(sbound[2], sbound[3])));
+    qkeep = qok && mask_kept(mk[qok ? qtok : 0]);
+    wkeep = __ballot(qkeep) != 0;                     // wave-uniform
+    if (kend == 0) {                                  // no key kept in the group: zero rows, and the block leaves
+      if (!qok) return;
+      T* zrow = out + src.out_row(b, qrow) * ld_out;
+#pragma unroll
+      for (int n = 0; n < ND; ++n)
+        if (16 * n < dv) st4(zrow + h * dv + 16 * n + 4 * g, f32x4{0.f, 0.f, 0.f, 0.f});
+      if (h == heads - 1)
+        for (int cc = heads * dv + g; cc < ld_out; cc += 4) st(zrow + cc, 0.f);
+      return;
+    }
+  }
   f32x4 qf[ND];
 #pragma unroll
   for (int t = 0; t < ND; ++t) {
     qf[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (qok && 16 * t < d) qf[t] = ld4(src.q(b, qrow) + 16 * t + 4 * g);
+    if constexpr (MASKED) {
+      if (qkeep && 16 * t < d) qf[t] = ld4(src.q(b, qrow) + 16 * t + 4 * g);      // a padded query's row is not read
+    } else {
+      if (qok && 16 * t < d) qf[t] = ld4(src.q(b, qrow) + 16 * t + 4 * g);
+    }
   }
   f32x4 o[ND];
 #pragma unroll
   for (int n = 0; n < ND; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.f;                       // l: this lane's keys only, summed over the groups at the end
 
-  // the keys this block walks: all of them, or under the causal mask those up to the last query of its tile.
-  // Block-uniform (from qt, never from wave): every wave passes both barriers of every iteration
-  int kend = Tk;
-  if constexpr (CAUSAL) kend = min(Tk, (qt + 1) * ATTN_QT);
   f32x4 st_[NST];
 #pragma unroll
   for (int j = 0; j < NST; ++j) {
     st_[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (sval[j] && srow[j] < kend) st_[j] = src.stage(b, sisv[j], srow[j], sgcol[j]);
   }
+  [[maybe_unused]] float kp_ = 0.f;                   // MASKED, tid < ATTN_KT: 1 where key k0 + tid is kept
+  if constexpr (MASKED) {
+    if (tid < ATTN_KT && tid < kend) kp_ = mask_kept(mk[tid]) ? 1.f : 0.f;
+  }
   for (int k0 = 0; k0 < kend; k0 += ATTN_KT) {        // the same trip count for every wave of the block
     __syncthreads();                                  // the previous tile has been read
 #pragma unroll
     for (int j = 0; j < NST; ++j)
       if (sval[j]) *(f32x4*)(smem + sloff[j]) = st_[j];
+    if constexpr (MASKED) {
+      if (tid < ATTN_KT) smem[TILES + tid] = kp_;
+    }
     __syncthreads();
+    if constexpr (MASKED) {
+      if (tid < ATTN_KT) {
+        const int r = k0 + ATTN_KT + tid;
+        kp_ = r < kend && mask_kept(mk[r < kend ? r : 0]) ? 1.f : 0.f;
+      }
+    }
     if (k0 + ATTN_KT < kend) {                        // causal: no tile the block will not use is loaded
 #pragma unroll
       for (int j = 0; j < NST; ++j) {
@@ -193,6 +263,9 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(Src src, T* __restr
     if (!active) continue;                            // after both barriers: the wave only helps staging
     if constexpr (CAUSAL) {
       if (k0 > q0 + 15) continue;                     // every key of the tile lies after the wave's 16 queries
+    }
+    if constexpr (MASKED) {
+      if (!wkeep) continue;                           // all 16 queries are padding: zeros are stored after the loop
     }
     // S^T = K Q^T: s[u][i] = score(key k0 + 16 u + 4 g + i, query c)
     f32x4 s[ATTN_KT / 16];
@@ -212,21 +285,26 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(Src src, T* __restr
     }
     float mx = -INFINITY;
 #pragma unroll
-    for (int u = 0; u < ATTN_KT / 16; ++u)
+    for (int u = 0; u < ATTN_KT / 16; ++u) {
+      [[maybe_unused]] f32x4 kf4 = f32x4{1.f, 1.f, 1.f, 1.f};
+      if constexpr (MASKED) kf4 = *(const f32x4*)(smem + TILES + 16 * u + 4 * g);   // the flags of this lane's keys
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         bool masked = k0 + 16 * u + 4 * g + i >= Tk;
         if constexpr (CAUSAL) masked = masked || k0 + 16 * u + 4 * g + i > qtok;    // before the maximum is taken
+        if constexpr (MASKED) masked = masked || kf4[i] == 0.f;
         if (masked) s[u][i] = -INFINITY;
         mx = fmaxf(mx, s[u][i]);
       }
+    }
     mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));               // finite: key k0 is in every tile
+    mx = fmaxf(mx, __shfl_xor(mx, 32));               // finite: key k0 is in every tile (MASKED: unless it is padding)
     const float mn = fmaxf(m, mx);
     float me = mn;                                    // what the exponents are taken against
-    if constexpr (CAUSAL) {
-      // a query that has seen no key yet and sees none in this tile (none with today's tiles: a processed tile
-      // holds key q0 <= qtok): exp(-inf - 0) = 0 for alpha and every p, never exp(-inf - -inf)
+    if constexpr (CAUSAL || MASKED) {
+      // a query that has seen no key yet and sees none in this tile (causal: none with today's tiles, a processed
+      // tile holds key q0 <= qtok; padding mask: every tile before the first kept key): exp(-inf - 0) = 0 for
+      // alpha and every p, never exp(-inf - -inf)
       if (mn == -INFINITY) me = 0.f;
     }
     const float alpha = expf(m - me);                 // 0 on the first tile (m = -inf)
@@ -260,7 +338,15 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(Src src, T* __restr
   l += __shfl_xor(l, 16);
   l += __shfl_xor(l, 32);
   if (!qok) return;
-  const float inv = 1.f / l;
+  float inv = 1.f / l;
+  if constexpr (MASKED) {
+    if (l == 0.f) inv = 0.f;
+    if (!qkeep) {                                     // a padded query: zeros, whatever the arithmetic carried
+      inv = 0.f;
+#pragma unroll
+      for (int n = 0; n < ND; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
   T* orow = out + src.out_row(b, qrow) * ld_out;
 #pragma unroll
   for (int n = 0; n < ND; ++n)
@@ -288,7 +374,7 @@ __device__ __forceinline__ float dot(const T* __restrict__ a, const T* __restric
 }
 
 // Any head sizes, strides and alignment: one wave per (group, head, query); rows = groups x heads x queries.
-template <typename T, typename Src, bool CAUSAL = false>
+template <typename T, typename Src, bool CAUSAL = false, bool MASKED = false>
 __global__ __launch_bounds__(256) void attention_plain_kernel(Src src, T* __restrict__ out, int ld_out, int rows) {
   const int lane = threadIdx.x & 63;
   const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -300,6 +386,48 @@ __global__ __launch_bounds__(256) void attention_plain_kernel(Src src, T* __rest
   const int h = r % heads;
   const typename Src::Block b = src.block(r / heads, h);
   const T* qp = src.q(b, q);
+  if constexpr (MASKED) {
+    // the padding mask: a body of its own, so that the one below stays the text, and the instructions, it was
+    static_assert(!CAUSAL, "a padding mask together with the causal mask is not built");
+    const float* mk = src.key_mask(b);                // the group's mask row
+    int ke = 0;
+    for (int k = lane; k < Tk; k += 64)
+      if (mask_kept(mk[k])) ke = k + 1;
+#pragma unroll
+    for (int o_ = 32; o_ > 0; o_ >>= 1) ke = max(ke, __shfl_xor(ke, o_));
+    Tk = ke;                                          // the last kept key + 1: nothing beyond it is read
+    T* orow = out + src.out_row(b, q) * ld_out;
+    if (Tk == 0 || !mask_kept(mk[q])) {               // wave-uniform: a padded query, or no key kept: a row of zeros
+      for (int cc = lane; cc < dv; cc += 64) st(orow + h * dv + cc, 0.f);
+    } else {
+      float mx = -INFINITY;
+      for (int k = lane; k < Tk; k += 64)
+        if (mask_kept(mk[k])) mx = fmaxf(mx, dot(qp, src.k(b, k), d));
+      mx = wave_max(mx);
+      for (int c0 = 0; c0 < dv; c0 += 64) {
+        const int cc = c0 + lane;
+        float acc = 0.f, ls = 0.f;
+        for (int kb = 0; kb < Tk; kb += 64) {
+          const int k = kb + lane;
+          const bool kin = k < Tk && mask_kept(mk[k < Tk ? k : 0]);
+          const float p = kin ? expf(dot(qp, src.k(b, k), d) - mx) : 0.f;     // a masked key's K row is not read
+          ls += p;
+          const unsigned long long km = __ballot(kin);                          // which of the 64 keys are kept
+          const int nk = min(64, Tk - kb);
+          for (int kk = 0; kk < nk; ++kk) {
+            if (!((km >> kk) & 1)) continue;          // wave-uniform: a masked key's V row is not read
+            const float pk = __shfl(p, kk);
+            if (cc < dv) acc += pk * ld(src.v(b, kb + kk) + cc);
+          }
+        }
+        const float l = wave_sum(ls);                 // > 0: the kept query is itself a kept key
+        if (cc < dv) st(orow + h * dv + cc, acc / l);
+      }
+    }
+    if (h == heads - 1)
+      for (int cc = heads * dv + lane; cc < ld_out; cc += 64) st(orow + cc, 0.f);
+    return;
+  }
   float mx = -INFINITY;
   for (int k = lane; k < Tk; k += 64) mx = fmaxf(mx, dot(qp, src.k(b, k), d));
   mx = wave_max(mx);
@@ -332,22 +460,23 @@ inline bool attention_vec4(uintptr_t ptrs, int strides, int elem_size) {
 
 // Launches `groups` groups of src: the MFMA kernel at the smallest DMAX of 32, 64, 128 that holds both head sizes
 // when `mfma`, else the plain kernel.  The caller has checked the 32-bit ranges.  CAUSAL selects the masked
-// instantiations (the caller has checked nq() == nk()); the default is the kernels as they were.
-template <typename T, typename Src, bool CAUSAL = false>
+// instantiations (the caller has checked nq() == nk()), MASKED those under the padding mask of src.key_mask; the
+// default is the kernels as they were.
+template <typename T, typename Src, bool CAUSAL = false, bool MASKED = false>
 hipError_t attention_core_launch(const Src& src, T* out, int ld_out, int groups, bool mfma, hipStream_t s) {
   if (mfma) {
     const int qtiles = (src.nq() + ATTN_QT - 1) / ATTN_QT;
     const dim3 grid(groups * src.heads * qtiles), block(256);
     const int dm = src.d > src.dv() ? src.d : src.dv();
     if (dm <= 32)
-      hipLaunchKernelGGL((attention_mfma_kernel<T, 32, Src, CAUSAL>), grid, block, 0, s, src, out, ld_out, qtiles);
+      hipLaunchKernelGGL((attention_mfma_kernel<T, 32, Src, CAUSAL, MASKED>), grid, block, 0, s, src, out, ld_out, qtiles);
     else if (dm <= 64)
-      hipLaunchKernelGGL((attention_mfma_kernel<T, 64, Src, CAUSAL>), grid, block, 0, s, src, out, ld_out, qtiles);
+      hipLaunchKernelGGL((attention_mfma_kernel<T, 64, Src, CAUSAL, MASKED>), grid, block, 0, s, src, out, ld_out, qtiles);
     else
-      hipLaunchKernelGGL((attention_mfma_kernel<T, 128, Src, CAUSAL>), grid, block, 0, s, src, out, ld_out, qtiles);
+      hipLaunchKernelGGL((attention_mfma_kernel<T, 128, Src, CAUSAL, MASKED>), grid, block, 0, s, src, out, ld_out, qtiles);
   } else {
     const int rows = groups * src.heads * src.nq();
-    hipLaunchKernelGGL((attention_plain_kernel<T, Src, CAUSAL>), dim3((rows + 3) / 4), dim3(256), 0, s, src, out, ld_out,
+    hipLaunchKernelGGL((attention_plain_kernel<T, Src, CAUSAL, MASKED>), dim3((rows + 3) / 4), dim3(256), 0, s, src, out, ld_out,
                        rows);
   }
   return hipGetLastError();

@@ -452,6 +452,18 @@ PYBIND11_MODULE(_C, m) {
     check(adapt::attention_causal_bf16(P<const bf16>(qkv), P<bf16>(out), B, T, heads, d, dv, ld_in, ld_out, S(s)),
           "attention_causal_bf16");
   });
+  m.def("attention_masked_f32", [](u64 qkv, u64 mask, u64 out, int B, int T, int heads, int d, int dv, int ld_in,
+                                   int ld_out, u64 s) {
+    check(adapt::attention_masked_f32(P<const float>(qkv), P<const float>(mask), P<float>(out), B, T, heads, d, dv,
+                                      ld_in, ld_out, S(s)),
+          "attention_masked_f32");
+  });
+  m.def("attention_masked_bf16", [](u64 qkv, u64 mask, u64 out, int B, int T, int heads, int d, int dv, int ld_in,
+                                    int ld_out, u64 s) {
+    check(adapt::attention_masked_bf16(P<const bf16>(qkv), P<const float>(mask), P<bf16>(out), B, T, heads, d, dv,
+                                       ld_in, ld_out, S(s)),
+          "attention_masked_bf16");
+  });
   m.def("attention_path", &adapt::attention_path);
   m.def("attention_query_tile", &adapt::attention_query_tile);
   m.def("attention_key_tile", &adapt::attention_key_tile);

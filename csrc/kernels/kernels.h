@@ -419,6 +419,12 @@ hipError_t attention_causal_f32(const float* qkv, float* out, int B, int T, int 
                                 int ld_out, hipStream_t s);
 hipError_t attention_causal_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, int d, int dv, int ld_in,
                                  int ld_out, hipStream_t s);
+// the same under a padding mask [B][T] fp32 (token j of an image is padding iff -1 < mask[j] < 1): padded keys are
+// not attended, padded queries get zero rows, the key tiles past an image's last kept key are not loaded
+hipError_t attention_masked_f32(const float* qkv, const float* mask, float* out, int B, int T, int heads, int d, int dv,
+                                int ld_in, int ld_out, hipStream_t s);
+hipError_t attention_masked_bf16(const bf16* qkv, const float* mask, bf16* out, int B, int T, int heads, int d, int dv,
+                                 int ld_in, int ld_out, hipStream_t s);
 int attention_path(int d, int dv);     // 1: MFMA path, 0: plain kernel
 int attention_query_tile();            // queries per block of the MFMA path
 int attention_key_tile();              // keys per LDS tile of the MFMA path

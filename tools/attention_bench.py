@@ -20,6 +20,13 @@ without the mask on the same shape.  The causal launch below the unmasked one is
 above the diagonal are skipped and not merely masked; TF/s is on the T (T + 1) / 2 pairs the mask leaves.
 
     python tools/attention_bench.py --causal [--batch 8]
+
+`--padding` times the padding-mask instantiation on DistilBERT's shapes (12 heads of 64 at 128 and 512 tokens): with
+an all-kept mask against the unmasked entry point (the difference is the prologue's cost), and with random
+right-padded lengths of mean T / 2 against the all-kept time (the gain from the key bound and the skipped query
+waves) and against `scaled_dot_product_attention` with a boolean mask of the same lengths.
+
+    python tools/attention_bench.py --padding [--batch 32]
 """
 import argparse
 import os
@@ -134,14 +141,63 @@ def bench_causal(name, B, T, h, d, reps, rounds):
     return t
 
 
+# (name, tokens, heads, key_dim = value_dim): DistilBERT at its default and its full context
+PADDING_SHAPES = [("distilbert@128", 128, 12, 64), ("distilbert@512", 512, 12, 64)]
+
+
+def bench_padding(name, B, T, h, d, reps, rounds):
+    g = torch.Generator().manual_seed(T)
+    qkv = torch.randn(B * T, 3 * h * d, device="cuda")
+    qkv[:, :h * d] *= d ** -0.5
+    qkv16 = qkv.to(torch.bfloat16)
+    outs = {n: torch.empty(B * T, h * d, device="cuda") for n in ("full", "kept", "padded")}
+    outs16 = {n: torch.empty(B * T, h * d, device="cuda", dtype=torch.bfloat16) for n in ("full", "kept", "padded")}
+    lengths = torch.randint(1, T, (B, 1), generator=g)            # uniform on [1, T - 1]: mean T / 2
+    keep = (torch.arange(T)[None, :] < lengths)
+    all_kept = torch.ones(B, T, device="cuda")
+    padded = keep.float().cuda()                                  # id 1 where kept, 0 where padded
+    q, k, v = (qkv[:, i * h * d:(i + 1) * h * d].reshape(B, T, h, d).permute(0, 2, 1, 3).contiguous() for i in range(3))
+    bmask = (keep[:, None, :, None] & keep[:, None, None, :]).cuda()
+    bmask = bmask | ~keep[:, None, :, None].cuda()                # a padded query attends everything: no NaN row
+
+    def sdpa():
+        return F.scaled_dot_product_attention(q, k, v, attn_mask=bmask, scale=1.0)
+
+    t = interleaved_us({
+        "full": lambda: A.attention(qkv, outs["full"], B, T, h, d, d),
+        "kept": lambda: A.attention(qkv, outs["kept"], B, T, h, d, d, key_mask=all_kept),
+        "padded": lambda: A.attention(qkv, outs["padded"], B, T, h, d, d, key_mask=padded),
+        "full16": lambda: A.attention(qkv16, outs16["full"], B, T, h, d, d),
+        "kept16": lambda: A.attention(qkv16, outs16["kept"], B, T, h, d, d, key_mask=all_kept),
+        "padded16": lambda: A.attention(qkv16, outs16["padded"], B, T, h, d, d, key_mask=padded),
+        "sdpa": sdpa}, reps, rounds)
+    want = sdpa().permute(0, 2, 1, 3).reshape(B * T, h * d)
+    rows = keep.reshape(-1).cuda()
+    diff = (want - outs["padded"])[rows].abs().max().item()
+    same = torch.equal(outs["full"], outs["kept"])
+    print(f"{name:14s} B{B} T{T} h{h} d{d} [{A.attention_path(d, d)}] mean length {lengths.float().mean().item():.0f}: "
+          f"unmasked {t['full']:8.1f} us | all-kept mask {t['kept']:8.1f} us ({t['kept'] / t['full']:4.2f}x, "
+          f"+{t['kept'] - t['full']:.1f} us, bits equal: {same}) | right-padded {t['padded']:8.1f} us "
+          f"({t['padded'] / t['kept']:4.2f}x of all-kept) | bf16 act unmasked {t['full16']:8.1f} us | all-kept "
+          f"{t['kept16']:8.1f} us ({t['kept16'] / t['full16']:4.2f}x) | right-padded {t['padded16']:8.1f} us "
+          f"({t['padded16'] / t['kept16']:4.2f}x) | sdpa bool mask {t['sdpa']:8.1f} us ({t['sdpa'] / t['padded']:5.2f}x "
+          f"ours) | max diff vs sdpa at kept rows {diff:.2e}", flush=True)
+    return t
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--causal", action="store_true", help="the causal kernel on GPT-2 shapes (module docstring)")
+    ap.add_argument("--padding", action="store_true", help="the padding-mask kernel on DistilBERT shapes")
     a = ap.parse_args()
     print(torch.cuda.get_device_name(0))
+    if a.padding:
+        for name, T, h, d in PADDING_SHAPES:
+            bench_padding(name, a.batch, T, h, d, a.reps, a.rounds)
+        return
     if a.causal:
         for name, T, h, d in CAUSAL_SHAPES:
             bench_causal(name, a.batch, T, h, d, a.reps, a.rounds)

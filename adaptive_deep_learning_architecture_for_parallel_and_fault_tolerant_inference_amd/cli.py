@@ -75,8 +75,8 @@ def _model(cfg: AdaptConfig):
 
 
 def _token_models():
-    from .models.zoo import DISTILBERT, GPT
-    return {**GPT, **DISTILBERT}
+    from .models.zoo import DISTILBERT, GPT, LLAMA
+    return {**GPT, **DISTILBERT, **LLAMA}
 
 
 def _request(cfg: AdaptConfig, m, rng, uint8: bool = False) -> np.ndarray:

@@ -43,6 +43,8 @@ OPS = (
     "rescale",    # Keras Rescaling: attrs scale, offset (scalars or per-channel lists)
     "normalization",  # Keras Normalization(axis=-1): weights mean, variance, count
     "layernorm",  # Keras LayerNormalization over the last axis: attrs epsilon; center / scale only when False
+    "rmsnorm",    # Keras 3 RMSNormalization over the last axis: y = x rsqrt(mean(x^2) + epsilon) scale; attrs epsilon
+                  # (Keras default 1e-6); scale only when False; weight scale (C,); a (T, C) or (H, W, C) input
     "layerscale",  # ConvNeXt LayerScale: y = x * gamma (per channel); attrs init_values
     "groupnorm",  # Keras GroupNormalization over (H, W, C / G) of an (H, W, C) map: attrs groups (the resolved G;
                   # Keras' groups=-1, instance norm, is stored as C), epsilon; center / scale only when False
@@ -61,7 +63,15 @@ OPS = (
                   # the edge).  A padded token is not attended as a key; at kept positions this is Keras' implicit
                   # padding mask exactly.  At a padded QUERY position the context row is zeros, where Keras' fully
                   # masked softmax row yields the plain mean of V: outputs at padded positions are defined but
-                  # not Keras'; nothing at a kept position reads them
+                  # not Keras'; nothing at a kept position reads them.
+                  # kv_heads (grouped-query attention, Keras 3 GroupedQueryAttention; one source only, never with
+                  # key_mask): the num_heads query heads share kv_heads key / value heads, head h reads K / V head
+                  # h // (num_heads // kv_heads); the key / value kernels are then (C, kv_heads, d).  Absent means
+                  # num_heads; a layer read from GroupedQueryAttention always stores it.
+                  # rope (stored only when set; one source only, never with key_mask; key_dim even): the max
+                  # wavelength W of a rotary position embedding applied to Q and K between the projection and the
+                  # score product, rotate-half convention, theta(t, i) = t W^(-2i/d) (Keras class
+                  # RotaryGroupedQueryAttention, the project's own)
     "posembed",   # ViT class token + learned position embedding: attrs class_token; (H, W, C) -> (1, T + ct, C)
     "winattn",    # Swin window attention (the project's own layer, Keras class WindowAttention): num_heads, key_dim,
                   # window (M), shift (0 <= s < M), use_bias; (H, W, C) -> (H, W, C), H and W multiples of M.
@@ -154,9 +164,13 @@ def mha_projection(weights, name: str, head: Dict, part: str):
     if part == "out":
         return (weights[f"{name}/attention_output/kernel"].reshape(h * dv, -1),
                 weights.get(f"{name}/attention_output/bias"))
+    # The 1/sqrt(d) query scale stays folded here also under a rotary embedding (the layer's `rope`): the rotation
+    # of the `rope` step is linear, so it commutes with the scale.  Grouped-query attention: K and V have
+    # head["kv_heads"] heads (absent: h), so "qkv" is (C, h d + hkv d + hkv dv)
+    hkv = int(head.get("kv_heads") or h)
     scale = {"query": 1.0 / np.sqrt(np.float64(d)), "key": 1.0, "value": 1.0}
-    width = {"query": d, "key": d, "value": dv}
-    ks = [(weights[f"{name}/{q}/kernel"].astype(np.float64) * scale[q]).reshape(-1, h * width[q])
+    width = {"query": h * d, "key": hkv * d, "value": hkv * dv}
+    ks = [(weights[f"{name}/{q}/kernel"].astype(np.float64) * scale[q]).reshape(-1, width[q])
           for q in MHA_PARTS[part]]
     kernel = np.concatenate(ks, axis=1).astype(np.float32)
     if f"{name}/query/bias" not in weights:
@@ -252,6 +266,8 @@ class Layer:
             c = in_shapes[0][-1]
             keep = (("gamma", self.attrs.get("scale", True)), ("beta", self.attrs.get("center", True)))
             return [(f"{self.name}/{n}", (c,)) for n, k in keep if k]
+        if self.op == "rmsnorm":                # Keras omits scale for scale=False
+            return [(f"{self.name}/scale", (in_shapes[0][-1],))] if self.attrs.get("scale", True) else []
         if self.op == "layerscale":
             return [(f"{self.name}/gamma", (in_shapes[0][-1],))]
         if self.op == "mha":
@@ -259,9 +275,10 @@ class Layer:
             dv = self.attrs.get("value_dim") or d
             # each projection follows its own source
             _, ck, cv = (s[-1] for s in mha_sources(in_shapes, bool(self.attrs.get("key_mask"))))
+            hkv = int(self.attrs.get("kv_heads") or h)
             out = []
-            for part, shp, bshp in (("query", (c, h, d), (h, d)), ("key", (ck, h, d), (h, d)),
-                                    ("value", (cv, h, dv), (h, dv)), ("attention_output", (h, dv, c), (c,))):
+            for part, shp, bshp in (("query", (c, h, d), (h, d)), ("key", (ck, hkv, d), (hkv, d)),
+                                    ("value", (cv, hkv, dv), (hkv, dv)), ("attention_output", (h, dv, c), (c,))):
                 out.append((f"{self.name}/{part}/kernel", shp))
                 if self.attrs.get("use_bias", True):
                     out.append((f"{self.name}/{part}/bias", bshp))
@@ -318,7 +335,8 @@ class Layer:
             _, sk, sv = mha_sources(in_shapes, bool(self.attrs.get("key_mask")))
             tk = _tokens(sk)
             pairs = t * (t + 1) // 2 if self.attrs.get("causal") else t * tk      # (query, key) pairs of the core
-            return (t * c * h * d + tk * sk[-1] * h * d + tk * sv[-1] * h * dv + pairs * h * (d + dv)
+            hkv = int(self.attrs.get("kv_heads") or h)       # the K / V projections have kv_heads heads
+            return (t * c * h * d + tk * sk[-1] * hkv * d + tk * sv[-1] * hkv * dv + pairs * h * (d + dv)
                     + t * h * dv * c)
         if self.op == "winattn":                # projections (h d = C in Swin), scores and P V inside M x M windows
             (hh, ww, c), m = in_shapes[0], self.attrs["window"]
@@ -423,6 +441,28 @@ class Graph:
             if _tokens(sk) != _tokens(sv):
                 raise ValueError(f"mha {layer.name!r}: the key has {_tokens(sk)} tokens and the value "
                                  f"{_tokens(sv)}; they must agree")
+            hq = int(layer.attrs["num_heads"])
+            if "kv_heads" in layer.attrs:
+                hkv = layer.attrs["kv_heads"]
+                if not isinstance(hkv, int) or isinstance(hkv, bool) or hkv < 1 or hq % hkv:
+                    raise ValueError(f"mha {layer.name!r}: kv_heads={hkv!r} must be a positive int that divides "
+                                     f"num_heads={hq}")
+            if "rope" in layer.attrs:
+                w = layer.attrs["rope"]
+                if isinstance(w, bool) or not isinstance(w, (int, float)) or not w > 0:
+                    raise ValueError(f"mha {layer.name!r}: rope is the max wavelength, a positive number, and is "
+                                     f"stored only when set (got {w!r})")
+                if int(layer.attrs["key_dim"]) % 2:
+                    raise ValueError(f"mha {layer.name!r}: a rotary embedding needs an even key_dim (got "
+                                     f"{layer.attrs['key_dim']}): the rotation pairs channel i with i + key_dim / 2")
+            if "kv_heads" in layer.attrs or "rope" in layer.attrs:
+                what = " and ".join(k for k in ("kv_heads", "rope") if k in layer.attrs)
+                if layer.attrs.get("key_mask"):
+                    raise ValueError(f"mha {layer.name!r}: a padding mask (key_mask) together with {what} is not "
+                                     f"built")
+                if len(layer.inputs) != 1:
+                    raise ValueError(f"mha {layer.name!r}: {what} needs one input (self-attention), got "
+                                     f"{len(layer.inputs)} sources")
             if "causal" in layer.attrs:
                 if layer.attrs["causal"] is not True:
                     raise ValueError(f"mha {layer.name!r}: causal is stored only when True (got "
@@ -442,6 +482,13 @@ class Graph:
                 raise ValueError(f"queries {layer.name!r}: needs one input (the batch size), length >= 1, dim >= 1 "
                                  f"and initializer 'normal' or 'zeros' (got {a.get('length')}, {a.get('dim')}, "
                                  f"{a.get('initializer')!r})")
+        if layer.op == "winattn" and ("rope" in layer.attrs or "kv_heads" in layer.attrs):
+            raise ValueError(f"winattn {layer.name!r}: a rotary embedding (rope) or kv_heads on window attention is "
+                             f"not built")
+        if layer.op == "rmsnorm":
+            shp = self.layers[layer.inputs[0]].out_shape if len(layer.inputs) == 1 else ()
+            if len(shp) not in (2, 3):
+                raise ValueError(f"rmsnorm {layer.name!r}: needs one (T, C) or (H, W, C) input, got {tuple(shp)}")
         if layer.op == "embedding":
             shp = self.layers[layer.inputs[0]].out_shape if len(layer.inputs) == 1 else None
             v, c = int(layer.attrs.get("input_dim", 0)), int(layer.attrs.get("output_dim", 0))
@@ -517,7 +564,7 @@ class Graph:
                 raise ValueError(f"crop {layer.name!r}: {a['crop']} leaves nothing of {ins[0]}")
             return (h - t - b, w - l - r, c)
         if layer.op in ("bn", "relu", "softmax", "identity", "act", "rescale", "normalization", "layernorm",
-                        "layerscale", "mha", "winattn", "groupnorm"):
+                        "layerscale", "mha", "winattn", "groupnorm", "rmsnorm"):
             return ins[0]
         if layer.op == "space_to_depth":
             return (ins[0][0] // 2, ins[0][1] // 2, 4 * ins[0][2])
@@ -716,7 +763,7 @@ def holds_token_ids(g: "Graph", name: str) -> bool:
 
 # layers a padding mask travels through unchanged (Keras >= 2.10 and Keras 3 propagate it implicitly); `add`,
 # `binary`, `posembed` and `mha` have rules of their own below; every other consumer drops the mask
-MASK_TRANSPARENT = ("layernorm", "dense", "act", "identity", "layerscale")
+MASK_TRANSPARENT = ("layernorm", "dense", "act", "identity", "layerscale", "rmsnorm")
 
 
 def propagate_masks(g: "Graph") -> Dict[str, str]:
@@ -765,6 +812,9 @@ def propagate_masks(g: "Graph") -> Dict[str, str]:
                                           f"sources; only self-attention takes it")
             if L.attrs.get("causal"):
                 raise NotImplementedError(f"mha {n!r}: a padding mask ({have[0]!r}) together with the causal mask")
+            if "kv_heads" in L.attrs or "rope" in L.attrs:
+                raise NotImplementedError(f"mha {n!r}: a padding mask ({have[0]!r}) together with kv_heads / rope "
+                                          f"(grouped-query or rotary attention)")
             reached[n] = out = got[0]
         elif L.op == "winattn":
             raise NotImplementedError(f"winattn {n!r}: its input carries a padding mask ({have[0]!r})")

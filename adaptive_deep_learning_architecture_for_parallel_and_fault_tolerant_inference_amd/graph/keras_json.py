@@ -70,6 +70,12 @@ def _tensor_name(v):
     return None
 
 
+# the attention classes whose call `_mha_inputs` parses; the grouped-query ones (Keras 3 GroupedQueryAttention and
+# the project's own RotaryGroupedQueryAttention, which rotates Q and K between projection and core) read to an
+# `mha` layer with `kv_heads` (and `rope`) and take one source only
+_ATTENTION_CLASSES = ("MultiHeadAttention", "GroupedQueryAttention", "RotaryGroupedQueryAttention")
+
+
 def _mha_inputs(layer: Dict[str, Any], name: str, cross_attention: bool,
                 causal_attention: bool = False) -> Tuple[List[str], bool]:
     """The tensors a MultiHeadAttention call attends over, as the `mha` op's inputs: [query] for plain
@@ -96,6 +102,10 @@ def _mha_inputs(layer: Dict[str, Any], name: str, cross_attention: bool,
     k = _tensor_name(call.get("key")) if call.get("key") is not None else v
     if q is None or v is None or k is None:
         raise NotImplementedError(f"{name}: MultiHeadAttention call without a query and a value tensor")
+    cls = layer.get("class_name", "MultiHeadAttention")
+    if not q == v == k and cls != "MultiHeadAttention":
+        raise NotImplementedError(f"{name}: {cls} on separate sources (query {q!r}, value {v!r}, key {k!r}); only "
+                                  f"self-attention is built for grouped-query attention")
     if not q == v == k and not cross_attention:
         raise NotImplementedError(f"{name}: cross-attention (query {q!r}, value {v!r}, key {k!r}); "
                                   f"from_keras_json(..., cross_attention=True) reads it")
@@ -115,7 +125,7 @@ def _mha_inputs(layer: Dict[str, Any], name: str, cross_attention: bool,
     return ([q, v] if k == v else [q, v, k]), causal
 
 
-def _check_mha(cfg: Dict[str, Any], in_shape: Tuple[int, ...], name: str) -> None:
+def _check_mha(cfg: Dict[str, Any], in_shape: Tuple[int, ...], name: str, cls: str = "MultiHeadAttention") -> None:
     """What the config may ask for beyond the defaults: attention over all position axes, and an output as
     wide as the input (`in_shape` is per image)."""
     rank = len(in_shape) + 1                          # with the batch axis, as Keras counts
@@ -123,11 +133,11 @@ def _check_mha(cfg: Dict[str, Any], in_shape: Tuple[int, ...], name: str) -> Non
     if axes is not None:
         axes = [axes] if isinstance(axes, int) else list(axes)
         if sorted(a + rank if a < 0 else a for a in axes) != list(range(1, rank - 1)):
-            raise NotImplementedError(f"{name}: MultiHeadAttention attention_axes={cfg['attention_axes']} (only all "
+            raise NotImplementedError(f"{name}: {cls} attention_axes={cfg['attention_axes']} (only all "
                                       f"position axes)")
     osh = cfg.get("output_shape")
     if osh is not None and (list(osh) if isinstance(osh, (list, tuple)) else [osh]) != [in_shape[-1]]:
-        raise NotImplementedError(f"{name}: MultiHeadAttention output_shape={osh} (only the input's "
+        raise NotImplementedError(f"{name}: {cls} output_shape={osh} (only the input's "
                                   f"{in_shape[-1]} channels)")
 
 
@@ -165,12 +175,12 @@ def _activation(act, name: str):
     return act
 
 
-def _check_last_axis(axis, rank: int, name: str) -> None:
-    """LayerNormalization normalises the last axis only: -1, [-1], or that axis given positively
-    (`rank` counts the batch axis: [3] for NHWC, [1] for a (batch, C) input)."""
+def _check_last_axis(axis, rank: int, name: str, cls: str = "LayerNormalization") -> None:
+    """LayerNormalization (and RMSNormalization) normalises the last axis only: -1, [-1], or that axis given
+    positively (`rank` counts the batch axis: [3] for NHWC, [1] for a (batch, C) input)."""
     ax = list(axis) if isinstance(axis, (list, tuple)) else [axis]
     if len(ax) != 1 or ax[0] not in (-1, rank - 1):
-        raise NotImplementedError(f"{name}: LayerNormalization over axis {axis} (only the last axis is supported)")
+        raise NotImplementedError(f"{name}: {cls} over axis {axis} (only the last axis is supported)")
 
 
 def _layers_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str]) -> List[Layer]:
@@ -265,6 +275,27 @@ def _layer_from_keras(cls: str, cfg: Dict[str, Any], name: str, inputs: List[str
             if not cfg.get(k, True):
                 a[k] = False
         return Layer(name, "layernorm", inputs, a)
+    if cls == "RMSNormalization":                      # Keras 3; the axis is checked in from_keras_json
+        a = {"epsilon": float(cfg.get("epsilon", 1e-6))}
+        if not cfg.get("scale", True):
+            a["scale"] = False
+        return Layer(name, "rmsnorm", inputs, a)
+    if cls in ("GroupedQueryAttention", "RotaryGroupedQueryAttention"):
+        # kv_heads is always stored, also when it equals num_heads: the writer then emits the class it read
+        a = {"num_heads": int(cfg["num_query_heads"]), "key_dim": int(cfg["head_dim"]),
+             "kv_heads": int(cfg["num_key_value_heads"]), "use_bias": bool(cfg.get("use_bias", True))}
+        if a["kv_heads"] < 1 or a["num_heads"] % a["kv_heads"]:
+            raise NotImplementedError(f"{name}: {cls} with num_query_heads={a['num_heads']} not a multiple of "
+                                      f"num_key_value_heads={a['kv_heads']}")
+        if cls == "RotaryGroupedQueryAttention":       # frequency scaling is not built
+            a["rope"] = float(cfg.get("rope_max_wavelength", 10000.0))
+            if a["key_dim"] % 2:
+                raise NotImplementedError(f"{name}: {cls} with an odd head_dim={a['key_dim']} (the rotation pairs "
+                                          f"channel i with i + head_dim / 2)")
+            if cfg.get("rope_scaling_factor") not in (None, 1, 1.0):
+                raise NotImplementedError(f"{name}: {cls} with rope_scaling_factor={cfg['rope_scaling_factor']} "
+                                          f"(frequency scaling is not built)")
+        return Layer(name, "mha", inputs, a)
     if cls == "GroupNormalization":
         axis = cfg.get("axis", -1)
         axis = axis[0] if isinstance(axis, (list, tuple)) and len(axis) == 1 else axis
@@ -395,14 +426,14 @@ def from_keras_json(s, cross_attention: bool = False, causal_attention: bool = F
     g = Graph(cfg.get("name", "model"))
     for ld in cfg["layers"]:
         name = ld.get("name") or ld["config"]["name"]
-        mha = ld["class_name"] == "MultiHeadAttention"
+        mha = ld["class_name"] in _ATTENTION_CLASSES
         inputs, causal = (_mha_inputs(ld, name, cross_attention, causal_attention) if mha
                           else (_inbound_names(ld), False))
         if mha:
             for i in inputs:
                 if i not in g.layers:
                     raise ValueError(f"layer {name!r} consumes unknown tensor {i!r}")
-            _check_mha(ld["config"], g.layers[inputs[0]].out_shape, name)      # against the query
+            _check_mha(ld["config"], g.layers[inputs[0]].out_shape, name, ld["class_name"])      # against the query
         if ld["class_name"] == "Embedding":
             shp = g.layers[inputs[0]].out_shape if len(inputs) == 1 and inputs[0] in g.layers else None
             il = ld["config"].get("input_length")
@@ -417,8 +448,9 @@ def from_keras_json(s, cross_attention: bool = False, causal_attention: bool = F
             if causal:
                 layer.attrs["causal"] = True
             g.add(layer)
-        if ld["class_name"] == "LayerNormalization":
-            _check_last_axis(ld["config"].get("axis", -1), len(g.layers[name].out_shape) + 1, name)
+        if ld["class_name"] in ("LayerNormalization", "RMSNormalization"):
+            _check_last_axis(ld["config"].get("axis", -1), len(g.layers[name].out_shape) + 1, name,
+                             ld["class_name"])
 
     def names(v) -> List[str]:
         if isinstance(v, list) and v and isinstance(v[0], str):
@@ -473,6 +505,19 @@ def _keras_layer(L: Layer, g: Graph) -> Dict[str, Any]:
         cls = "GroupNormalization"
         cfg.update(groups=a["groups"], axis=-1, epsilon=a.get("epsilon", 1e-3), center=a.get("center", True),
                    scale=a.get("scale", True))
+    elif L.op == "rmsnorm":
+        cls = "RMSNormalization"
+        cfg.update(axis=-1, epsilon=a.get("epsilon", 1e-6), scale=a.get("scale", True))
+    elif L.op == "mha" and ("kv_heads" in a or "rope" in a):
+        if a.get("value_dim") not in (None, a["key_dim"]):
+            raise NotImplementedError(f"mha {L.name!r}: GroupedQueryAttention has one head_dim; value_dim="
+                                      f"{a['value_dim']} != key_dim={a['key_dim']} cannot be written")
+        cls = "RotaryGroupedQueryAttention" if "rope" in a else "GroupedQueryAttention"
+        cfg.update(head_dim=a["key_dim"], num_query_heads=a["num_heads"],
+                   num_key_value_heads=a.get("kv_heads", a["num_heads"]), dropout=0.0,
+                   use_bias=a.get("use_bias", True))
+        if "rope" in a:
+            cfg.update(rope_max_wavelength=float(a["rope"]))
     elif L.op == "mha":
         cls = "MultiHeadAttention"
         cfg.update(num_heads=a["num_heads"], key_dim=a["key_dim"], value_dim=a.get("value_dim") or a["key_dim"],

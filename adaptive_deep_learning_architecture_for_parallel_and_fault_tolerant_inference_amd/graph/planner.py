@@ -160,7 +160,18 @@ def layer_costs(g: Graph, batch: int = 32, hw: Optional[HwModel] = None) -> Dict
         # planner cannot know the lengths, so the key tiles its kernel skips are not counted out (uncalibrated).
         # posembed: its traffic.
         # winattn: 4 H W C^2 + 2 H W M^2 C MACs (projections and the window-local core); space_to_depth: its traffic
+        # rmsnorm: its traffic and one launch, as layernorm.  Uncalibrated: no planner fit includes a model with
+        # an RMSNormalization.  An mha with kv_heads counts the narrower K / V projections (graph/ir.py).
         t = max(2.0 * macs / hw.mfma_flops, byts / hw.hbm_bw) + hw.launch_s
+        if L.op == "mha" and L.attrs.get("rope"):
+            # the `rope` step: the [Q | K | V] projection buffer read and written once, one launch.  Uncalibrated:
+            # no planner fit includes a model with a rotary embedding
+            h, d = int(L.attrs["num_heads"]), int(L.attrs["key_dim"])
+            hkv, dv = int(L.attrs.get("kv_heads") or h), int(L.attrs.get("value_dim") or d)
+            tokens = 1
+            for v in L.out_shape[:-1]:
+                tokens *= v
+            t += 2.0 * tokens * (h * d + hkv * (d + dv)) * hw.act_bytes * batch / hw.hbm_bw + hw.launch_s
         out[n] = t
     return out
 

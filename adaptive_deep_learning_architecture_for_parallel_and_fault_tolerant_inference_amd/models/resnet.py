@@ -146,6 +146,9 @@ def init_weights(g: Graph, seed: int = 0, layers: Optional[List[str]] = None) ->
                     "beta": (rng.standard_normal(c) * 0.05).astype(np.float32)}
             for wname, _ in specs:                 # scale=False / center=False drop gamma / beta
                 out[wname] = vals[wname.rsplit("/", 1)[1]]
+        elif L.op == "rmsnorm":
+            for wname, shp in specs:               # scale=False drops the weight
+                out[wname] = rng.uniform(0.8, 1.2, shp[0]).astype(np.float32)
         elif L.op in ("mha", "winattn"):
             # projections: fan-in C (h * dv for the output projection), biases zero; a window attention's
             # relative position bias table: N(0, 0.02)

@@ -38,6 +38,9 @@ Not from `keras.applications` (models whose output is a map, not a class vector)
   decoder whose MultiHeadAttention layers take separate query / key / value tensors, LearnedQueries for the object
   queries and the position table; a 480 x 640 x 3 image to (1, 100, 96) class logits and boxes, 41,759,968
   parameters (Keras counting: BatchNormalization statistics, conv biases and the two tables included).
+* Llama (`tinyllama_1_1b`, `llama2_7b`, test size `llama_micro`): RMSNormalization, a rotary position embedding on
+  Q and K, causal grouped-query attention and the SwiGLU MLP, no bias anywhere; (T,) token ids to the next-token
+  logits, the published 1,100,048,384 and 6,738,415,616 parameters.
 """
 from __future__ import annotations
 
@@ -831,7 +834,67 @@ def build_distilbert(name: str = "distilbert_base", classes: Optional[int] = Non
     return with_key_masks(g)
 
 
+# ------------------------------------------------------------------- Llama
+# name -> (depth, width, heads, kv_heads, ffn, vocabulary, default tokens, eps, rope max wavelength); micro: same
+# naming / structure, for fast tests (head size 16, so the attention core's MFMA path, with g = 2 query heads per
+# key / value head; 40 tokens: one above the attention key tile plus 7, below the query tile)
+LLAMA = {
+    "tinyllama_1_1b": (22, 2048, 32, 4, 5632, 32000, 128, 1e-5, 10000.0),
+    "llama2_7b": (32, 4096, 32, 32, 11008, 32000, 128, 1e-5, 10000.0),
+    "llama_micro": (2, 64, 4, 2, 176, 97, 40, 1e-5, 10000.0),
+}
+
+
+def build_llama(name: str = "tinyllama_1_1b", classes: Optional[int] = None, input_shape=None,
+                all_positions: bool = False) -> Graph:
+    """The Llama family (Touvron et al. 2023; TinyLlama 1.1B and Llama 2 7B as published) as a flat pre-norm
+    graph without a bias anywhere, the full-sequence forward pass: the (T,) token ids (carried as float32) through
+    an Embedding; `depth` blocks of RMSNormalization -> causal RotaryGroupedQueryAttention -> Add and
+    RMSNormalization -> gate = Dense(F) -> swish, up = Dense(F), Multiply -> down = Dense(C) -> Add on a (1, T, C)
+    token map; the last token cropped out (`all_positions=True` keeps every token), the final RMSNormalization
+    and `lm_head`, a Dense without bias onto the vocabulary: the next-token logits.  There is no position table:
+    the attention layers rotate Q and K (`rope`, the max wavelength).  `classes` is the vocabulary.  With
+    kv_heads == heads (llama2_7b) the layer is plain multi-head attention behind the rope step.  No KV cache and
+    no incremental decoding; frequency scaling (Llama 3) is not built."""
+    depth, width, heads, kv_heads, ffn, vocab, default_tokens, eps, wavelength = LLAMA[name]
+    vocab = int(classes or vocab)
+    shape = tuple(input_shape or (default_tokens,))
+    if len(shape) != 1 or shape[0] < 1:
+        raise ValueError(f"{name}: input {shape} is not (T,) token ids with T >= 1")
+    tokens = shape[0]
+    g = Graph(name)
+    x = g.add(Layer("input_1", "input", [], {"shape": shape}))
+    x = g.add(Layer(f"{name}_embed_tokens", "embedding", [x], {"input_dim": vocab, "output_dim": width}))
+    # the (1, T, C) token map every other transformer of the zoo runs on (there a position embedding makes it);
+    # the same elements in the same order, so no plan step
+    x = g.add(Layer(f"{name}_tokens", "reshape", [x], {"shape": (1, tokens, width)}))
+
+    def norm(x: str, nm: str) -> str:
+        return g.add(Layer(nm, "rmsnorm", [x], {"epsilon": eps}))
+
+    for i in range(depth):
+        nm = f"{name}_block_{i}"
+        attrs = {"num_heads": heads, "key_dim": width // heads, "use_bias": False, "causal": True,
+                 "kv_heads": kv_heads, "rope": wavelength}
+        y = g.add(Layer(f"{nm}_attn", "mha", [norm(x, f"{nm}_input_norm")], attrs))
+        x = g.add(Layer(f"{nm}_add1", "add", [x, y]))
+        h = norm(x, f"{nm}_post_attention_norm")
+        gate = g.add(Layer(f"{nm}_mlp_gate", "dense", [h], {"units": ffn, "use_bias": False}))
+        gate = g.add(Layer(f"{nm}_mlp_swish", "act", [gate], {"fn": "swish"}))
+        up = g.add(Layer(f"{nm}_mlp_up", "dense", [h], {"units": ffn, "use_bias": False}))
+        y = g.add(Layer(f"{nm}_mlp_mul", "binary", [gate, up], {"fn": "mul"}))
+        y = g.add(Layer(f"{nm}_mlp_down", "dense", [y], {"units": width, "use_bias": False}))
+        x = g.add(Layer(f"{nm}_add2", "add", [x, y]))
+    if not all_positions:
+        x = g.add(Layer(f"{name}_last", "crop", [x], {"crop": ((0, 0), (tokens - 1, 0))}))      # the last token
+    x = norm(x, f"{name}_norm")
+    g.add(Layer("lm_head", "dense", [x], {"units": vocab, "use_bias": False}))
+    g.output_names = ["lm_head"]
+    return g
+
+
 BUILDERS: Dict[str, Callable[..., Graph]] = {
+    **{n: (lambda n: lambda **kw: build_llama(n, **kw))(n) for n in LLAMA},
     **{n: (lambda n: lambda **kw: build_distilbert(n, **kw))(n) for n in DISTILBERT},
     **{n: (lambda n: lambda **kw: build_gpt(n, **kw))(n) for n in GPT},
     **{n: (lambda n: lambda **kw: build_detr(n, **kw))(n) for n in DETR},

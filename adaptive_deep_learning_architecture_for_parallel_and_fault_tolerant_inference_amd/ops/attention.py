@@ -2,7 +2,7 @@
 scheme of all three), the attention core with separate query /
 key / value sources (csrc/kernels/cross_attention.hip), Swin's window attention core and its bias packer
 (csrc/kernels/window_attention.hip), and the ViT class token / position embedding, learned-queries and token
-embedding kernels (csrc/kernels/layers.hip).
+embedding kernels and the rotary position embedding with its host-side table (csrc/kernels/layers.hip).
 
 Shapes, dtypes, strides and the 32-bit index range are checked here before any launch; a shape the kernels do
 not take is an error, never a fall-back to torch.
@@ -31,7 +31,7 @@ def attention_path(key_dim: int, value_dim: int) -> str:
 
 def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, tokens: int, heads: int, key_dim: int,
               value_dim: Optional[int] = None, stream=None, causal: bool = False,
-              key_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+              key_mask: Optional[torch.Tensor] = None, kv_heads: Optional[int] = None) -> torch.Tensor:
     """out = softmax(Q K^T) V per (image, head); `causal`: query i attends keys j <= i only (Keras'
     use_causal_mask), on the kernels' masked instantiations, which skip the key tiles above the diagonal.  qkv [..., ld_in] holds batch * tokens rows of [Q | K | V]
     (head-major inside each part; Q already scaled by 1/sqrt(key_dim)), out [..., ld_out] gets heads * value_dim
@@ -40,19 +40,27 @@ def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, tokens: int, hea
     padding mask of batch * tokens fp32 values on the device (never with `causal`); token j of an image is padding
     iff -1 < key_mask[j] < 1, the ids of an Embedding(mask_zero=True).  A padded key is not attended, a padded
     query's row and every row of an image with no kept key are zeros, and the key tiles past an image's last kept
-    token are not loaded (the kernels' masked instantiations)."""
+    token are not loaded (the kernels' masked instantiations).  `kv_heads` (grouped-query attention): the `heads`
+    query heads share kv_heads key / value heads, head h reads K / V head h // (heads // kv_heads), and a row is
+    [Q: heads x key_dim | K: kv_heads x key_dim | V: kv_heads x value_dim]; given and different from `heads` it
+    runs the gqa entry points (plain or causal, never with `key_mask`), else the launch is the one it always was."""
     dv = int(value_dim or key_dim)
     B, T, h, d = int(batch), int(tokens), int(heads), int(key_dim)
+    hkv = h if kv_heads is None else int(kv_heads)
+    if hkv < 1 or h < 1 or h % hkv:
+        raise ValueError(f"attention: kv_heads={kv_heads} must be positive and divide the {h} heads")
+    if hkv != h and key_mask is not None:
+        raise ValueError("attention: a padding mask together with kv_heads is not built")
     if qkv.dtype not in (torch.float32, torch.bfloat16):
         raise ValueError(f"attention: fp32 or bf16 tensors, got {qkv.dtype}")
     _chk(qkv, qkv.dtype, "qkv"); _chk(out, qkv.dtype, "out")
     if min(B, T, h, d, dv) < 1:
         raise ValueError(f"attention: batch, tokens, heads and head sizes must be positive ({B}, {T}, {h}, {d}, {dv})")
     ld_in, ld_out = qkv.shape[-1], out.shape[-1]
-    if (qkv.numel() != B * T * ld_in or out.numel() != B * T * ld_out or ld_in < h * (2 * d + dv)
+    if (qkv.numel() != B * T * ld_in or out.numel() != B * T * ld_out or ld_in < h * d + hkv * (d + dv)
             or ld_out < h * dv):
         raise ValueError(f"attention: qkv{tuple(qkv.shape)} out{tuple(out.shape)} do not hold {B} x {T} rows of "
-                         f"{h} heads ({d}, {dv})")
+                         f"{h} heads ({d}, {dv})" + (f" over {hkv} key / value heads" if hkv != h else ""))
     if max(qkv.numel(), out.numel(), B * h * T) >= 2 ** 31:
         raise ValueError("attention: tensors must hold fewer than 2^31 elements (32-bit index math)")
     if key_mask is not None:
@@ -64,11 +72,67 @@ def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, tokens: int, hea
         fn = kernels().attention_masked_f32 if qkv.dtype == torch.float32 else kernels().attention_masked_bf16
         fn(ptr(qkv), ptr(key_mask), ptr(out), B, T, h, d, dv, int(ld_in), int(ld_out), stream_handle(stream))
         return out
+    if hkv != h:
+        k, f32 = kernels(), qkv.dtype == torch.float32
+        if causal:
+            fn = k.attention_gqa_causal_f32 if f32 else k.attention_gqa_causal_bf16
+        else:
+            fn = k.attention_gqa_f32 if f32 else k.attention_gqa_bf16
+        fn(ptr(qkv), ptr(out), B, T, h, hkv, d, dv, int(ld_in), int(ld_out), stream_handle(stream))
+        return out
     if causal:
         fn = kernels().attention_causal_f32 if qkv.dtype == torch.float32 else kernels().attention_causal_bf16
     else:
         fn = kernels().attention_f32 if qkv.dtype == torch.float32 else kernels().attention_bf16
     fn(ptr(qkv), ptr(out), B, T, h, d, dv, int(ld_in), int(ld_out), stream_handle(stream))
+    return out
+
+
+def rope_table(tokens: int, key_dim: int, max_wavelength: float = 10000.0, device=None) -> torch.Tensor:
+    """The cos / sin table of the rotary position embedding, fp32 [2][T][d/2]: table[0, t, i] = cos(theta),
+    table[1, t, i] = sin(theta) with theta(t, i) = t * W^(-2i/d).  The angles, their cosines and sines are computed
+    in float64 on the host and rounded once to fp32 (an fp32 angle t * freq is already off by 5e-4 rad at
+    t = 8192); the table stays fp32 in both precisions.  Frequency scaling (keras_hub's scaling_factor, Llama 3's
+    banded scaling) is not built: it would change this function alone."""
+    T, d, W = int(tokens), int(key_dim), float(max_wavelength)
+    if T < 1 or d < 2 or d % 2 or not W > 0:
+        raise ValueError(f"rope_table: tokens >= 1, an even key_dim >= 2 and a positive wavelength "
+                         f"(got {tokens}, {key_dim}, {max_wavelength})")
+    i = np.arange(d // 2, dtype=np.float64)
+    theta = np.arange(T, dtype=np.float64)[:, None] * np.power(np.float64(W), -2.0 * i / d)[None, :]
+    t = torch.from_numpy(np.stack([np.cos(theta), np.sin(theta)]).astype(np.float32))
+    return t.to(device) if device is not None else t
+
+
+def rope(x: torch.Tensor, table: torch.Tensor, out: torch.Tensor, tokens: int, heads: int, key_dim: int,
+         value_dim: Optional[int] = None, kv_heads: Optional[int] = None, stream=None) -> torch.Tensor:
+    """Rotary position embedding on an attention layer's projection buffer, out of place
+    (csrc/kernels/layers.hip): x and out [..., ld] hold rows of [Q: heads x key_dim | K: kv_heads x key_dim |
+    V: kv_heads x value_dim]; the Q and K heads are rotated by the rotate-half convention with the angles of
+    `table` (`rope_table`, fp32 [2][tokens][key_dim / 2]) at position row % tokens, V is copied and the rest of a
+    row is written as zeros.  fp32 or bf16 (both tensors alike); key_dim must be even."""
+    T, h, d = int(tokens), int(heads), int(key_dim)
+    dv = int(value_dim or key_dim)
+    hkv = h if kv_heads is None else int(kv_heads)
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"rope: fp32 or bf16 tensors, got {x.dtype}")
+    if d < 2 or d % 2:
+        raise ValueError(f"rope: key_dim={d} must be even (the rotation pairs channel i with i + key_dim / 2)")
+    _chk(x, x.dtype, "x"); _chk(out, x.dtype, "out"); _chk(table, torch.float32, "table")
+    if min(T, h, hkv, dv) < 1:
+        raise ValueError(f"rope: tokens, heads and head sizes must be positive ({T}, {h}, {hkv}, {d}, {dv})")
+    ld = x.shape[-1]
+    rows = x.numel() // ld
+    if (out.shape[-1] != ld or out.numel() != x.numel() or rows % T or ld < (h + hkv) * d + hkv * dv
+            or tuple(table.shape) != (2, T, d // 2)):
+        raise ValueError(f"rope: x{tuple(x.shape)} out{tuple(out.shape)} table{tuple(table.shape)} do not hold rows "
+                         f"of {h} + {hkv} heads of {d} and {hkv} of {dv} at {T} positions")
+    if x.data_ptr() == out.data_ptr():
+        raise ValueError("rope: the step is out of place; x and out must differ")
+    if max(x.numel(), table.numel()) >= 2 ** 31:
+        raise ValueError("rope: tensors must hold fewer than 2^31 elements (32-bit index math)")
+    fn = kernels().rope_f32 if x.dtype == torch.float32 else kernels().rope_bf16
+    fn(ptr(x), ptr(table), ptr(out), rows, T, h, hkv, d, dv, int(ld), stream_handle(stream))
     return out
 
 

@@ -404,6 +404,30 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: tor
     return out
 
 
+def rmsnorm_f32(x: torch.Tensor, scale: torch.Tensor, out: torch.Tensor, eps: float, stream=None) -> torch.Tensor:
+    """fp32 RMSNormalization over the last axis (csrc/kernels/layernorm.hip): y = x rsqrt(mean(x^2) + eps) scale,
+    x [..., C], scale [C]."""
+    _chk(x, torch.float32, "x"); _chk(out, torch.float32, "out"); _chk(scale, torch.float32, "scale")
+    C = x.shape[-1]
+    if out.shape != x.shape or scale.numel() != C or x.numel() == 0 or x.numel() // C >= 2 ** 31:
+        raise ValueError(f"rmsnorm_f32: bad shapes x{tuple(x.shape)} out{tuple(out.shape)} scale{tuple(scale.shape)}")
+    kernels().rmsnorm_f32(ptr(x), ptr(scale), ptr(out), x.numel() // C, C, float(eps), stream_handle(stream))
+    return out
+
+
+def rmsnorm(x: torch.Tensor, scale: torch.Tensor, out: torch.Tensor, C: int, eps: float, stream=None) -> torch.Tensor:
+    """bf16 RMSNormalization over the first C of the Cp stored channels: x [..., Cp], scale fp32 [Cp].  Channels
+    C..Cp-1 are layout padding: out of the mean whatever they hold, zeros in `out`."""
+    _chk(x, name="x"); _chk(out, name="out"); _chk(scale, torch.float32, "scale")
+    Cp = x.shape[-1]
+    if (out.shape != x.shape or scale.numel() != Cp or Cp % 8 or not 0 < C <= Cp or x.numel() == 0
+            or x.numel() // Cp >= 2 ** 31):
+        raise ValueError(f"rmsnorm: bad shapes x{tuple(x.shape)} out{tuple(out.shape)} scale{tuple(scale.shape)} C={C}")
+    kernels().rmsnorm_bf16(ptr(x), ptr(scale), ptr(out), x.numel() // Cp, Cp, int(C), float(eps),
+                           stream_handle(stream))
+    return out
+
+
 GROUPNORM_PATHS = {0: "scalar split", 1: "vector split", 2: "vector single launch"}
 
 

@@ -147,6 +147,8 @@ class ReferenceExecutor:
             c = ins[0].shape[-1]
             return F.layer_norm(ins[0], (c,), self.w.get(f"{L.name}/gamma"), self.w.get(f"{L.name}/beta"),
                                 a.get("epsilon", 1e-3))
+        if L.op == "rmsnorm":
+            return F.rms_norm(ins[0], (ins[0].shape[-1],), self.w.get(f"{L.name}/scale"), a.get("epsilon", 1e-6))
         if L.op == "groupnorm":
             # the library normalises over (C / G, H, W) of an NCHW tensor.  A contiguous copy: on the strided
             # (channels-last) view its CPU kernel takes a one-pass form that loses every digit at mean >> sigma
@@ -165,6 +167,21 @@ class ReferenceExecutor:
             q = (torch.einsum("btc,chd->bthd", x, w("query")) + b("query")) * (1.0 / float(a["key_dim"]) ** 0.5)
             k = torch.einsum("btc,chd->bthd", xk, w("key")) + b("key")
             v = torch.einsum("btc,chd->bthd", xv, w("value")) + b("value")
+            if a.get("rope"):
+                # rotary embedding, rotate-half convention, at position t of the image: the angles in float64,
+                # rounded to the tensors' dtype (the 1/sqrt(d) scale above commutes with the rotation)
+                d = int(a["key_dim"])
+                inv = float(a["rope"]) ** (-2.0 * torch.arange(d // 2, dtype=torch.float64) / d)
+                th = torch.arange(q.shape[1], dtype=torch.float64)[:, None] * inv[None, :]
+                cs, sn = (f(th).to(q.dtype).to(q.device)[None, :, None, :] for f in (torch.cos, torch.sin))
+
+                def rot(t):
+                    t1, t2 = t[..., :d // 2], t[..., d // 2:]
+                    return torch.cat([t1 * cs - t2 * sn, t2 * cs + t1 * sn], dim=-1)
+                q, k = rot(q), rot(k)
+            if k.shape[2] != q.shape[2]:        # grouped-query attention: head h reads K / V head h // g
+                k = k.repeat_interleave(q.shape[2] // k.shape[2], dim=2)
+                v = v.repeat_interleave(q.shape[2] // v.shape[2], dim=2)
             s = torch.einsum("bqhd,bkhd->bhqk", q, k)
             if a.get("causal"):                 # Keras _compute_causal_mask: query i attends keys j <= i
                 t = s.shape[-1]

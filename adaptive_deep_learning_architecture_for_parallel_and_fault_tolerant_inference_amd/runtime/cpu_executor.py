@@ -56,7 +56,7 @@ class CpuExecutor:
 
     KINDS = ("conv", "gconv", "dwconv", "maxpool", "avgpool", "bn", "add", "relu", "act", "binary", "affine", "gmp", "copy",
              "concat", "gap", "dense", "softmax", "pad", "layernorm", "deconv", "upsample", "crop", "attention",
-             "posembed", "winattn", "space_to_depth", "groupnorm", "queries", "embedding")
+             "posembed", "winattn", "space_to_depth", "groupnorm", "queries", "embedding", "rmsnorm", "rope")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], outputs: Optional[Sequence[str]] = None):
         self.g = g
@@ -86,6 +86,7 @@ class CpuExecutor:
     def _pack(self, weights: Dict[str, np.ndarray]) -> None:
         cob = int(self.mod.COB)
         self.packed: Dict[int, tuple] = {}
+        self._rope_tables: Dict[tuple, np.ndarray] = {}      # one cos / sin table per (T, d, W)
         for i, st in enumerate(self.steps):
             if st.kind == "conv":
                 k, b = self._folded(weights, st.p)
@@ -121,6 +122,15 @@ class CpuExecutor:
                 c = self.g.layers[st.p["layer"]].out_shape[-1]
                 self.packed[i] = tuple(np.ascontiguousarray(weights.get(f"{st.p['layer']}/{w}", d), np.float32)
                                        for w, d in (("gamma", np.ones(c)), ("beta", np.zeros(c))))
+            elif st.kind == "rmsnorm":           # Keras' default for scale=False
+                c = self.g.layers[st.p["layer"]].out_shape[-1]
+                self.packed[i] = (np.ascontiguousarray(weights.get(f"{st.p['layer']}/scale", np.ones(c)), np.float32),)
+            elif st.kind == "rope":              # the cos / sin table, one per (T, d, W)
+                key = (int(st.p["tokens"]), int(st.p["key_dim"]), float(st.p["rope"]))
+                if key not in self._rope_tables:
+                    from ..ops.attention import rope_table
+                    self._rope_tables[key] = rope_table(*key).numpy()
+                self.packed[i] = (self._rope_tables[key],)
             elif st.kind == "posembed":
                 n = st.p["layer"]
                 cls = weights[f"{n}/class_token"].reshape(-1) if st.p["class_token"] else None
@@ -194,6 +204,12 @@ class CpuExecutor:
         elif k == "layernorm":
             gm, bt = self.packed[i]
             m.layernorm(ins[0], gm, bt, y, float(p["eps"]))
+        elif k == "rmsnorm":
+            m.rmsnorm(ins[0], self.packed[i][0], y, float(p["eps"]))
+        elif k == "rope":
+            m.rope(ins[0].reshape(-1, ins[0].shape[-1]), self.packed[i][0], y.reshape(-1, y.shape[-1]),
+                   int(p["tokens"]), int(p["heads"]), int(p.get("kv_heads", p["heads"])), int(p["key_dim"]),
+                   int(p["value_dim"]))
         elif k == "groupnorm":
             gm, bt = self.packed[i]
             m.groupnorm(ins[0], gm, bt, y, int(p["groups"]), float(p["eps"]), int(p["act"]), 0.3)
@@ -208,7 +224,8 @@ class CpuExecutor:
         elif k == "attention":
             m.attention(ins[0].reshape(-1, ins[0].shape[-1]), y.reshape(-1, y.shape[-1]), batch, int(p["tokens"]),
                         int(p["heads"]), int(p["key_dim"]), int(p["value_dim"]), bool(p.get("causal")),
-                        np.ascontiguousarray(ins[1], np.float32).reshape(-1) if p.get("key_mask") else None)
+                        np.ascontiguousarray(ins[1], np.float32).reshape(-1) if p.get("key_mask") else None,
+                        int(p.get("kv_heads", 0)))
         elif k == "embedding":
             m.embedding(ins[0], self.packed[i][0], y)
         elif k == "winattn":

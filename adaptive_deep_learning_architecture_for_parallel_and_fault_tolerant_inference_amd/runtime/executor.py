@@ -88,7 +88,7 @@ class SliceExecutor:
     FP32_KINDS = ("conv", "pair", "dense", "maxpool", "gap", "softmax", "add", "bn", "relu", "pad", "copy",
                   "dwconv", "avgpool", "concat", "act", "binary", "affine", "stem_f32", "gconv", "layernorm",
                   "deconv", "upsample", "crop", "attention", "posembed", "winattn", "space_to_depth", "groupnorm",
-                  "queries", "embedding")
+                  "queries", "embedding", "rmsnorm", "rope")
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], batch: int, device="cuda",
                  outputs: Optional[Sequence[str]] = None, tune: bool = False, num_sets: int = 1,
@@ -166,6 +166,17 @@ class SliceExecutor:
     def _pack_weights(self, weights: Dict[str, np.ndarray]) -> None:
         self.packed: Dict[int, object] = {}
         dev = self.device
+        # rotary embedding tables, prepared once: one fp32 [2][T][d/2] table per (T, d, W), shared by every layer
+        # that has them
+        self._rope_tables: Dict[Tuple[int, int, float], torch.Tensor] = {}
+        for i, st in enumerate(self.steps):
+            if st.kind == "rmsnorm":             # fp32 [cp] in both precisions, the bf16 padding channels 0
+                self.packed[i] = self._pack_rmsnorm(weights, st, self.shape_of(st.out)[-1])
+            elif st.kind == "rope":
+                key = (int(st.p["tokens"]), int(st.p["key_dim"]), float(st.p["rope"]))
+                if key not in self._rope_tables:
+                    self._rope_tables[key] = attn_ops.rope_table(*key, device=dev)
+                self.packed[i] = self._rope_tables[key]
         if self.fp32:
             self._pack_weights_f32(weights)
             return
@@ -381,7 +392,11 @@ class SliceExecutor:
             p = st.p
             attn_ops.attention(b[st.ins[0]], b[st.out], self.batch, p["tokens"], p["heads"], p["key_dim"],
                                p["value_dim"], stream=stream, causal=bool(p.get("causal")),
-                               key_mask=b[st.ins[1]] if p.get("key_mask") else None)
+                               key_mask=b[st.ins[1]] if p.get("key_mask") else None, kv_heads=p.get("kv_heads"))
+        elif st.kind == "rope":
+            p = st.p
+            attn_ops.rope(b[st.ins[0]], self.packed[i], b[st.out], p["tokens"], p["heads"], p["key_dim"],
+                          p["value_dim"], kv_heads=p.get("kv_heads"), stream=stream)
         elif st.kind == "embedding":
             attn_ops.embedding(b[st.ins[0]], self.packed[i], b[st.out], stream=stream)
         elif st.kind == "queries":
@@ -397,6 +412,15 @@ class SliceExecutor:
             cls, pos = self.packed[i]
             attn_ops.posembed(b[st.ins[0]], cls, pos, b[st.out], C=self.g.layers[st.p["layer"]].out_shape[-1],
                               stream=stream)
+
+    def _pack_rmsnorm(self, weights: Dict[str, np.ndarray], st: Step, cp: int):
+        """scale fp32 [cp] of an rmsnorm step, with Keras' default for scale=False; the bf16 layout's padding
+        channels get 0."""
+        name = st.p["layer"]
+        c = self.g.layers[name].out_shape[-1]
+        sc = np.zeros(cp, np.float32)
+        sc[:c] = weights.get(f"{name}/scale", np.ones(c, np.float32))
+        return torch.tensor(sc, device=self.device)
 
     def _pack_layernorm(self, weights: Dict[str, np.ndarray], st: Step, cp: int):
         """(gamma, beta) fp32 [cp] of a layernorm / groupnorm step, with Keras' defaults for scale=False / center=False;
@@ -884,8 +908,11 @@ class SliceExecutor:
                 gm, bt = self.packed[i]
                 E.groupnorm(b[st.ins[0]], gm, bt, b[st.out], self.g.layers[st.p["layer"]].out_shape[-1],
                             st.p["groups"], st.p["eps"], act=st.p["act"], workspace=self._gn_ws, stream=stream)
-            elif k in ("attention", "posembed", "winattn", "space_to_depth", "queries", "embedding"):
+            elif k in ("attention", "posembed", "winattn", "space_to_depth", "queries", "embedding", "rope"):
                 self._launch_tokens(i, st, b, stream)
+            elif k == "rmsnorm":
+                E.rmsnorm(b[st.ins[0]], self.packed[i], b[st.out], self.g.layers[st.p["layer"]].out_shape[-1],
+                          st.p["eps"], stream=stream)
             elif k == "act":
                 E.act(b[st.ins[0]], b[st.out], st.p["mode"], st.p["alpha"], stream=stream)
             elif k == "binary":
@@ -1018,8 +1045,10 @@ class SliceExecutor:
             gm, bt = self.packed[i]
             E.groupnorm_f32(b[st.ins[0]], gm, bt, b[st.out], st.p["groups"], st.p["eps"], act=st.p["act"],
                             workspace=self._gn_ws, stream=stream)
-        elif k in ("attention", "posembed", "winattn", "space_to_depth", "queries", "embedding"):
+        elif k in ("attention", "posembed", "winattn", "space_to_depth", "queries", "embedding", "rope"):
             self._launch_tokens(i, st, b, stream)
+        elif k == "rmsnorm":
+            E.rmsnorm_f32(b[st.ins[0]], self.packed[i], b[st.out], st.p["eps"], stream=stream)
         elif k == "deconv":
             conv_ops.deconv_forward_f32(b[st.ins[0]], self.packed[i], b[st.out], relu=st.p["relu"], stream=stream)
         elif k == "upsample":

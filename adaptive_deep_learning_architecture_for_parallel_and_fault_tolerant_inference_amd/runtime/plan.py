@@ -17,6 +17,10 @@ kernels:
 * ``dwconv``   DepthwiseConv2D, or Conv2D(groups=C) with one channel per group,
                [+BN folded] [+ReLU/ReLU6], explicit pads
 * ``layernorm`` LayerNormalization over the last axis; nothing fuses into it
+* ``rmsnorm``  RMSNormalization over the last axis (Keras 3); nothing fuses into it
+* ``rope``     the rotary position embedding of an attention layer `n` with `rope`: reads `n#qkv`, writes `n#rot`,
+               the same rows of [Q | K | V] with the Q and K heads rotated (the angles from a host-side table) and
+               V copied.  Out of place: no plan step aliases its input.  The ``attention`` step then reads `n#rot`
 * ``groupnorm`` GroupNormalization over (H, W, C / G) per image; an activation directly after it (an
                ``act`` or ``relu`` layer of ``ACT_MODE``, its sole consumer, not exposed by a cut or an
                output) folds into the step as `act`, the ``binary`` step's rule: GN + swish is one launch
@@ -108,6 +112,8 @@ def tensor_shape(g: Graph, name: str, compact: Optional[Dict[str, tuple]] = None
     if tag in ("qkv", "ctx") and L.op == "winattn":     # a window attention's stay (H, W, channels) maps
         hd = int(L.attrs["num_heads"]) * int(L.attrs["key_dim"])
         return tuple(L.out_shape[:-1]) + (3 * hd if tag == "qkv" else hd,)
+    if tag == "rot":                            # the rotated copy of `n#qkv`
+        return tensor_shape(g, base + "#qkv", compact)
     if tag == "ctx" or tag in MHA_PARTS:
         # "ctx" has the query's tokens; a projection (`n#q`, `n#kv`, ...) the tokens of the source its parts share
         h, d = int(L.attrs["num_heads"]), int(L.attrs["key_dim"])
@@ -117,7 +123,8 @@ def tensor_shape(g: Graph, name: str, compact: Optional[Dict[str, tuple]] = None
         tokens = 1
         for v in shape[:-1]:
             tokens *= v
-        width = {"query": h * d, "key": h * d, "value": h * dv}
+        hkv = int(L.attrs.get("kv_heads") or h)
+        width = {"query": h * d, "key": hkv * d, "value": hkv * dv}
         return (1, tokens, h * dv if tag == "ctx" else sum(width[p] for p in MHA_PARTS[tag]))
     return tuple(L.out_shape)
 
@@ -427,6 +434,10 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
             steps.append(Step("layernorm", n, [R(L.inputs[0])], [n],
                               {"layer": n, "eps": float(a.get("epsilon", 1e-3))}))
             done.add(n)
+        elif L.op == "rmsnorm":
+            steps.append(Step("rmsnorm", n, [R(L.inputs[0])], [n],
+                              {"layer": n, "eps": float(a.get("epsilon", 1e-6))}))
+            done.add(n)
         elif L.op == "groupnorm":
             cover = [n]
             out = n
@@ -447,6 +458,9 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
             for v in L.out_shape[:-1]:
                 tokens *= v
             head = {"heads": h, "key_dim": d, "value_dim": dv}
+            hkv = int(a.get("kv_heads") or h)
+            if hkv != h:                        # only then: every other layer's steps are what they were
+                head["kv_heads"] = hkv
 
             def proj(part: str, filters: int, res) -> Dict:
                 # a Dense step whose weights the packers assemble from the layer's projections (graph/ir.py
@@ -458,13 +472,20 @@ def compile_plan(g: Graph, outputs: Optional[List[str]] = None, fp32: bool = Fal
             sq, sk, sv = ((R(t) for t in mha_sources(L.inputs, bool(a.get("key_mask")))) if L.op == "mha"
                           else (R(L.inputs[0]),) * 3)
             if sq == sk == sv:
-                steps.append(Step("conv", n + "#qkv", [sq], [], proj("qkv", h * (2 * d + dv), None)))
+                steps.append(Step("conv", n + "#qkv", [sq], [], proj("qkv", h * d + hkv * (d + dv), None)))
             if L.op == "winattn":               # on the (H, W, C) map, windows and shift resolved by the kernel
                 steps.append(Step("winattn", n + "#ctx", [n + "#qkv"], [],
                                   {"layer": n, "height": L.out_shape[0], "width": L.out_shape[1],
                                    "window": int(a["window"]), "shift": int(a.get("shift", 0)), **head}))
             elif sq == sk == sv:
-                steps.append(Step("attention", n + "#ctx", [n + "#qkv"], [], {"layer": n, "tokens": tokens, **head}))
+                core_in = n + "#qkv"
+                if a.get("rope"):               # Q and K rotated out of place; the core reads the rotated rows
+                    core_in = n + "#rot"
+                    steps.append(Step("rope", core_in, [n + "#qkv"], [],
+                                      {"layer": n, "tokens": tokens, "rope": float(a["rope"]), **head}))
+                steps.append(Step("attention", n + "#ctx", [core_in], [], {"layer": n, "tokens": tokens, **head}))
+                if a.get("rope"):
+                    steps[-1].p["rope"] = float(a["rope"])
                 if a.get("causal"):
                     steps[-1].p["causal"] = True
                 if a.get("key_mask"):           # the (T,) mask tensor (the layer's last input) as a second input

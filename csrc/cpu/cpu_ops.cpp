@@ -435,9 +435,15 @@ void window_attention(const Arr<float>& qkv, const Arr<float>& table, Arr<float>
 // causal: query q attends keys k <= q (Keras' use_causal_mask).  key_mask (None, or B * T floats; never with
 // causal): token j of an image is padding iff -1 < key_mask[j] < 1 (a NaN is kept); a padded key is not attended
 // (its K and V rows are not read), a padded query's row and every row of an image with no kept key are zeros.
+// kv_heads (0: heads): grouped-query attention, head h reads K / V head h / (heads / kv_heads) of a row
+// [Q: heads x d | K: kv_heads x d | V: kv_heads x dv]; never with key_mask.
 void attention(const Arr<float>& qkv, Arr<float>& out, int B, int T, int heads, int d, int dv, bool causal,
-               const py::object& key_mask) {
+               const py::object& key_mask, int kv_heads) {
   const bool masked = !key_mask.is_none();
+  const int hkv = kv_heads > 0 ? kv_heads : heads;
+  need(kv_heads >= 0 && heads >= 1 && heads % hkv == 0, "attention kv_heads must divide heads");
+  need(hkv == heads || !masked, "attention kv_heads never with key_mask");
+  const int grp = heads / hkv;
   Arr<float> mask_arr;
   if (masked) {
     need(py::isinstance<Arr<float>>(key_mask), "attention key_mask must be a float32 array");
@@ -447,8 +453,8 @@ void attention(const Arr<float>& qkv, Arr<float>& out, int B, int T, int heads, 
   const float* mk = masked ? cptr(mask_arr) : nullptr;
   need(qkv.ndim() >= 2 && out.ndim() >= 2 && B >= 1 && T >= 1 && heads >= 1 && d >= 1 && dv >= 1, "attention args");
   const long ld_in = qkv.shape(qkv.ndim() - 1), ld_out = out.shape(out.ndim() - 1);
-  need(qkv.size() == (long)B * T * ld_in && out.size() == (long)B * T * ld_out && ld_in >= (long)heads * (2 * d + dv)
-           && ld_out >= (long)heads * dv, "attention shapes");
+  need(qkv.size() == (long)B * T * ld_in && out.size() == (long)B * T * ld_out &&
+           ld_in >= (long)heads * d + (long)hkv * (d + dv) && ld_out >= (long)heads * dv, "attention shapes");
   const float* xp = cptr(qkv);
   float* yp = mptr(out);
   py::gil_scoped_release nogil;
@@ -459,8 +465,8 @@ void attention(const Arr<float>& qkv, Arr<float>& out, int B, int T, int heads, 
     for (int b = 0; b < B; ++b)
       for (int h = 0; h < heads; ++h) {
         const float* base = xp + (size_t)b * T * ld_in;
-        const float* kb = base + heads * d + h * d;
-        const float* vb = base + 2 * heads * d + h * dv;
+        const float* kb = base + heads * d + (h / grp) * d;
+        const float* vb = base + heads * d + hkv * d + (h / grp) * dv;
         for (int q = 0; q < T; ++q) {
           const float* qr = base + (size_t)q * ld_in + h * d;
           const int nk = causal ? q + 1 : T;           // the keys this query attends
@@ -738,6 +744,57 @@ void layernorm(const Arr<float>& x, const Arr<float>& gamma, const Arr<float>& b
   }
 }
 
+// Keras 3 RMSNormalization over the last axis: y = x * rsqrt(mean(x^2) + eps) * scale[c], the sum of squares in
+// double
+void rmsnorm(const Arr<float>& x, const Arr<float>& scale, Arr<float>& y, float eps) {
+  const int C = x.shape(x.ndim() - 1);
+  const long rows = x.size() / C;
+  need(scale.size() == C && y.size() == x.size(), "rmsnorm shapes");
+  const float *xp = cptr(x), *gp = cptr(scale);
+  float* yp = mptr(y);
+  py::gil_scoped_release nogil;
+#pragma omp parallel for schedule(static)
+  for (long r = 0; r < rows; ++r) {
+    const float* xr = xp + r * C;
+    float* yr = yp + r * C;
+    double q = 0.0;
+    for (int c = 0; c < C; ++c) q += (double)xr[c] * xr[c];
+    const double rstd = 1.0 / std::sqrt(q / C + (double)eps);
+    for (int c = 0; c < C; ++c) yr[c] = (float)(xr[c] * rstd) * gp[c];
+  }
+}
+
+// Rotary position embedding, rotate-half convention (the GPU op's arguments, csrc/kernels/layers.hip): x / y
+// [rows][ld] rows of [Q: hq x d | K: hkv x d | V: hkv x dv | rest], the position of a row is row % T, table
+// [2][T][d / 2] holds cos then sin.  Q and K heads are rotated in fp32, V is copied, the rest of a row becomes zero.
+void rope(const Arr<float>& x, const Arr<float>& table, Arr<float>& y, int T, int hq, int hkv, int d, int dv) {
+  need(x.ndim() >= 2 && T >= 1 && hq >= 1 && hkv >= 1 && d >= 2 && d % 2 == 0 && dv >= 1, "rope args (d is even)");
+  const long ld = x.shape(x.ndim() - 1), rows = x.size() / ld;
+  const long rotw = (long)(hq + hkv) * d, W = rotw + (long)hkv * dv;
+  const int half = d / 2;
+  need(y.size() == x.size() && y.shape(y.ndim() - 1) == ld && W <= ld && rows % T == 0 &&
+           table.size() == 2l * T * half, "rope shapes");
+  const float *xp = cptr(x), *tp = cptr(table);
+  float* yp = mptr(y);
+  need(xp != yp, "rope is out of place");
+  py::gil_scoped_release nogil;
+#pragma omp parallel for schedule(static)
+  for (long r = 0; r < rows; ++r) {
+    const float* xr = xp + r * ld;
+    float* yr = yp + r * ld;
+    const float* cs = tp + (r % T) * half;
+    const float* sn = cs + (long)T * half;
+    for (int h = 0; h < hq + hkv; ++h)
+      for (int i = 0; i < half; ++i) {
+        const float a = xr[h * d + i], b = xr[h * d + i + half];
+        yr[h * d + i] = a * cs[i] - b * sn[i];
+        yr[h * d + i + half] = b * cs[i] + a * sn[i];
+      }
+    for (long c = rotw; c < W; ++c) yr[c] = xr[c];
+    for (long c = W; c < ld; ++c) yr[c] = 0.f;
+  }
+}
+
 // Keras GroupNormalization on an NHWC map: per (image, group) the mean and the biased variance over (H, W, C / G)
 // from the centred values (two passes in double, never E[x^2] - mu^2), then
 // y = act((x - mu) * rsqrt(var + eps) * gamma[c] + beta[c])
@@ -898,7 +955,8 @@ PYBIND11_MODULE(_cpu, m) {
   m.def("affine", &affine, py::arg("x"), py::arg("scale"), py::arg("shift"), py::arg("y"), py::arg("act") = 0,
         py::arg("alpha") = 0.3f);
   m.def("attention", &attention, py::arg("qkv"), py::arg("out"), py::arg("B"), py::arg("T"), py::arg("heads"),
-        py::arg("key_dim"), py::arg("value_dim"), py::arg("causal") = false, py::arg("key_mask") = py::none());
+        py::arg("key_dim"), py::arg("value_dim"), py::arg("causal") = false, py::arg("key_mask") = py::none(),
+        py::arg("kv_heads") = 0);
   m.def("embedding", &embedding, py::arg("ids"), py::arg("table"), py::arg("out"));
   m.def("window_attention", &window_attention, py::arg("qkv"), py::arg("table"), py::arg("out"), py::arg("B"),
         py::arg("H"), py::arg("W"), py::arg("window"), py::arg("shift"), py::arg("heads"), py::arg("key_dim"));
@@ -907,6 +965,9 @@ PYBIND11_MODULE(_cpu, m) {
         py::arg("Tq"), py::arg("Tk"), py::arg("heads"), py::arg("d"), py::arg("dv"));
   m.def("queries", &queries, py::arg("emb"), py::arg("out"), py::arg("B"));
   m.def("layernorm", &layernorm, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("y"), py::arg("eps"));
+  m.def("rmsnorm", &rmsnorm, py::arg("x"), py::arg("scale"), py::arg("y"), py::arg("eps"));
+  m.def("rope", &rope, py::arg("x"), py::arg("table"), py::arg("y"), py::arg("T"), py::arg("hq"), py::arg("hkv"),
+        py::arg("key_dim"), py::arg("value_dim"));
   m.def("groupnorm", &groupnorm, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("y"), py::arg("groups"),
         py::arg("eps"), py::arg("act") = 0, py::arg("alpha") = 0.3f);
   m.def("activation", &activation, py::arg("x"), py::arg("y"), py::arg("act"), py::arg("alpha") = 0.3f);

@@ -7,6 +7,13 @@
 // staging table carries the K or V column of each vector, so a staged load needs no select.  The causal entry
 // points run the core's CAUSAL instantiations on the same layout, the masked entry points its MASKED ones with a
 // [B][T] fp32 padding mask (token j of an image is padding iff -1 < mask[j] < 1).
+//
+// Grouped-query attention (the gqa entry points): `heads` query heads share hkv < heads key / value heads, g =
+// heads / hkv of them each, and a row is [Q: heads x d | K: hkv x d | V: hkv x dv].  That is a source policy derived
+// from SelfSrc, GqaSrc, on the same templates: head h's K at column heads d + (h / g) d, its V at
+// heads d + hkv d + (h / g) dv, everything else as SelfSrc.  Per (image, head) the arithmetic is that of a plain
+// launch on rows in which each K / V head stands g times, so the two agree bit for bit.  SelfSrc and the templates
+// are untouched.
 #include "attention_core.h"
 
 namespace adapt {
@@ -42,6 +49,38 @@ struct MaskedSelfSrc : SelfSrc<T> {
   const float* mask;
   __device__ const float* key_mask(const typename SelfSrc<T>::Block& b) const { return mask + b.img * this->Tn; }
 };
+
+// Grouped-query rows: hkv key / value heads, each read by g = heads / hkv consecutive query heads.  SelfSrc with
+// the K and V columns of a block taken from its key / value head
+template <typename T>
+struct GqaSrc : SelfSrc<T> {
+  int hkv, g;
+  __device__ typename SelfSrc<T>::Block block(int img, int h) const {
+    const int kv = h / g;
+    return typename SelfSrc<T>::Block{this->qkv + img * this->Tn * this->ld_in, img, h * this->d,
+                                      this->heads * this->d + kv * this->d,
+                                      this->heads * this->d + hkv * this->d + kv * this->dv_};
+  }
+};
+
+template <typename T, bool CAUSAL>
+hipError_t attention_gqa_launch(const T* qkv, T* out, int B, int Tn, int heads, int hkv, int d, int dv, int ld_in,
+                                int ld_out, hipStream_t s) {
+  if (B < 1 || Tn < 1 || heads < 1 || hkv < 1 || heads % hkv || d < 1 || dv < 1 || !qkv || !out)
+    return hipErrorInvalidValue;
+  const long long lim = 0x7fffffffll;
+  // the GQA row width: heads Q heads, hkv K and hkv V heads
+  if ((long long)heads * d + (long long)hkv * ((long long)d + dv) > ld_in || (long long)heads * dv > ld_out)
+    return hipErrorInvalidValue;
+  if ((long long)B * Tn * ld_in > lim || (long long)B * Tn * ld_out > lim || (long long)B * heads * Tn > lim)
+    return hipErrorInvalidValue;
+  const bool mfma = attention_path(d, dv) &&
+                    attn::attention_vec4((uintptr_t)qkv | (uintptr_t)out, ld_in | ld_out, (int)sizeof(T));
+  GqaSrc<T> src;
+  src.qkv = qkv; src.Tn = Tn; src.heads = heads; src.d = d; src.dv_ = dv; src.ld_in = ld_in;
+  src.hkv = hkv; src.g = heads / hkv;
+  return attn::attention_core_launch<T, GqaSrc<T>, CAUSAL>(src, out, ld_out, B, mfma, s);
+}
 
 template <typename T, bool CAUSAL>
 hipError_t attention_launch(const T* qkv, T* out, int B, int Tn, int heads, int d, int dv, int ld_in, int ld_out,
@@ -109,6 +148,28 @@ hipError_t attention_masked_bf16(const bf16* qkv, const float* mask, bf16* out, 
                                  int ld_in, int ld_out, hipStream_t s) {
   if (!mask) return hipErrorInvalidValue;
   return attention_launch<bf16, false>(qkv, out, B, T, heads, d, dv, ld_in, ld_out, s, mask);
+}
+
+// Grouped-query attention: `heads` query heads over kv_heads key / value heads (heads % kv_heads == 0), rows of
+// [Q: heads x d | K: kv_heads x d | V: kv_heads x dv]; plain and causal, same paths
+hipError_t attention_gqa_f32(const float* qkv, float* out, int B, int T, int heads, int kv_heads, int d, int dv,
+                             int ld_in, int ld_out, hipStream_t s) {
+  return attention_gqa_launch<float, false>(qkv, out, B, T, heads, kv_heads, d, dv, ld_in, ld_out, s);
+}
+
+hipError_t attention_gqa_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, int kv_heads, int d, int dv,
+                              int ld_in, int ld_out, hipStream_t s) {
+  return attention_gqa_launch<bf16, false>(qkv, out, B, T, heads, kv_heads, d, dv, ld_in, ld_out, s);
+}
+
+hipError_t attention_gqa_causal_f32(const float* qkv, float* out, int B, int T, int heads, int kv_heads, int d, int dv,
+                                    int ld_in, int ld_out, hipStream_t s) {
+  return attention_gqa_launch<float, true>(qkv, out, B, T, heads, kv_heads, d, dv, ld_in, ld_out, s);
+}
+
+hipError_t attention_gqa_causal_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, int kv_heads, int d, int dv,
+                                     int ld_in, int ld_out, hipStream_t s) {
+  return attention_gqa_launch<bf16, true>(qkv, out, B, T, heads, kv_heads, d, dv, ld_in, ld_out, s);
 }
 
 }  // namespace adapt

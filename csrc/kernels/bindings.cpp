@@ -401,6 +401,13 @@ PYBIND11_MODULE(_C, m) {
                            eps, S(s)), "layernorm");
   });
   m.def("layernorm_lanes", &adapt::layernorm_lanes);
+  m.def("rmsnorm_f32", [](u64 x, u64 scale, u64 y, int rows, int C, float eps, u64 s) {
+    check(adapt::rmsnorm_f32(P<const float>(x), P<const float>(scale), P<float>(y), rows, C, eps, S(s)), "rmsnorm_f32");
+  });
+  m.def("rmsnorm_bf16", [](u64 x, u64 scale, u64 y, int rows, int Cp, int C, float eps, u64 s) {
+    check(adapt::rmsnorm_bf16(P<const bf16>(x), P<const float>(scale), P<bf16>(y), rows, Cp, C, eps, S(s)),
+          "rmsnorm_bf16");
+  });
   m.def("groupnorm_f32", [](u64 x, u64 gamma, u64 beta, u64 y, u64 ws, u64 ws_floats, int B, int Px, int C, int G,
                             float eps, int act, float alpha, u64 s) {
     check(adapt::groupnorm_f32(P<const float>(x), P<const float>(gamma), P<const float>(beta), P<float>(y),
@@ -464,6 +471,26 @@ PYBIND11_MODULE(_C, m) {
                                        ld_in, ld_out, S(s)),
           "attention_masked_bf16");
   });
+  m.def("attention_gqa_f32", [](u64 qkv, u64 out, int B, int T, int heads, int kv_heads, int d, int dv, int ld_in,
+                              int ld_out, u64 s) {
+    check(adapt::attention_gqa_f32(P<const float>(qkv), P<float>(out), B, T, heads, kv_heads, d, dv, ld_in, ld_out, S(s)),
+          "attention_gqa_f32");
+  });
+  m.def("attention_gqa_bf16", [](u64 qkv, u64 out, int B, int T, int heads, int kv_heads, int d, int dv, int ld_in,
+                               int ld_out, u64 s) {
+    check(adapt::attention_gqa_bf16(P<const bf16>(qkv), P<bf16>(out), B, T, heads, kv_heads, d, dv, ld_in, ld_out, S(s)),
+          "attention_gqa_bf16");
+  });
+  m.def("attention_gqa_causal_f32", [](u64 qkv, u64 out, int B, int T, int heads, int kv_heads, int d, int dv, int ld_in,
+                                     int ld_out, u64 s) {
+    check(adapt::attention_gqa_causal_f32(P<const float>(qkv), P<float>(out), B, T, heads, kv_heads, d, dv, ld_in, ld_out, S(s)),
+          "attention_gqa_causal_f32");
+  });
+  m.def("attention_gqa_causal_bf16", [](u64 qkv, u64 out, int B, int T, int heads, int kv_heads, int d, int dv, int ld_in,
+                                      int ld_out, u64 s) {
+    check(adapt::attention_gqa_causal_bf16(P<const bf16>(qkv), P<bf16>(out), B, T, heads, kv_heads, d, dv, ld_in, ld_out, S(s)),
+          "attention_gqa_causal_bf16");
+  });
   m.def("attention_path", &adapt::attention_path);
   m.def("attention_query_tile", &adapt::attention_query_tile);
   m.def("attention_key_tile", &adapt::attention_key_tile);
@@ -493,6 +520,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("embedding_bf16", [](u64 ids, u64 table, u64 y, int rows, int V, int ld, u64 s) {
     check(adapt::embedding_bf16(P<const float>(ids), P<const bf16>(table), P<bf16>(y), rows, V, ld, S(s)),
           "embedding_bf16");
+  });
+  m.def("rope_f32", [](u64 x, u64 table, u64 y, int rows, int T, int hq, int hkv, int d, int dv, int ld, u64 s) {
+    check(adapt::rope_f32(P<const float>(x), P<const float>(table), P<float>(y), rows, T, hq, hkv, d, dv, ld, S(s)),
+          "rope_f32");
+  });
+  m.def("rope_bf16", [](u64 x, u64 table, u64 y, int rows, int T, int hq, int hkv, int d, int dv, int ld, u64 s) {
+    check(adapt::rope_bf16(P<const bf16>(x), P<const float>(table), P<bf16>(y), rows, T, hq, hkv, d, dv, ld, S(s)),
+          "rope_bf16");
   });
   m.def("window_attention_f32", [](u64 qkv, u64 bias, u64 out, int B, int H, int W, int M, int shift, int heads, int d,
                                    int ld_in, int ld_out, u64 s) {

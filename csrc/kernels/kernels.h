@@ -254,6 +254,10 @@ hipError_t layernorm_f32(const float* x, const float* gamma, const float* beta, 
 hipError_t layernorm(const bf16* x, const float* gamma, const float* beta, bf16* y, int rows, int Cp, int C, float eps,
                      hipStream_t s);
 int layernorm_lanes(int nvec);   // lanes per row for `nvec` 16-byte vectors per row; 0 = the looped path
+// RMSNormalization over the last axis (layernorm.hip): y = x * rsqrt(mean(x^2) + eps) * scale, the layouts and
+// paths of layernorm (scale holds Cp floats in bf16), one pass of statistics
+hipError_t rmsnorm_f32(const float* x, const float* scale, float* y, int rows, int C, float eps, hipStream_t s);
+hipError_t rmsnorm_bf16(const bf16* x, const float* scale, bf16* y, int rows, int Cp, int C, float eps, hipStream_t s);
 // GroupNormalization on an NHWC map (groupnorm.hip): x / y [B][P][C] fp32, or [B][P][Cp] bf16 with channels C..Cp-1
 // layout padding (kept out of the statistics, written as zeros; gamma / beta then hold Cp floats).  G groups of
 // C / G channels, then the activation `act` (common.h ActMode).  `ws`: groupnorm_workspace_floats() floats, owned
@@ -425,6 +429,16 @@ hipError_t attention_masked_f32(const float* qkv, const float* mask, float* out,
                                 int ld_in, int ld_out, hipStream_t s);
 hipError_t attention_masked_bf16(const bf16* qkv, const float* mask, bf16* out, int B, int T, int heads, int d, int dv,
                                  int ld_in, int ld_out, hipStream_t s);
+// grouped-query attention: `heads` query heads over kv_heads key / value heads (heads % kv_heads == 0), head h
+// reads K / V head h / (heads / kv_heads); rows of [Q: heads x d | K: kv_heads x d | V: kv_heads x dv]
+hipError_t attention_gqa_f32(const float* qkv, float* out, int B, int T, int heads, int kv_heads, int d, int dv,
+                             int ld_in, int ld_out, hipStream_t s);
+hipError_t attention_gqa_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, int kv_heads, int d, int dv,
+                              int ld_in, int ld_out, hipStream_t s);
+hipError_t attention_gqa_causal_f32(const float* qkv, float* out, int B, int T, int heads, int kv_heads, int d, int dv,
+                                    int ld_in, int ld_out, hipStream_t s);
+hipError_t attention_gqa_causal_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, int kv_heads, int d, int dv,
+                                     int ld_in, int ld_out, hipStream_t s);
 int attention_path(int d, int dv);     // 1: MFMA path, 0: plain kernel
 int attention_query_tile();            // queries per block of the MFMA path
 int attention_key_tile();              // keys per LDS tile of the MFMA path
@@ -473,6 +487,14 @@ hipError_t queries_bf16(const float* emb, bf16* y, int B, int N, int Cp, int C, 
 // type, rows of ld elements (bf16: padded to 8 channels, the table's padding prepared as zeros); V <= 2^24
 hipError_t embedding_f32(const float* ids, const float* table, float* y, int rows, int V, int ld, hipStream_t s);
 hipError_t embedding_bf16(const float* ids, const bf16* table, bf16* y, int rows, int V, int ld, hipStream_t s);
+// Rotary position embedding (layers.hip), rotate-half convention, out of place: x / y [rows][ld] rows of
+// [Q: hq x d | K: hkv x d | V: hkv x dv | padding], rows a multiple of T and the position of a row is row % T; table
+// fp32 [2][T][d / 2] (cos, then sin).  Q and K heads are rotated, V is copied, the columns past the true width are
+// written as zeros.  d even; x != y
+hipError_t rope_f32(const float* x, const float* table, float* y, int rows, int T, int hq, int hkv, int d, int dv,
+                    int ld, hipStream_t s);
+hipError_t rope_bf16(const bf16* x, const float* table, bf16* y, int rows, int T, int hq, int hkv, int d, int dv,
+                     int ld, hipStream_t s);
 bool gconv_f32_mfma_ok(int Cin, int Cout, int G);     // shape rule of the MFMA path
 // mfma: which path to launch (the caller packed w for it); an ineligible shape is an error, never a fall-through
 hipError_t gconv_f32_forward(const GconvF32Params& p, bool mfma, hipStream_t s);

@@ -233,4 +233,143 @@ hipError_t layernorm(const bf16* x, const float* gamma, const float* beta, bf16*
   return hipGetLastError();
 }
 
+// RMSNormalization over the last axis (Keras 3 semantics; the norm of every Llama-family model):
+//
+//   y = x * rsqrt(mean_c(x^2) + eps) * scale[c]
+//
+// The scheme above with kernels of their own, so the layernorm kernels stay the instructions they are: the same
+// rows-per-wave split, a row read once with 16-byte loads, kept in registers and written once, `__shfl_xor` sums
+// only.  There is no mean to subtract, so one pass of statistics (the sum of squares, in fp32) is all there is:
+// the cancellation that forces layernorm's second pass cannot arise in a sum of non-negative terms.  The looped
+// path (fp32 C % 4 != 0, a misaligned base, more than 512 vectors per row) sweeps the row twice.  bf16 padding
+// channels stay out of the sum (the divisor is C) and are written as zeros.
+namespace {
+
+template <int LPR, int VPL>
+__global__ __launch_bounds__(64 * LN_WAVES) void rmsnorm_f32_kernel(const float* __restrict__ x,
+                                                                     const float* __restrict__ scale,
+                                                                     float* __restrict__ y, int rows, int C,
+                                                                     float eps) {
+  constexpr int RPW = 64 / LPR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane & (LPR - 1);
+  const long row = ((long)blockIdx.x * LN_WAVES + wave) * RPW + lane / LPR;
+  const int nvec = C >> 2;
+  const bool live = row < rows;
+  const f32x4* xr = (const f32x4*)(x + (size_t)(live ? row : 0) * C);
+  f32x4 v[VPL];
+  bool has[VPL];
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int j = sub + i * LPR;
+    has[i] = live && j < nvec;
+    v[i] = f32x4{0.f, 0.f, 0.f, 0.f};                 // lanes without a vector add zeros
+    if (has[i]) v[i] = xr[j];
+  }
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) q += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
+  const float rstd = 1.f / sqrtf(group_sum<LPR>(q) / (float)C + eps);
+  f32x4* yr = (f32x4*)(y + (size_t)(live ? row : 0) * C);
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int j = sub + i * LPR;
+    if (has[i]) yr[j] = v[i] * rstd * ((const f32x4*)scale)[j];
+  }
+}
+
+template <int LPR, int VPL>
+__global__ __launch_bounds__(64 * LN_WAVES) void rmsnorm_bf16_kernel(const bf16* __restrict__ x,
+                                                                      const float* __restrict__ scale,
+                                                                      bf16* __restrict__ y, int rows, int Cp, int C,
+                                                                      float eps) {
+  constexpr int RPW = 64 / LPR;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane & (LPR - 1);
+  const long row = ((long)blockIdx.x * LN_WAVES + wave) * RPW + lane / LPR;
+  const int nvec = Cp >> 3;
+  const bool live = row < rows;
+  const u32x4* xr = (const u32x4*)(x + (size_t)(live ? row : 0) * Cp);
+  float f[VPL][8];
+  bool has[VPL];
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int j = sub + i * LPR;
+    has[i] = live && j < nvec;
+    V8 t;
+    t.u = u32x4{0u, 0u, 0u, 0u};
+    if (has[i]) t.u = xr[j];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[i][e] = (has[i] && j * 8 + e < C) ? bf2f(t.e[e]) : 0.f;    // pads never enter
+  }
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPL; ++i)
+    q += ((f[i][0] * f[i][0] + f[i][1] * f[i][1]) + (f[i][2] * f[i][2] + f[i][3] * f[i][3])) +
+         ((f[i][4] * f[i][4] + f[i][5] * f[i][5]) + (f[i][6] * f[i][6] + f[i][7] * f[i][7]));
+  const float rstd = 1.f / sqrtf(group_sum<LPR>(q) / (float)C + eps);
+  u32x4* yr = (u32x4*)(y + (size_t)(live ? row : 0) * Cp);
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int j = sub + i * LPR;
+    if (!has[i]) continue;
+    const f32x4 g0 = ((const f32x4*)scale)[2 * j], g1 = ((const f32x4*)scale)[2 * j + 1];
+    const float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+    V8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o.e[e] = f2bf(j * 8 + e < C ? f[i][e] * rstd * g[e] : 0.f);
+    yr[j] = o.u;
+  }
+}
+
+// Any C, any alignment: one wave per row, scalar accesses, the row swept twice.  scale holds C values at least;
+// channels C..Cp-1 of the output are written as zeros and never read.
+template <typename T>
+__global__ __launch_bounds__(64 * LN_WAVES) void rmsnorm_loop_kernel(const T* __restrict__ x,
+                                                                      const float* __restrict__ scale,
+                                                                      T* __restrict__ y, int rows, int Cp, int C,
+                                                                      float eps) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * LN_WAVES + (threadIdx.x >> 6);
+  if (row >= rows) return;                        // the whole wave leaves together
+  const T* xr = x + (size_t)row * Cp;
+  T* yr = y + (size_t)row * Cp;
+  float q = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float v = ln_ld(xr + c);
+    q += v * v;
+  }
+  const float rstd = 1.f / sqrtf(group_sum<64>(q) / (float)C + eps);
+  for (int c = lane; c < C; c += 64) ln_st(yr + c, ln_ld(xr + c) * rstd * scale[c]);
+  for (int c = C + lane; c < Cp; c += 64) ln_st(yr + c, 0.f);
+}
+
+}  // namespace
+
+hipError_t rmsnorm_f32(const float* x, const float* scale, float* y, int rows, int C, float eps, hipStream_t s) {
+  if (rows < 1 || C < 1) return hipErrorInvalidValue;
+  if (C % 4 == 0 && C / 4 <= LN_MAX_NVEC && aligned16(x, scale, scale, y)) {
+    const int nvec = C / 4;
+    LN_DISPATCH(rmsnorm_f32_kernel, nvec, x, scale, y, rows, C, eps);
+  } else {
+    hipLaunchKernelGGL(rmsnorm_loop_kernel<float>, dim3(blocks_for(rows, LN_WAVES)), dim3(64 * LN_WAVES), 0, s, x,
+                       scale, y, rows, C, C, eps);
+  }
+  return hipGetLastError();
+}
+
+// scale: Cp floats (the register path loads whole vectors of it; its padding values are not used)
+hipError_t rmsnorm_bf16(const bf16* x, const float* scale, bf16* y, int rows, int Cp, int C, float eps,
+                        hipStream_t s) {
+  if (rows < 1 || C < 1 || Cp < C || Cp % 8) return hipErrorInvalidValue;
+  if (Cp / 8 <= LN_MAX_NVEC && aligned16(x, scale, scale, y)) {
+    const int nvec = Cp / 8;
+    LN_DISPATCH(rmsnorm_bf16_kernel, nvec, x, scale, y, rows, Cp, C, eps);
+  } else {
+    hipLaunchKernelGGL(rmsnorm_loop_kernel<bf16>, dim3(blocks_for(rows, LN_WAVES)), dim3(64 * LN_WAVES), 0, s, x,
+                       scale, y, rows, Cp, C, eps);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace adapt

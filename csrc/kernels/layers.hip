@@ -610,4 +610,149 @@ hipError_t embedding_bf16(const float* ids, const bf16* table, bf16* y, int rows
   return embedding_launch<bf16>(ids, table, y, rows, V, ld, s);
 }
 
+// Rotary position embedding (the rotate-half convention of Hugging Face Llama and keras_hub RotaryEmbedding) on
+// the attention layer's projection buffer, out of place: x and y are [rows][ld] rows of [Q | K | V | padding], Q
+// hq heads of d, K hkv heads of d, V hkv heads of dv.  For a Q or K head vector at position t = row % T (a batch
+// restarts at 0 per image) and i in [0, d/2):
+//
+//   y[i] = x[i] cos(t, i) - x[i + d/2] sin(t, i),   y[i + d/2] = x[i + d/2] cos(t, i) + x[i] sin(t, i)
+//
+// cos and sin come from the fp32 table [2][T][d/2] that the host computed in float64 (ops/attention.py
+// rope_table): the kernel evaluates no sinf / cosf, whose fp32 argument t * freq is already off by 5e-4 rad at
+// t = 8192.  A thread owns one 16-byte vector of a head's first half, its partner vector at + d/2 and the matching
+// cos and sin vectors, and writes both halves; the threads behind the rotated columns copy the V columns and
+// write the columns from the true width to ld as zeros, so one launch writes every element of y.  Math is fp32,
+// one rounding on a bf16 store.  VEC = 16 bytes per thread where d/2 and ld are multiples of it and the bases are
+// aligned, else 1: every other even d.  Offsets are 32-bit: the launcher refuses what does not fit.
+namespace {
+template <typename T, int VEC>
+struct RopeVec {
+  float f[VEC];
+};
+
+template <typename T, int VEC>
+__device__ __forceinline__ RopeVec<T, VEC> rope_ld(const T* p) {
+  RopeVec<T, VEC> r;
+  if constexpr (VEC == 1) {
+    r.f[0] = (float)p[0];
+  } else if constexpr (sizeof(T) == 4) {
+    const f32x4 q = *(const f32x4*)p;
+    r.f[0] = q.x; r.f[1] = q.y; r.f[2] = q.z; r.f[3] = q.w;
+  } else {
+    V8 q;
+    q.u = *(const u32x4*)p;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) r.f[e] = bf2f(q.e[e]);
+  }
+  return r;
+}
+
+template <typename T, int VEC>
+__device__ __forceinline__ void rope_st(T* p, const RopeVec<T, VEC>& r) {
+  if constexpr (VEC == 1) {
+    p[0] = (T)r.f[0];
+  } else if constexpr (sizeof(T) == 4) {
+    *(f32x4*)p = f32x4{r.f[0], r.f[1], r.f[2], r.f[3]};
+  } else {
+    V8 q;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q.e[e] = f2bf(r.f[e]);
+    *(u32x4*)p = q.u;
+  }
+}
+
+// nrot: rotating threads per row ((hq + hkv) * half / VEC), ncopy: copying threads per row ((ld - rotw) / VEC);
+// rotw = (hq + hkv) d, the first V column; W the true row width
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void rope_kernel(const T* __restrict__ x, const float* __restrict__ table,
+                                                    T* __restrict__ y, int Tn, int half, int ld, int rotw, int W,
+                                                    int nrot, int ncopy, int total) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int per = nrot + ncopy;
+  const int row = idx / per, u = idx % per;
+  const T* xr = x + row * ld;
+  T* yr = y + row * ld;
+  if (u < nrot) {
+    const int hv = half / VEC;                        // vectors per half head
+    const int head = u / hv, i = (u % hv) * VEC;
+    const int col = head * 2 * half + i;
+    const float* cs = table + (row % Tn) * half + i;  // cos; sin lies Tn * half further on
+    const float* sn = cs + Tn * half;
+    const RopeVec<T, VEC> a = rope_ld<T, VEC>(xr + col), b = rope_ld<T, VEC>(xr + col + half);
+    RopeVec<T, VEC> oa, ob;
+    if constexpr (VEC == 1) {
+      const float c = cs[0], s = sn[0];
+      oa.f[0] = a.f[0] * c - b.f[0] * s;
+      ob.f[0] = b.f[0] * c + a.f[0] * s;
+    } else {
+#pragma unroll
+      for (int v4 = 0; v4 < VEC / 4; ++v4) {
+        const f32x4 c = ((const f32x4*)cs)[v4], s = ((const f32x4*)sn)[v4];
+        const float cc[4] = {c.x, c.y, c.z, c.w}, ss[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          oa.f[4 * v4 + e] = a.f[4 * v4 + e] * cc[e] - b.f[4 * v4 + e] * ss[e];
+          ob.f[4 * v4 + e] = b.f[4 * v4 + e] * cc[e] + a.f[4 * v4 + e] * ss[e];
+        }
+      }
+    }
+    rope_st<T, VEC>(yr + col, oa);
+    rope_st<T, VEC>(yr + col + half, ob);
+  } else {
+    // V is copied as it stands (no arithmetic: bit-exact); the columns from W on are zeros, whatever x holds there
+    const int col = rotw + (u - nrot) * VEC;
+    if constexpr (VEC == 1) {
+      yr[col] = col < W ? xr[col] : (T)0.f;
+    } else {
+      union { u32x4 u; T e[VEC]; } q;
+      q.u = u32x4{0u, 0u, 0u, 0u};
+      if (col < W) q.u = *(const u32x4*)(xr + col);
+      if (col + VEC > W) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e)
+          if (col + e >= W) q.e[e] = (T)0.f;
+      }
+      *(u32x4*)(yr + col) = q.u;
+    }
+  }
+}
+
+template <typename T>
+hipError_t rope_launch(const T* x, const float* table, T* y, int rows, int Tn, int hq, int hkv, int d, int dv, int ld,
+                       hipStream_t s) {
+  constexpr int VEC = 16 / sizeof(T);
+  if (rows < 1 || Tn < 1 || rows % Tn || hq < 1 || hkv < 1 || d < 2 || d % 2 || dv < 1 || !x || !table || !y || x == y)
+    return hipErrorInvalidValue;
+  const long long lim = 0x7fffffffll;
+  const long long rotw = ((long long)hq + hkv) * d, W = rotw + (long long)hkv * dv;
+  if (W > ld || (long long)rows * ld > lim || (long long)Tn * d > lim) return hipErrorInvalidValue;
+  const int half = d / 2;
+  const bool vec = half % VEC == 0 && ld % VEC == 0 &&
+                   ((((uintptr_t)x | (uintptr_t)y) & 15) == 0) && (((uintptr_t)table & 15) == 0);
+  const int v = vec ? VEC : 1;
+  const int nrot = (int)(rotw / 2 / v), ncopy = (int)((ld - rotw) / v);
+  if ((long long)rows * (nrot + ncopy) > lim) return hipErrorInvalidValue;
+  const int total = rows * (nrot + ncopy);
+  const dim3 grid((total + 255) / 256), block(256);
+  if (vec)
+    hipLaunchKernelGGL((rope_kernel<T, VEC>), grid, block, 0, s, x, table, y, Tn, half, ld, (int)rotw, (int)W, nrot,
+                       ncopy, total);
+  else
+    hipLaunchKernelGGL((rope_kernel<T, 1>), grid, block, 0, s, x, table, y, Tn, half, ld, (int)rotw, (int)W, nrot,
+                       ncopy, total);
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t rope_f32(const float* x, const float* table, float* y, int rows, int T, int hq, int hkv, int d, int dv,
+                    int ld, hipStream_t s) {
+  return rope_launch<float>(x, table, y, rows, T, hq, hkv, d, dv, ld, s);
+}
+
+hipError_t rope_bf16(const bf16* x, const float* table, bf16* y, int rows, int T, int hq, int hkv, int d, int dv,
+                     int ld, hipStream_t s) {
+  return rope_launch<bf16>(x, table, y, rows, T, hq, hkv, d, dv, ld, s);
+}
+
 }  // namespace adapt

@@ -14,8 +14,11 @@ communicator, with the data moved through device memory exported by IPC handle:
 * a message is one grouped `p2p` call: a send enqueues, on the link stream, a wait for its slot to be free,
   device copies of every tensor into the slot and a counter store; a receive enqueues a wait for that
   counter, the copies out and a "consumed" counter store (`csrc/kernels/loopback.hip`); the counters, a
-  shared abort word and per-rank status words live in a page-locked /dev/shm control block both
-  processes map;
+  shared abort word and per-rank status words live in a /dev/shm control block both processes map.
+  The kernels do not touch those pages: each process gives them a page-locked mirror of the block
+  (allocated page-locked, since pages a process already has cannot be page-locked everywhere), and a
+  native relay thread copies each word from its one writer's side to the other
+  (`csrc/kernels/loopback.h`);
 * `abort()` raises the shared abort word, which ends every spinning wait of both ranks (ncclCommAbort's
   role); a wait that ends by abort or by its time bound marks the communicator failed, so `Work` raises.
 
@@ -24,11 +27,13 @@ environment (parallel/rccl.py `RcclComm`); it is never a default and never a fal
 """
 from __future__ import annotations
 
+import atexit
 import mmap
 import os
 import threading
 import time
 import uuid
+import weakref
 
 import numpy as np
 import torch
@@ -49,6 +54,18 @@ def selected() -> bool:
 def _kernels():
     from ..ops._lib import kernels
     return kernels()
+
+
+_live: "weakref.WeakSet[LoopbackComm]" = weakref.WeakSet()
+
+
+@atexit.register
+def _stop_relays() -> None:
+    """A relay thread must not poll its page-locked block while the HIP runtime unmaps it at process exit
+    (csrc/kernels/loopback.h).  An abort ends the thread; this ends those of links nobody aborted."""
+    for c in list(_live):
+        if c._relay is not None:
+            c._relay.stop()
 
 
 class LoopbackComm:
@@ -78,7 +95,8 @@ class LoopbackComm:
         self._peer_ring = None
         self._ctl_name = None
         self._mm = None
-        self._ctl_host = self._ctl_dev = 0
+        self._relay = None
+        self._ctl_dev = 0
         store.set(f"{key}/lb_ring{rank}", handle)
         store.set(f"{key}/lb_owner{rank}", f"{os.getpid()}:{self._ring}".encode())
         if rank == 0:                                              # rank 0 owns the control block
@@ -97,9 +115,14 @@ class LoopbackComm:
         finally:
             os.close(fd)
         self._arr = np.frombuffer(self._mm, dtype=np.uint8)
-        self._ctl_host = int(self._arr.ctypes.data)
+        # the kernels work on a page-locked mirror of the block; the relay carries this rank's words out of
+        # it and the peer's words and the abort word into it (csrc/kernels/loopback.h)
+        d_out, d_in = self.rank, 1 - self.rank
         with torch.cuda.device(self.device):
-            self._ctl_dev = _kernels().host_register(self._ctl_host, CTL_BYTES)
+            self._relay = _kernels().LbRelay(self._arr, [_POSTED[d_out], _CONSUMED[d_in], _STATUS[self.rank]],
+                                             [_POSTED[d_in], _CONSUMED[d_out], _ABORT], _ABORT)
+        self._ctl_dev = self._relay.dev
+        _live.add(self)
 
     def start_watch(self, watch_us: int, abort_on_error: bool) -> None:
         pass                                                       # errors surface through `failed`

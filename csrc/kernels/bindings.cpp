@@ -13,7 +13,7 @@
 #include <vector>
 
 #include "kernels.h"
-
+#include "loopback.h"
 
 
 namespace py = pybind11;
@@ -126,15 +126,19 @@ PYBIND11_MODULE(_C, m) {
   m.def("lb_signal", [](u64 ctr, unsigned long long value, u64 s) {
     check(adapt::lb_signal(P<unsigned long long>(ctr), value, S(s)), "lb_signal");
   });
-  // page-lock a host range for the GPU (mapped, portable) and return its device address
-  m.def("host_register", [](u64 ptr, size_t n) {
-    check(hipHostRegister(reinterpret_cast<void*>(ptr), n, hipHostRegisterMapped | hipHostRegisterPortable),
-          "host_register");
-    void* d = nullptr;
-    check(hipHostGetDevicePointer(&d, reinterpret_cast<void*>(ptr), 0), "host_register: device pointer");
-    return reinterpret_cast<u64>(d);
-  });
-  m.def("host_unregister", [](u64 ptr) { check(hipHostUnregister(reinterpret_cast<void*>(ptr)), "host_unregister"); });
+  // the loopback link's control block as its kernels see it (loopback.h): `shared` is the mapping both
+  // processes hold, kept alive as long as the relay; `dev` the device address of the page-locked mirror
+  py::class_<adapt::LbRelay>(m, "LbRelay")
+      .def(py::init([](py::buffer shared, std::vector<size_t> out_words, std::vector<size_t> in_words,
+                       size_t abort_word) {
+             py::buffer_info b = shared.request(/*writable=*/true);
+             return new adapt::LbRelay(b.ptr, static_cast<size_t>(b.size * b.itemsize), std::move(out_words),
+                                       std::move(in_words), abort_word);
+           }),
+           py::arg("shared"), py::arg("out_words"), py::arg("in_words"), py::arg("abort_word"),
+           py::keep_alive<1, 2>())
+      .def("stop", &adapt::LbRelay::stop)
+      .def_property_readonly("dev", &adapt::LbRelay::dev);
   m.def("spin_flag", [](u64 flag, u64 out, double timeout_ms, u64 s) {
     check(adapt::spin_flag(P<const int>(flag), P<int>(out), timeout_ms, S(s)), "spin_flag");
   });

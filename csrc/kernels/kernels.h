@@ -66,7 +66,8 @@ void conv_cfg_tile(int cfg, int* bm, int* bn);
 // diagnostic: occupy stream `s` until *flag != 0 (host-written) or timeout_ms; *out = 1 (flag) / 2 (timeout)
 hipError_t spin_flag(const int* flag, int* out, double timeout_ms, hipStream_t s);
 // test-only loopback link (loopback.hip): wait until *ctr >= target (or *abort_word != 0, or timeout_ms) /
-// publish *ctr = value behind the stream's earlier work; ctr / abort_word / status in mapped host memory
+// publish *ctr = value behind the stream's earlier work; ctr / abort_word / status in page-locked host
+// memory (the block an LbRelay of loopback.h mirrors)
 hipError_t lb_wait(const unsigned long long* ctr, unsigned long long target, const int* abort_word, int* status,
                    double timeout_ms, hipStream_t s);
 hipError_t lb_signal(unsigned long long* ctr, unsigned long long value, hipStream_t s);

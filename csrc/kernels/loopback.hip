@@ -3,7 +3,8 @@
 // a fallback).  The data path of the RCCL branch of a pipeline stage (parallel/stage_runtime.py, nccl
 // backend) otherwise runs only when every stage owns a GPU of its own.  A message is copied into a slot of
 // a ring in device memory that the sender exported by IPC handle; the hand-off is two counters in a
-// page-locked host control block mapped by both processes:
+// control block both processes map, which each process's kernels see through a page-locked block of
+// its own that a host relay keeps in step with the shared one (loopback.h):
 //   sender stream:   wait(consumed >= seq - depth) -> copies into slot seq % depth -> signal(posted = seq)
 //   receiver stream: wait(posted >= seq) -> copies out of the slot -> signal(consumed = seq)
 // A wait is one wave spinning on system-scope relaxed atomic loads of host memory; it ends when the
@@ -11,7 +12,13 @@
 // wall-clock bound, and reports which into a host status word, so every wave always terminates.
 #include <hip/hip_runtime.h>
 
+#include <chrono>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+
 #include "kernels.h"
+#include "loopback.h"
 
 namespace adapt {
 
@@ -55,6 +62,53 @@ hipError_t lb_wait(const unsigned long long* ctr, unsigned long long target, con
 hipError_t lb_signal(unsigned long long* ctr, unsigned long long value, hipStream_t s) {
   hipLaunchKernelGGL(lb_signal_kernel, dim3(1), dim3(64), 0, s, ctr, value);
   return hipGetLastError();
+}
+
+LbRelay::LbRelay(void* shared, size_t bytes, std::vector<size_t> out_words, std::vector<size_t> in_words,
+                 size_t abort_word)
+    : shared_(static_cast<unsigned char*>(shared)), out_(std::move(out_words)), in_(std::move(in_words)),
+      abort_(abort_word) {
+  auto word_ok = [bytes](size_t off) { return off % 8 == 0 && off + 8 <= bytes; };
+  bool ok = shared != nullptr && reinterpret_cast<uintptr_t>(shared) % 8 == 0 && word_ok(abort_);
+  for (size_t off : out_) ok = ok && word_ok(off);
+  for (size_t off : in_) ok = ok && word_ok(off);
+  if (!ok) throw std::invalid_argument("LbRelay: words must be 8-aligned and inside the control block");
+  hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&pinned_), bytes,
+                               hipHostMallocMapped | hipHostMallocCoherent);
+  if (e == hipSuccess) {
+    std::memset(pinned_, 0, bytes);
+    e = hipHostGetDevicePointer(&dev_, pinned_, 0);
+  }
+  if (e != hipSuccess) throw std::runtime_error(std::string("LbRelay: ") + hipGetErrorString(e));
+  thread_ = std::thread([this] { run(); });
+}
+
+void LbRelay::stop() {
+  stop_.store(true);
+  if (thread_.joinable()) thread_.join();
+}
+
+LbRelay::~LbRelay() {
+  stop();
+  __atomic_store_n(reinterpret_cast<uint64_t*>(pinned_ + abort_), uint64_t{1}, __ATOMIC_RELEASE);
+}
+
+bool LbRelay::mirror() {
+  auto copy = [](unsigned char* dst, const unsigned char* src) {
+    const uint64_t v = __atomic_load_n(reinterpret_cast<const uint64_t*>(src), __ATOMIC_ACQUIRE);
+    uint64_t* d = reinterpret_cast<uint64_t*>(dst);
+    if (__atomic_load_n(d, __ATOMIC_RELAXED) != v) __atomic_store_n(d, v, __ATOMIC_RELEASE);
+  };
+  for (size_t off : out_) copy(shared_ + off, pinned_ + off);
+  for (size_t off : in_) copy(pinned_ + off, shared_ + off);
+  return __atomic_load_n(reinterpret_cast<const uint64_t*>(pinned_ + abort_), __ATOMIC_RELAXED) != 0;
+}
+
+void LbRelay::run() {
+  while (!stop_.load(std::memory_order_relaxed)) {
+    if (mirror()) break;
+    std::this_thread::sleep_for(std::chrono::microseconds(20));
+  }
 }
 
 }  // namespace adapt

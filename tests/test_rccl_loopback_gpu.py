@@ -59,6 +59,37 @@ def _stop(d, procs):
             pass
 
 
+def test_relay_carries_the_control_words_between_two_mirrors():
+    """Two relays on one shared block, as the two ranks of a link hold them: a counter a kernel publishes in
+    one rank's page-locked mirror ends a wait on the other's, and the abort word written into the shared
+    block ends a wait whose counter never comes.  Every wait carries a 20 s bound of its own."""
+    import torch
+    from adaptive_deep_learning_architecture_for_parallel_and_fault_tolerant_inference_amd.ops._lib import kernels
+    from adaptive_deep_learning_architecture_for_parallel_and_fault_tolerant_inference_amd.parallel import \
+        loopback_comm as lb
+    K = kernels()
+    shared = np.zeros(lb.CTL_BYTES, dtype=np.uint8)
+    words = [[lb._POSTED[r], lb._CONSUMED[1 - r], lb._STATUS[r]] for r in (0, 1)]
+    relays = [K.LbRelay(shared, words[r], [lb._POSTED[1 - r], lb._CONSUMED[r], lb._ABORT], lb._ABORT)
+              for r in (0, 1)]
+    s0, s1 = torch.cuda.Stream(), torch.cuda.Stream()
+    d0, d1 = relays[0].dev, relays[1].dev
+    K.lb_wait(d1 + lb._POSTED[0], 7, d1 + lb._ABORT, d1 + lb._STATUS[1], 20e3, s1.cuda_stream)
+    K.lb_signal(d0 + lb._POSTED[0], 7, s0.cuda_stream)
+    s1.synchronize()
+    assert int(shared[lb._POSTED[0]:lb._POSTED[0] + 8].view(np.uint64)[0]) == 7
+    assert int(shared[lb._STATUS[1]:lb._STATUS[1] + 4].view(np.int32)[0]) == 0
+    K.lb_wait(d1 + lb._POSTED[0], 8, d1 + lb._ABORT, d1 + lb._STATUS[1], 20e3, s1.cuda_stream)
+    shared[lb._ABORT:lb._ABORT + 4].view(np.int32)[0] = 1
+    t0 = time.time()
+    s1.synchronize()
+    assert time.time() - t0 < 5.0, "the wait ran to its own bound: the abort word did not reach it"
+    for r in relays + relays:                        # stop() may be called again: the exit hook and the
+        r.stop()                                     # destructor both do
+    with pytest.raises(ValueError):
+        K.LbRelay(shared, [lb.CTL_BYTES], [], lb._ABORT)
+
+
 @pytest.mark.parametrize("fault", ["none", "kill", "hang"])
 def test_rccl_branch_over_loopback_links(fault):
     """Three GPU stage processes on cuda:0, transport "rccl": the steady pipeline matches the fp32 oracle;

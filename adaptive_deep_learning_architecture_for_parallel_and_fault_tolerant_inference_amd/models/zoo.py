@@ -30,7 +30,8 @@ Not from `keras.applications` (models whose output is a map, not a class vector)
 
 * U-Net (`unet`, `unet_bilinear`, test size `unet_tiny`): Conv2DTranspose or UpSampling2D decoders, skip
   Concatenates; 31,031,745 parameters at base 64, depth 4, one class, RGB input.
-* Stable Diffusion VAE decoder (`sd_vae_decoder`, test size `vae_decoder_micro`): GroupNormalization + swish
+* Stable Diffusion VAE decoder (`sd_vae_decoder`, test sizes `vae_decoder_micro` and, with a mid-block
+  head of 160 that takes the wide attention kernel, `vae_decoder_wide_micro`): GroupNormalization + swish
   residual blocks, one-head MultiHeadAttention on the (H, W, C) map, nearest UpSampling2D; a 64 x 64 x 4 latent
   to a 512 x 512 x 3 image, 49,490,199 parameters (the published decoder's 49,490,179 and the 20 of the 1x1
   post-quantisation conv in front of it).
@@ -478,6 +479,8 @@ def build_unet(name: str = "unet", classes: int = 1, input_shape=None, base: int
 VAE_DECODER = {
     "sd_vae_decoder": ((512, 512, 256, 128), 3, 32, (64, 64, 4)),
     "vae_decoder_micro": ((32, 32, 16, 8), 1, 4, (8, 8, 4)),
+    # the smallest decoder whose attention is a wide head (one head of 160 over 64 tokens)
+    "vae_decoder_wide_micro": ((160, 32, 16, 8), 1, 4, (8, 8, 4)),
 }
 VAE_EPS = 1e-5
 VAE_LATENT_SCALE = 0.18215

@@ -29,6 +29,24 @@ def attention_path(key_dim: int, value_dim: int) -> str:
     return "mfma" if kernels().attention_path(int(key_dim), int(value_dim)) else "plain"
 
 
+def attention_kernel(key_dim: int, value_dim: int) -> str:
+    """The kernel `attention` launches for a head of this size on aligned buffers, plain, causal or grouped-query:
+    'mfma' (head sizes that are multiples of 16 up to 128), 'wide' (multiples of 16 up to 512 with the larger above
+    128: the head-split kernel of csrc/kernels/attention_wide.h) or 'plain' (one wave per query: every other size,
+    and every size under a padding mask or with a pointer or row stride that is not a multiple of 4 elements)."""
+    k, d, dv = kernels(), int(key_dim), int(value_dim)
+    return "mfma" if k.attention_path(d, dv) else "wide" if k.attention_wide_path(d, dv) else "plain"
+
+
+def attention_wide_tiles(key_dim: int, value_dim: int):
+    """(queries per block, keys per LDS tile) of the head-split kernel at a head size that `attention_kernel` calls
+    'wide'."""
+    k, d, dv = kernels(), int(key_dim), int(value_dim)
+    if not k.attention_wide_path(d, dv):
+        raise ValueError(f"attention_wide_tiles: ({d}, {dv}) is not a head of the wide kernel")
+    return int(k.attention_wide_query_tile(d, dv)), int(k.attention_wide_key_tile(d, dv))
+
+
 def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, tokens: int, heads: int, key_dim: int,
               value_dim: Optional[int] = None, stream=None, causal: bool = False,
               key_mask: Optional[torch.Tensor] = None, kv_heads: Optional[int] = None) -> torch.Tensor:

@@ -14,7 +14,11 @@
 // heads d + hkv d + (h / g) dv, everything else as SelfSrc.  Per (image, head) the arithmetic is that of a plain
 // launch on rows in which each K / V head stands g times, so the two agree bit for bit.  SelfSrc and the templates
 // are untouched.
-#include "attention_core.h"
+//
+// Wide heads (d and dv multiples of 16 up to 512, the larger above 128; attention_wide.h): the plain, causal, gqa and
+// gqa-causal entry points launch the head-split kernel on the same policies when the buffers are aligned to 4
+// elements; the padding-mask entry points and misaligned buffers stay on the plain kernel at these sizes.
+#include "attention_wide.h"
 
 namespace adapt {
 namespace {
@@ -79,6 +83,8 @@ hipError_t attention_gqa_launch(const T* qkv, T* out, int B, int Tn, int heads, 
   GqaSrc<T> src;
   src.qkv = qkv; src.Tn = Tn; src.heads = heads; src.d = d; src.dv_ = dv; src.ld_in = ld_in;
   src.hkv = hkv; src.g = heads / hkv;
+  if (attention_wide_path(d, dv) && attn::attention_vec4((uintptr_t)qkv | (uintptr_t)out, ld_in | ld_out, (int)sizeof(T)))
+    return attn::attention_wide_launch<T, GqaSrc<T>, CAUSAL>(src, out, ld_out, B, s);
   return attn::attention_core_launch<T, GqaSrc<T>, CAUSAL>(src, out, ld_out, B, mfma, s);
 }
 
@@ -102,6 +108,8 @@ hipError_t attention_launch(const T* qkv, T* out, int B, int Tn, int heads, int 
     }
     return hipErrorInvalidValue;                      // a padding mask together with the causal mask is not built
   }
+  if (attention_wide_path(d, dv) && attn::attention_vec4((uintptr_t)qkv | (uintptr_t)out, ld_in | ld_out, (int)sizeof(T)))
+    return attn::attention_wide_launch<T, SelfSrc<T>, CAUSAL>(SelfSrc<T>{qkv, Tn, heads, d, dv, ld_in}, out, ld_out, B, s);
   return attn::attention_core_launch<T, SelfSrc<T>, CAUSAL>(SelfSrc<T>{qkv, Tn, heads, d, dv, ld_in}, out, ld_out, B,
                                                             mfma, s);
 }
@@ -113,6 +121,11 @@ int attention_key_tile() { return attn::ATTN_KT; }
 
 // 1: the MFMA path, 0: the plain kernel (which a misaligned buffer or stride takes as well)
 int attention_path(int d, int dv) { return d >= 16 && dv >= 16 && d <= 128 && dv <= 128 && d % 16 == 0 && dv % 16 == 0; }
+
+// 1: a wide head, on the head-split kernel when the buffers are aligned as the MFMA path needs them; 0: not one
+int attention_wide_path(int d, int dv) { return attn::wide_dw(d, dv) != 0; }
+int attention_wide_query_tile(int d, int dv) { return attn::wide_dw(d, dv) ? attn::WIDE_WQ : 0; }
+int attention_wide_key_tile(int d, int dv) { return attn::wide_dw(d, dv) ? attn::WIDE_WK : 0; }
 
 hipError_t attention_f32(const float* qkv, float* out, int B, int T, int heads, int d, int dv, int ld_in, int ld_out,
                          hipStream_t s) {

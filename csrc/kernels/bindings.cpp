@@ -498,6 +498,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("attention_path", &adapt::attention_path);
   m.def("attention_query_tile", &adapt::attention_query_tile);
   m.def("attention_key_tile", &adapt::attention_key_tile);
+  m.def("attention_wide_path", &adapt::attention_wide_path);
+  m.def("attention_wide_query_tile", &adapt::attention_wide_query_tile);
+  m.def("attention_wide_key_tile", &adapt::attention_wide_key_tile);
   m.def("attention_qkv_f32", [](u64 q, u64 k, u64 v, u64 out, int B, int Tq, int Tk, int heads, int d, int dv, int ldq,
                                 int ldk, int ldv, int ld_out, u64 s) {
     check(adapt::attention_qkv_f32(P<const float>(q), P<const float>(k), P<const float>(v), P<float>(out), B, Tq, Tk,

@@ -443,6 +443,11 @@ hipError_t attention_gqa_causal_bf16(const bf16* qkv, bf16* out, int B, int T, i
 int attention_path(int d, int dv);     // 1: MFMA path, 0: plain kernel
 int attention_query_tile();            // queries per block of the MFMA path
 int attention_key_tile();              // keys per LDS tile of the MFMA path
+// wide heads (attention_wide.h): d and dv multiples of 16 up to 512 with the larger above 128, on the plain, causal,
+// gqa and gqa-causal entry points with aligned buffers; `attention_path` is 0 for them as it was
+int attention_wide_path(int d, int dv);         // 1: the head-split kernel serves this head, 0: it does not
+int attention_wide_query_tile(int d, int dv);   // queries per block of the head-split kernel at this head; 0: not wide
+int attention_wide_key_tile(int d, int dv);     // keys per LDS tile of the head-split kernel at this head; 0: not wide
 // Attention core with separate sources (cross_attention.hip): q [B*Tq][ldq], k [B*Tk][ldk], v [B*Tk][ldv], each
 // pointer already offset to its part's first column (head h at h*d for Q and K, h*dv for V; Q pre-scaled), out
 // [B*Tq][ld_out] with heads*dv true channels (the rest of a row is written as zeros).  The MFMA path takes what

@@ -27,6 +27,16 @@ right-padded lengths of mean T / 2 against the all-kept time (the gain from the 
 waves) and against `scaled_dot_product_attention` with a boolean mask of the same lengths.
 
     python tools/attention_bench.py --padding [--batch 32]
+
+`--wide` times the head-split kernel for wide heads (csrc/kernels/attention_wide.h) on the Stable Diffusion VAE
+decoder's mid-block (one head of 512 over 4,096 tokens, 1 and 4 images), a Gemma-like shape (8 query heads over one
+key / value head of 256, 1,024 tokens, causal, 8 images) and a U-Net-like shape (8 heads of 160, 1,024 tokens, 4
+images), each in fp32 and on bf16 activations, against the plain kernel on the same values (rows of stride width + 1:
+a stride off the 4-element grid takes the plain kernel, which is what these head sizes ran on before) and against
+`scaled_dot_product_attention` in the same type.  The batch is part of the shape; the plain kernel's graph holds one
+call, it runs for tens to hundreds of milliseconds.
+
+    python tools/attention_bench.py --wide
 """
 import argparse
 import os
@@ -59,13 +69,14 @@ def capture(run, reps):
     return g
 
 
-def interleaved_us(runs, reps, rounds):
+def interleaved_us(runs, reps, rounds, reps_of=None):
     """Median microseconds per call of each of `runs` (name -> callable): every round replays each
-    implementation's graph once, in turn."""
+    implementation's graph once, in turn.  `reps_of`: calls per graph of the implementations that differ from `reps`."""
     graphs = {}
+    reps_of = {name: (reps_of or {}).get(name, reps) for name in runs}
     for name, run in runs.items():
         try:
-            graphs[name] = capture(run, reps)
+            graphs[name] = capture(run, reps_of[name])
         except RuntimeError as e:                                # a library path that cannot be captured
             print(f"  {name} not graph-timed: {str(e).splitlines()[0]}")
     times = {name: [] for name in graphs}
@@ -76,7 +87,7 @@ def interleaved_us(runs, reps, rounds):
             g.replay()
             e1.record()
             e1.synchronize()
-            times[name].append(e0.elapsed_time(e1) / reps * 1e3)
+            times[name].append(e0.elapsed_time(e1) / reps_of[name] * 1e3)
     return {name: sorted(times[name])[rounds // 2] if times.get(name) else float("nan") for name in runs}
 
 
@@ -185,6 +196,43 @@ def bench_padding(name, B, T, h, d, reps, rounds):
     return t
 
 
+# (name, batch, tokens, query heads, key / value heads, key_dim = value_dim, causal)
+WIDE_SHAPES = [("sd_vae_mid", 1, 4096, 1, 1, 512, False), ("sd_vae_mid", 4, 4096, 1, 1, 512, False),
+               ("gemma_like", 8, 1024, 8, 1, 256, True), ("unet_like", 4, 1024, 8, 8, 160, False)]
+
+
+def bench_wide(name, B, T, h, hkv, d, causal, reps, rounds):
+    w_in, w_out = (h + 2 * hkv) * d, h * d
+    x = torch.randn(B * T, w_in, device="cuda")
+    x[:, :h * d] *= d ** -0.5
+    q = x[:, :h * d].reshape(B, T, h, d).permute(0, 2, 1, 3).contiguous()
+    k, v = (x[:, h * d + i * hkv * d:h * d + (i + 1) * hkv * d].reshape(B, T, hkv, d).permute(0, 2, 1, 3)
+            .repeat_interleave(h // hkv, dim=1).contiguous() for i in range(2))
+    flop = 2.0 * B * (T * (T + 1) // 2 if causal else T * T) * h * 2 * d
+    for dtype in (torch.float32, torch.bfloat16):
+        xa = x.to(dtype)
+        xo = torch.zeros(B * T, w_in + 1, device="cuda", dtype=dtype)              # the same values, stride off the grid
+        xo[:, :w_in] = xa
+        out = torch.empty(B * T, w_out, device="cuda", dtype=dtype)
+        outo = torch.empty(B * T, w_out + 1, device="cuda", dtype=dtype)
+        qt, kt, vt = q.to(dtype), k.to(dtype), v.to(dtype)
+
+        def sdpa():
+            return F.scaled_dot_product_attention(qt, kt, vt, scale=1.0, is_causal=causal)
+
+        t = interleaved_us({"wide": lambda: A.attention(xa, out, B, T, h, d, d, causal=causal, kv_heads=hkv),
+                            "plain": lambda: A.attention(xo, outo, B, T, h, d, d, causal=causal, kv_heads=hkv),
+                            "sdpa": sdpa}, reps, rounds, reps_of={"plain": 1})
+        want = sdpa().permute(0, 2, 1, 3).reshape(B * T, w_out).float()
+        diff = (want - out.float()).abs().max().item()
+        diffo = (outo[:, :w_out].float() - out.float()).abs().max().item()
+        print(f"{name:10s} B{B} T{T} h{h}/{hkv} d{d} {'causal' if causal else 'full  '} {str(dtype)[6:]:8s} "
+              f"[{A.attention_kernel(d, d)}, tiles {A.attention_wide_tiles(d, d)}]: wide {t['wide']:9.1f} us "
+              f"({flop / t['wide'] / 1e6:5.1f} TF/s) | plain {t['plain']:11.1f} us ({t['plain'] / t['wide']:6.1f}x wide) | "
+              f"sdpa {t['sdpa']:9.1f} us ({t['sdpa'] / t['wide']:5.2f}x wide) | max diff vs sdpa {diff:.2e}, vs plain "
+              f"{diffo:.2e}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -192,8 +240,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--causal", action="store_true", help="the causal kernel on GPT-2 shapes (module docstring)")
     ap.add_argument("--padding", action="store_true", help="the padding-mask kernel on DistilBERT shapes")
+    ap.add_argument("--wide", action="store_true", help="the head-split kernel on wide heads (module docstring)")
     a = ap.parse_args()
     print(torch.cuda.get_device_name(0))
+    if a.wide:
+        for name, B, T, h, hkv, d, causal in WIDE_SHAPES:
+            bench_wide(name, B, T, h, hkv, d, causal, a.reps, a.rounds)
+        return
     if a.padding:
         for name, T, h, d in PADDING_SHAPES:
             bench_padding(name, a.batch, T, h, d, a.reps, a.rounds)

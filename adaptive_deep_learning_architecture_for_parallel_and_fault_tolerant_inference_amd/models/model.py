@@ -82,10 +82,12 @@ class Model:
 
     # ------------------------------------------------------------ compute
     def predict(self, x: np.ndarray, device: Optional[str] = None, batch: Optional[int] = None,
-                precision: str = "fp32") -> np.ndarray:
+                precision: str = "fp32", attention_math: Optional[str] = None) -> np.ndarray:
         """Single-device inference (`test/local_infer.py:22`): our HIP runtime on
         a GPU (precision "bf16" or "fp32", the reference's Keras float32), the
-        native OpenMP fp32 path on CPU.  Inputs are NHWC float32 images."""
+        native OpenMP fp32 path on CPU.  Inputs are NHWC float32 images.
+        attention_math: SliceExecutor's switch for the self-attention cores ("fp32",
+        or "bf16" under precision "bf16"; None reads ADAPT_ATTENTION_MATH)."""
         import torch
         x = np.asarray(x, np.float32)
         if device is None:
@@ -99,13 +101,14 @@ class Model:
             return ex(x)
         from ..runtime.executor import SliceExecutor
         b = batch or x.shape[0]
-        key = (device, b, precision)
+        key = (device, b, precision, attention_math)
         ent = self._executors.get(key)
         if ent is None:
             # one hipGraph per (device, batch) and a pinned result buffer: a request is
             # H2D -> graph replay -> async D2H -> one sync (the reference re-enters TF's
             # per-layer dispatch on every `model.predict`, test/local_infer.py:22)
-            ex = SliceExecutor(self.graph, self.weights, b, device=device, precision=precision)
+            ex = SliceExecutor(self.graph, self.weights, b, device=device, precision=precision,
+                               attention_math=attention_math)
             ex.capture()
             yout = ex.output_buf(ex.outputs[0])
             ent = self._executors[key] = (ex, torch.empty(yout.shape, dtype=yout.dtype, pin_memory=True))

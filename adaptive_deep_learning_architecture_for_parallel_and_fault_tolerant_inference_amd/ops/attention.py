@@ -9,7 +9,7 @@ not take is an error, never a fall-back to torch.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
@@ -29,12 +29,29 @@ def attention_path(key_dim: int, value_dim: int) -> str:
     return "mfma" if kernels().attention_path(int(key_dim), int(value_dim)) else "plain"
 
 
-def attention_kernel(key_dim: int, value_dim: int) -> str:
+ATTENTION_MATH = ("fp32", "bf16")
+
+
+def attention_bf16_tiles():
+    """(queries per block, keys per LDS tile) of the bf16-MFMA kernel (`math="bf16"`)."""
+    k = kernels()
+    return int(k.attention_bf16_query_tile()), int(k.attention_bf16_key_tile())
+
+
+def attention_kernel(key_dim: int, value_dim: int, math: str = "fp32", key_mask: bool = False,
+                     strides: Sequence[int] = ()) -> str:
     """The kernel `attention` launches for a head of this size on aligned buffers, plain, causal or grouped-query:
     'mfma' (head sizes that are multiples of 16 up to 128), 'wide' (multiples of 16 up to 512 with the larger above
     128: the head-split kernel of csrc/kernels/attention_wide.h) or 'plain' (one wave per query: every other size,
-    and every size under a padding mask or with a pointer or row stride that is not a multiple of 4 elements)."""
+    and every size under a padding mask or with a pointer or row stride that is not a multiple of 4 elements).
+    `math="bf16"` (bf16 tensors): 'mfma_bf16', the bf16-MFMA kernel of csrc/kernels/attention_bf16.h, for the head
+    sizes of 'mfma' when there is no `key_mask` and every row stride in `strides` is a multiple of 8 elements;
+    everywhere else the answer, like the launch, is the one of `math="fp32"`."""
+    if math not in ATTENTION_MATH:
+        raise ValueError(f"attention_kernel: math must be one of {ATTENTION_MATH}, got {math!r}")
     k, d, dv = kernels(), int(key_dim), int(value_dim)
+    if math == "bf16" and k.attention_bf16_path(d, dv) and not key_mask and not any(int(x) % 8 for x in strides):
+        return "mfma_bf16"
     return "mfma" if k.attention_path(d, dv) else "wide" if k.attention_wide_path(d, dv) else "plain"
 
 
@@ -49,7 +66,8 @@ def attention_wide_tiles(key_dim: int, value_dim: int):
 
 def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, tokens: int, heads: int, key_dim: int,
               value_dim: Optional[int] = None, stream=None, causal: bool = False,
-              key_mask: Optional[torch.Tensor] = None, kv_heads: Optional[int] = None) -> torch.Tensor:
+              key_mask: Optional[torch.Tensor] = None, kv_heads: Optional[int] = None,
+              math: str = "fp32") -> torch.Tensor:
     """out = softmax(Q K^T) V per (image, head); `causal`: query i attends keys j <= i only (Keras'
     use_causal_mask), on the kernels' masked instantiations, which skip the key tiles above the diagonal.  qkv [..., ld_in] holds batch * tokens rows of [Q | K | V]
     (head-major inside each part; Q already scaled by 1/sqrt(key_dim)), out [..., ld_out] gets heads * value_dim
@@ -61,7 +79,16 @@ def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, tokens: int, hea
     token are not loaded (the kernels' masked instantiations).  `kv_heads` (grouped-query attention): the `heads`
     query heads share kv_heads key / value heads, head h reads K / V head h // (heads // kv_heads), and a row is
     [Q: heads x key_dim | K: kv_heads x key_dim | V: kv_heads x value_dim]; given and different from `heads` it
-    runs the gqa entry points (plain or causal, never with `key_mask`), else the launch is the one it always was."""
+    runs the gqa entry points (plain or causal, never with `key_mask`), else the launch is the one it always was.
+    `math`: "fp32" (the default: both products on the fp32 matrix instruction whatever the tensors hold) or "bf16"
+    (bf16 tensors only: both products on the bf16 matrix instruction with fp32 accumulation, the softmax in fp32, the
+    probabilities rounded to bf16 once: csrc/kernels/attention_bf16.h).  "bf16" runs that kernel where it serves (head
+    sizes that are multiples of 16 up to 128, no `key_mask`, pointers and row strides that are multiples of 8
+    elements; `attention_kernel` says 'mfma_bf16') and is exactly the "fp32" launch everywhere else."""
+    if math not in ATTENTION_MATH:
+        raise ValueError(f"attention: math must be one of {ATTENTION_MATH}, got {math!r}")
+    if math == "bf16" and qkv.dtype != torch.bfloat16:
+        raise ValueError(f"attention: math=\"bf16\" takes bf16 tensors, got {qkv.dtype}")
     dv = int(value_dim or key_dim)
     B, T, h, d = int(batch), int(tokens), int(heads), int(key_dim)
     hkv = h if kv_heads is None else int(kv_heads)
@@ -89,6 +116,10 @@ def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, tokens: int, hea
             raise ValueError(f"attention: key_mask{tuple(key_mask.shape)} does not hold {B} x {T} values")
         fn = kernels().attention_masked_f32 if qkv.dtype == torch.float32 else kernels().attention_masked_bf16
         fn(ptr(qkv), ptr(key_mask), ptr(out), B, T, h, d, dv, int(ld_in), int(ld_out), stream_handle(stream))
+        return out
+    if math == "bf16":                # the entry point itself falls back to the launches below where it does not serve
+        kernels().attention_mm_bf16(ptr(qkv), ptr(out), B, T, h, hkv, d, dv, int(ld_in), int(ld_out), int(bool(causal)),
+                                    stream_handle(stream))
         return out
     if hkv != h:
         k, f32 = kernels(), qkv.dtype == torch.float32

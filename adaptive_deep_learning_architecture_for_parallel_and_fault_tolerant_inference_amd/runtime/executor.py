@@ -92,7 +92,7 @@ class SliceExecutor:
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], batch: int, device="cuda",
                  outputs: Optional[Sequence[str]] = None, tune: bool = False, num_sets: int = 1,
-                 precision: str = "fp32", private_sets: bool = False):
+                 precision: str = "fp32", private_sets: bool = False, attention_math: Optional[str] = None):
         """precision: "bf16" (bf16 activations / weights, fp32 accumulation: the
         fast path) or "fp32" (fp32 activations and weights on the fp32 matrix
         cores: the reference's Keras float32 numerics, csrc/kernels/conv_f32.hip).
@@ -100,9 +100,22 @@ class SliceExecutor:
         and scratch (split-K workspace, stream-K counters, head / GAP partials), so
         the sets' graphs may replay concurrently on different streams (a serving
         stage keeps two micro-batches in flight); by default the sets share them
-        and replay one after the other."""
+        and replay one after the other.
+        attention_math: "fp32" (both products of a self-attention core on the fp32
+        matrix instruction, whatever the activations) or "bf16" (bf16 precision only:
+        the bf16-MFMA kernel of csrc/kernels/attention_bf16.h where it serves); None
+        reads ADAPT_ATTENTION_MATH, default fp32.  It reaches the launch of the
+        `attention` steps with one [Q | K | V] source only: the plan is the same, and
+        cross-attention and window attention ignore it."""
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"precision must be bf16 or fp32, got {precision!r}")
+        if attention_math is None:
+            attention_math = os.environ.get("ADAPT_ATTENTION_MATH", "fp32")
+        if attention_math not in attn_ops.ATTENTION_MATH:
+            raise ValueError(f"attention_math must be one of {attn_ops.ATTENTION_MATH}, got {attention_math!r}")
+        if attention_math == "bf16" and precision != "bf16":
+            raise ValueError("attention_math=\"bf16\" needs precision=\"bf16\": the kernel takes bf16 activations")
+        self.attention_math = attention_math
         self.g = g
         self.batch = batch
         self.device = torch.device(device)
@@ -392,7 +405,8 @@ class SliceExecutor:
             p = st.p
             attn_ops.attention(b[st.ins[0]], b[st.out], self.batch, p["tokens"], p["heads"], p["key_dim"],
                                p["value_dim"], stream=stream, causal=bool(p.get("causal")),
-                               key_mask=b[st.ins[1]] if p.get("key_mask") else None, kv_heads=p.get("kv_heads"))
+                               key_mask=b[st.ins[1]] if p.get("key_mask") else None, kv_heads=p.get("kv_heads"),
+                               math=self.attention_math)
         elif st.kind == "rope":
             p = st.p
             attn_ops.rope(b[st.ins[0]], self.packed[i], b[st.out], p["tokens"], p["heads"], p["key_dim"],

@@ -18,6 +18,11 @@
 // Wide heads (d and dv multiples of 16 up to 512, the larger above 128; attention_wide.h): the plain, causal, gqa and
 // gqa-causal entry points launch the head-split kernel on the same policies when the buffers are aligned to 4
 // elements; the padding-mask entry points and misaligned buffers stay on the plain kernel at these sizes.
+//
+// bf16 matrix math (attention_bf16.h, opt-in through `attention_mm_bf16`): bf16 rows with head sizes of the MFMA path
+// and pointers and strides on the 8-element grid run the bf16-MFMA kernel on SelfSrc or GqaSrc; every other call of
+// that entry point is the launch of the entry points below, unchanged.
+#include "attention_bf16.h"
 #include "attention_wide.h"
 
 namespace adapt {
@@ -114,6 +119,31 @@ hipError_t attention_launch(const T* qkv, T* out, int B, int Tn, int heads, int 
                                                             mfma, s);
 }
 
+// 32-bit ranges of a [Q | K | V] launch with hkv key / value heads, as the two launchers above check them
+bool attention_fits(int B, int Tn, int heads, int hkv, int d, int dv, int ld_in, int ld_out) {
+  const long long lim = 0x7fffffffll;
+  if ((long long)heads * d + (long long)hkv * ((long long)d + dv) > ld_in || (long long)heads * dv > ld_out) return false;
+  return (long long)B * Tn * ld_in <= lim && (long long)B * Tn * ld_out <= lim && (long long)B * heads * Tn <= lim;
+}
+
+template <bool CAUSAL>
+hipError_t attention_mm_launch(const bf16* qkv, bf16* out, int B, int Tn, int heads, int hkv, int d, int dv, int ld_in,
+                               int ld_out, hipStream_t s) {
+  if (B < 1 || Tn < 1 || heads < 1 || hkv < 1 || heads % hkv || d < 1 || dv < 1 || !qkv || !out)
+    return hipErrorInvalidValue;
+  const bool serves = attention_bf16_path(d, dv) && attn::attention_vec8((uintptr_t)qkv | (uintptr_t)out, ld_in | ld_out);
+  if (!serves)                                        // exactly the launch of the fp32-math entry points
+    return hkv == heads ? attention_launch<bf16, CAUSAL>(qkv, out, B, Tn, heads, d, dv, ld_in, ld_out, s)
+                        : attention_gqa_launch<bf16, CAUSAL>(qkv, out, B, Tn, heads, hkv, d, dv, ld_in, ld_out, s);
+  if (!attention_fits(B, Tn, heads, hkv, d, dv, ld_in, ld_out)) return hipErrorInvalidValue;
+  if (hkv == heads)
+    return attn::attention_bf16_launch<SelfSrc<bf16>, CAUSAL>(SelfSrc<bf16>{qkv, Tn, heads, d, dv, ld_in}, out, ld_out, B, s);
+  GqaSrc<bf16> src;
+  src.qkv = qkv; src.Tn = Tn; src.heads = heads; src.d = d; src.dv_ = dv; src.ld_in = ld_in;
+  src.hkv = hkv; src.g = heads / hkv;
+  return attn::attention_bf16_launch<GqaSrc<bf16>, CAUSAL>(src, out, ld_out, B, s);
+}
+
 }  // namespace
 
 int attention_query_tile() { return attn::ATTN_QT; }
@@ -126,6 +156,21 @@ int attention_path(int d, int dv) { return d >= 16 && dv >= 16 && d <= 128 && dv
 int attention_wide_path(int d, int dv) { return attn::wide_dw(d, dv) != 0; }
 int attention_wide_query_tile(int d, int dv) { return attn::wide_dw(d, dv) ? attn::WIDE_WQ : 0; }
 int attention_wide_key_tile(int d, int dv) { return attn::wide_dw(d, dv) ? attn::WIDE_WK : 0; }
+
+// bf16 matrix math: 1 when the bf16-MFMA kernel serves a head of this size (on bf16 rows, without a padding mask,
+// with pointers and row strides that are multiples of 8 elements)
+int attention_bf16_path(int d, int dv) { return attention_path(d, dv); }
+int attention_bf16_query_tile() { return attn::B16_QT; }
+int attention_bf16_key_tile() { return attn::B16_KT; }
+
+// The opt-in entry point of the bf16-MFMA kernel: plain (kv_heads == heads) or grouped-query rows, causal or not.
+// Where the kernel does not serve (other head sizes, buffers off the 8-element grid) this is the launch that
+// attention_bf16 / attention_causal_bf16 / attention_gqa_bf16 / attention_gqa_causal_bf16 make
+hipError_t attention_mm_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, int kv_heads, int d, int dv, int ld_in,
+                             int ld_out, int causal, hipStream_t s) {
+  return causal ? attention_mm_launch<true>(qkv, out, B, T, heads, kv_heads, d, dv, ld_in, ld_out, s)
+                : attention_mm_launch<false>(qkv, out, B, T, heads, kv_heads, d, dv, ld_in, ld_out, s);
+}
 
 hipError_t attention_f32(const float* qkv, float* out, int B, int T, int heads, int d, int dv, int ld_in, int ld_out,
                          hipStream_t s) {

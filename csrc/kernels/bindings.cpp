@@ -501,6 +501,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("attention_wide_path", &adapt::attention_wide_path);
   m.def("attention_wide_query_tile", &adapt::attention_wide_query_tile);
   m.def("attention_wide_key_tile", &adapt::attention_wide_key_tile);
+  m.def("attention_mm_bf16", [](u64 qkv, u64 out, int B, int T, int heads, int kv_heads, int d, int dv, int ld_in,
+                                int ld_out, int causal, u64 s) {
+    check(adapt::attention_mm_bf16(P<const bf16>(qkv), P<bf16>(out), B, T, heads, kv_heads, d, dv, ld_in, ld_out, causal,
+                                   S(s)), "attention_mm_bf16");
+  });
+  m.def("attention_bf16_path", &adapt::attention_bf16_path);
+  m.def("attention_bf16_query_tile", &adapt::attention_bf16_query_tile);
+  m.def("attention_bf16_key_tile", &adapt::attention_bf16_key_tile);
   m.def("attention_qkv_f32", [](u64 q, u64 k, u64 v, u64 out, int B, int Tq, int Tk, int heads, int d, int dv, int ldq,
                                 int ldk, int ldv, int ld_out, u64 s) {
     check(adapt::attention_qkv_f32(P<const float>(q), P<const float>(k), P<const float>(v), P<float>(out), B, Tq, Tk,

@@ -448,6 +448,15 @@ int attention_key_tile();              // keys per LDS tile of the MFMA path
 int attention_wide_path(int d, int dv);         // 1: the head-split kernel serves this head, 0: it does not
 int attention_wide_query_tile(int d, int dv);   // queries per block of the head-split kernel at this head; 0: not wide
 int attention_wide_key_tile(int d, int dv);     // keys per LDS tile of the head-split kernel at this head; 0: not wide
+// bf16 matrix math (attention_bf16.h): both products on v_mfma_f32_16x16x32_bf16, softmax in fp32; opt-in.  bf16 rows,
+// plain (kv_heads == heads) or grouped-query, causal != 0 or not.  The bf16-MFMA kernel runs where
+// attention_bf16_path(d, dv) and the pointers and row strides are multiples of 8 elements; every other call is the
+// launch of the matching entry point above
+hipError_t attention_mm_bf16(const bf16* qkv, bf16* out, int B, int T, int heads, int kv_heads, int d, int dv, int ld_in,
+                             int ld_out, int causal, hipStream_t s);
+int attention_bf16_path(int d, int dv);   // 1: the bf16-MFMA kernel serves this head, 0: it does not
+int attention_bf16_query_tile();          // queries per block of the bf16-MFMA kernel
+int attention_bf16_key_tile();            // keys per LDS tile of the bf16-MFMA kernel
 // Attention core with separate sources (cross_attention.hip): q [B*Tq][ldq], k [B*Tk][ldk], v [B*Tk][ldv], each
 // pointer already offset to its part's first column (head h at h*d for Q and K, h*dv for V; Q pre-scaled), out
 // [B*Tq][ld_out] with heads*dv true channels (the rest of a row is written as zeros).  The MFMA path takes what

@@ -37,6 +37,13 @@ a stride off the 4-element grid takes the plain kernel, which is what these head
 call, it runs for tens to hundreds of milliseconds.
 
     python tools/attention_bench.py --wide
+
+`--math bf16` times the bf16-MFMA kernel (csrc/kernels/attention_bf16.h, `attention(..., math="bf16")`) on bf16 rows
+against the fp32-math kernel on the same rows (the default launch) and against `scaled_dot_product_attention` in
+bf16: the ViT shapes above at 32 images, GPT-2's causal shapes at 8 images, and Llama's grouped-query causal shapes
+(32 query heads over 4 of 64; 4,096 rows each).  The batch is part of the shape.
+
+    python tools/attention_bench.py --math bf16
 """
 import argparse
 import os
@@ -233,6 +240,38 @@ def bench_wide(name, B, T, h, hkv, d, causal, reps, rounds):
               f"{diffo:.2e}", flush=True)
 
 
+# (name, batch, tokens, query heads, key / value heads, key_dim = value_dim, causal)
+MATH_SHAPES = ([(n, 32, T, h, h, d, False) for n, T, h, d in SHAPES] + [(n, 8, T, h, h, d, True) for n, T, h, d in CAUSAL_SHAPES]
+               + [("llama_gqa", 32, 128, 32, 4, 64, True), ("llama_gqa", 8, 512, 32, 4, 64, True),
+                  ("llama_gqa", 2, 2048, 32, 4, 64, True), ("llama_like", 2, 2048, 32, 8, 128, True)])
+
+
+def bench_math(name, B, T, h, hkv, d, causal, reps, rounds):
+    w_in, w_out = (h + 2 * hkv) * d, h * d
+    x = torch.randn(B * T, w_in, device="cuda")
+    x[:, :h * d] *= d ** -0.5
+    x = x.to(torch.bfloat16)
+    q = x[:, :h * d].reshape(B, T, h, d).permute(0, 2, 1, 3).contiguous()
+    k, v = (x[:, h * d + i * hkv * d:h * d + (i + 1) * hkv * d].reshape(B, T, hkv, d).permute(0, 2, 1, 3)
+            .repeat_interleave(h // hkv, dim=1).contiguous() for i in range(2))
+    out, old = (torch.empty(B * T, w_out, device="cuda", dtype=torch.bfloat16) for _ in range(2))
+    flop = 2.0 * B * (T * (T + 1) // 2 if causal else T * T) * h * 2 * d
+
+    def sdpa():
+        return F.scaled_dot_product_attention(q, k, v, scale=1.0, is_causal=causal)
+
+    t = interleaved_us({"bf16": lambda: A.attention(x, out, B, T, h, d, d, causal=causal, kv_heads=hkv, math="bf16"),
+                        "fp32": lambda: A.attention(x, old, B, T, h, d, d, causal=causal, kv_heads=hkv),
+                        "sdpa": sdpa}, reps, rounds)
+    want = F.scaled_dot_product_attention(q.float(), k.float(), v.float(), scale=1.0, is_causal=causal)
+    want = want.permute(0, 2, 1, 3).reshape(B * T, w_out)
+    print(f"{name:12s} B{B} T{T} h{h}/{hkv} d{d} {'causal' if causal else 'full  '} "
+          f"[{A.attention_kernel(d, d, math='bf16')}, tiles {A.attention_bf16_tiles()}]: bf16 math {t['bf16']:8.1f} us "
+          f"({flop / t['bf16'] / 1e6:6.1f} TF/s) | fp32 math, same rows {t['fp32']:8.1f} us ({t['fp32'] / t['bf16']:5.2f}x) | "
+          f"sdpa bf16 {t['sdpa']:8.1f} us ({t['sdpa'] / t['bf16']:5.2f}x) | max diff vs fp32 sdpa: bf16 math "
+          f"{(want - out.float()).abs().max().item():.2e}, fp32 math {(want - old.float()).abs().max().item():.2e}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -241,8 +280,14 @@ def main():
     ap.add_argument("--causal", action="store_true", help="the causal kernel on GPT-2 shapes (module docstring)")
     ap.add_argument("--padding", action="store_true", help="the padding-mask kernel on DistilBERT shapes")
     ap.add_argument("--wide", action="store_true", help="the head-split kernel on wide heads (module docstring)")
+    ap.add_argument("--math", choices=["fp32", "bf16"], default="fp32",
+                    help="bf16: the bf16-MFMA kernel against the fp32-math kernel on bf16 rows (module docstring)")
     a = ap.parse_args()
     print(torch.cuda.get_device_name(0))
+    if a.math == "bf16":
+        for name, B, T, h, hkv, d, causal in MATH_SHAPES:
+            bench_math(name, B, T, h, hkv, d, causal, a.reps, a.rounds)
+        return
     if a.wide:
         for name, B, T, h, hkv, d, causal in WIDE_SHAPES:
             bench_wide(name, B, T, h, hkv, d, causal, a.reps, a.rounds)

@@ -239,8 +239,33 @@ def cmd_summary(argv):
     _model(_cfg(a)).summary()
 
 
+def cmd_generate(argv):
+    """Greedy incremental decoding (Model.generate) on random prompt ids in range; prints tokens/s."""
+    ap = argparse.ArgumentParser(prog="generate")
+    ap.add_argument("--model", default="llama_micro")
+    ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--prompt-tokens", type=int, default=16)
+    ap.add_argument("--new-tokens", type=int, default=16)
+    ap.add_argument("--precision", default="fp32", choices=["bf16", "fp32"])
+    ap.add_argument("--device", default=None)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args(argv)
+    from .models.model import application
+    m = application(a.model, seed=a.seed)
+    vocab = int(m.graph.layers[m.graph.output_names[0]].attrs["units"])
+    ids = np.random.default_rng(a.seed).integers(0, vocab, (a.batch, a.prompt_tokens))
+    m.generate(ids, a.new_tokens, device=a.device, precision=a.precision)          # build / capture
+    start = time.time()
+    toks = m.generate(ids, a.new_tokens, device=a.device, precision=a.precision)
+    run = time.time() - start
+    print(toks[0].tolist())
+    print(f"{a.batch} x {a.new_tokens} tokens after a prompt of {a.prompt_tokens} in {run:.4f} seconds")
+    print(f"Throughput: {a.batch * a.new_tokens / run:.1f} tokens/s ({run / a.new_tokens * 1e3:.3f} ms per step, "
+          f"prefill included)")
+
+
 COMMANDS = {"membership": cmd_membership, "node": cmd_node, "serve": cmd_serve, "local-infer": cmd_local_infer,
-            "plan": cmd_plan, "summary": cmd_summary}
+            "plan": cmd_plan, "summary": cmd_summary, "generate": cmd_generate}
 
 
 def main(argv=None):

@@ -127,6 +127,62 @@ class Model:
             outs.append(hout[:n].float().numpy().copy())
         return np.concatenate(outs)
 
+    def generate(self, ids, new_tokens: int, max_tokens: Optional[int] = None, device: Optional[str] = None,
+                 precision: str = "fp32", return_logits: bool = False):
+        """Greedy incremental decoding of a decoder-only model with rotary positions (the Llama family): `ids`
+        (B, P) token ids; one prefill pass over the prompt fills the key / value caches, then every further token
+        is one replay of the captured one-token step graph (csrc/kernels/attention_decode.h).  Between replays the
+        argmax is a torch op on the device; ids stay float32, as everywhere here.  Returns (B, new_tokens) int64
+        ids, with `return_logits` also the (B, new_tokens, V) float32 logits they are the argmax of.  `max_tokens`
+        (default P + new_tokens) sizes the caches.  No sampling; the CPU path has no decoding.  The prefill graph
+        (P tokens) and the step graph (one token) are rebuilt by the zoo builder of `self.graph.name`, so the model
+        must be one that `models.zoo.build_model` knows by name; any other (a Keras-JSON model) is refused."""
+        import torch
+        ids = np.asarray(ids)
+        if ids.ndim != 2 or ids.shape[1] < 1:
+            raise ValueError(f"generate: ids {ids.shape} are not (B, P) with P >= 1")
+        B, P = ids.shape
+        n = int(new_tokens)
+        Tmax = P + n if max_tokens is None else int(max_tokens)
+        if n < 1:
+            raise ValueError(f"generate: new_tokens={n} must be at least 1")
+        if P + n > Tmax:
+            raise ValueError(f"generate: prompt {P} + new_tokens {n} exceeds max_tokens={Tmax}")
+        if device is None:
+            device = "cuda"
+        if str(device).startswith("cpu"):
+            raise ValueError("generate: incremental decoding has no native CPU path; use a GPU device")
+        from ..runtime.executor import SliceExecutor
+        from .resnet import STACKS
+        from .zoo import BUILDERS, build_model
+        if self.graph.name not in BUILDERS and self.graph.name not in STACKS:
+            raise ValueError(f"generate: {self.graph.name!r} is not a model of the zoo (models.zoo.build_model); the "
+                             f"prefill and step graphs are rebuilt by name at other token counts")
+        key = ("generate", device, B, P, Tmax, precision)
+        ent = self._executors.get(key)
+        V = int(self.graph.layers[self.graph.output_names[0]].attrs["units"])
+        if ent is None:
+            g = build_model(self.graph.name, input_shape=(P,), classes=V)
+            ex = SliceExecutor(g, self.weights, B, device=device, precision=precision, kv_cache=Tmax)
+            dec = ex.decoder()
+            dec.capture()
+            ent = self._executors[key] = (ex, dec)
+        ex, dec = ent
+        logits = torch.empty((B, n, V), dtype=torch.float32, device=device)
+        toks = torch.empty((B, n), dtype=torch.int64, device=device)
+        ex.input_buf(ex.g.input).copy_(torch.from_numpy(np.ascontiguousarray(ids, np.float32)))
+        y = ex.forward(0)[ex.outputs[0]]
+        step_in = dec.input_buf(dec.g.input)
+        for i in range(n):
+            if i:
+                step_in.copy_(toks[:, i - 1:i])       # int64 -> float32 on the device
+                y = dec.forward(0)[dec.outputs[0]]
+            logits[:, i] = y.reshape(B, -1)[:, :V]         # a padded row's true channels
+            toks[:, i] = logits[:, i].argmax(-1)
+        torch.cuda.synchronize(device)
+        out = toks.cpu().numpy()
+        return (out, logits.cpu().numpy()) if return_logits else out
+
     def __call__(self, x, **kw):
         return self.predict(x, **kw)
 

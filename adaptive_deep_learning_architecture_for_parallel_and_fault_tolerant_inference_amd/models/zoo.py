@@ -857,8 +857,8 @@ def build_llama(name: str = "tinyllama_1_1b", classes: Optional[int] = None, inp
     token map; the last token cropped out (`all_positions=True` keeps every token), the final RMSNormalization
     and `lm_head`, a Dense without bias onto the vocabulary: the next-token logits.  There is no position table:
     the attention layers rotate Q and K (`rope`, the max wavelength).  `classes` is the vocabulary.  With
-    kv_heads == heads (llama2_7b) the layer is plain multi-head attention behind the rope step.  No KV cache and
-    no incremental decoding; frequency scaling (Llama 3) is not built."""
+    kv_heads == heads (llama2_7b) the layer is plain multi-head attention behind the rope step.  Incremental
+    decoding runs this builder at `input_shape=(1,)` (`SliceExecutor.decoder`); frequency scaling (Llama 3) is not built."""
     depth, width, heads, kv_heads, ffn, vocab, default_tokens, eps, wavelength = LLAMA[name]
     vocab = int(classes or vocab)
     shape = tuple(input_shape or (default_tokens,))

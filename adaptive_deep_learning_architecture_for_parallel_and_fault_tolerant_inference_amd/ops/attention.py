@@ -425,3 +425,159 @@ def posembed(x: torch.Tensor, cls: Optional[torch.Tensor], pos: torch.Tensor, ou
         kernels().posembed_bf16(ptr(x), ptr(cls) if ct else 0, ptr(pos), ptr(out), B, T, Cp, C, ct,
                                 stream_handle(stream))
     return out
+
+
+# ---------------------------------------------------------------- incremental decoding
+# csrc/kernels/attention_decode.h: the key / value cache, its append kernel, the decode attention kernel
+
+def kv_cache(batch: int, kv_heads: int, max_tokens: int, key_dim: int, value_dim: Optional[int] = None,
+             dtype=torch.float32, device="cuda"):
+    """(K, V) caches of one attention layer, zero-filled: K [batch][kv_heads][max_tokens][key_dim] and V
+    [...][value_dim] in the activation dtype.  The key stream of one (sequence, kv head) is contiguous."""
+    B, hkv, Tmax, d = int(batch), int(kv_heads), int(max_tokens), int(key_dim)
+    dv = int(value_dim or key_dim)
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"kv_cache: fp32 or bf16, got {dtype}")
+    if min(B, hkv, Tmax, d, dv) < 1:
+        raise ValueError(f"kv_cache: batch, heads, tokens and head sizes must be positive ({B}, {hkv}, {Tmax}, {d}, {dv})")
+    if B * hkv * Tmax * max(d, dv) >= 2 ** 31:
+        raise ValueError("kv_cache: a cache must hold fewer than 2^31 elements (32-bit index math)")
+    return (torch.zeros((B, hkv, Tmax, d), dtype=dtype, device=device),
+            torch.zeros((B, hkv, Tmax, dv), dtype=dtype, device=device))
+
+
+def _decode_geometry(fn: str, kcache, vcache, pos, heads, key_dim, value_dim, kv_heads):
+    """(B, Tmax, hq, hkv, d, dv) of a cache pair and its `pos`, checked."""
+    h, d = int(heads), int(key_dim)
+    dv = int(value_dim or key_dim)
+    hkv = h if kv_heads is None else int(kv_heads)
+    if hkv < 1 or h < 1 or h % hkv:
+        raise ValueError(f"{fn}: kv_heads={kv_heads} must be positive and divide the {h} heads")
+    if kcache.dtype not in (torch.float32, torch.bfloat16) or vcache.dtype != kcache.dtype:
+        raise ValueError(f"{fn}: fp32 or bf16 caches of one dtype, got {kcache.dtype} and {vcache.dtype}")
+    if (kcache.dim() != 4 or vcache.dim() != 4 or tuple(kcache.shape[:3]) != tuple(vcache.shape[:3])
+            or kcache.shape[1] != hkv or kcache.shape[3] != d or vcache.shape[3] != dv or kcache.numel() == 0):
+        raise ValueError(f"{fn}: caches {tuple(kcache.shape)} {tuple(vcache.shape)} are not [B][{hkv}][Tmax][{d}] and "
+                         f"[B][{hkv}][Tmax][{dv}]")
+    B, Tmax = int(kcache.shape[0]), int(kcache.shape[2])
+    if pos.dtype != torch.int32 or pos.numel() != B:
+        raise ValueError(f"{fn}: pos must be int32 [{B}], got {pos.dtype} {tuple(pos.shape)}")
+    if max(kcache.numel(), vcache.numel()) >= 2 ** 31:
+        raise ValueError(f"{fn}: a cache must hold fewer than 2^31 elements (32-bit index math)")
+    return B, Tmax, h, hkv, d, dv
+
+
+def kv_append(x: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, pos: torch.Tensor, tokens: int, heads: int,
+              key_dim: int, value_dim: Optional[int] = None, kv_heads: Optional[int] = None,
+              table: Optional[torch.Tensor] = None, q_out: Optional[torch.Tensor] = None, stream=None) -> None:
+    """Append `tokens` new tokens per sequence to the caches: x [..., ld] holds B * tokens projection rows
+    [Q: heads x key_dim | K: kv_heads x key_dim | V: kv_heads x value_dim], token j of sequence b goes to position
+    pos[b] + j (pos: int32 [B] on the device, not advanced here).  With `table` (`rope_table`, fp32
+    [2][Ttab][key_dim / 2]) Q and K are rotated at that position, and the rotated Q heads are written to `q_out`
+    [B * tokens][ld_q] with zeros in the rest of each row; without one K and V are copied as they stand (the rows
+    are already rotated) and `q_out` must be None.  A position outside the cache or the table writes nothing: the
+    caller keeps pos[b] + tokens <= max_tokens."""
+    B, Tmax, h, hkv, d, dv = _decode_geometry("kv_append", kcache, vcache, pos, heads, key_dim, value_dim, kv_heads)
+    Tn = int(tokens)
+    if x.dtype != kcache.dtype:
+        raise ValueError(f"kv_append: x is {x.dtype}, the caches are {kcache.dtype}")
+    if Tn < 1:
+        raise ValueError(f"kv_append: tokens={Tn} must be positive")
+    ld = int(x.shape[-1])
+    if x.numel() != B * Tn * ld or ld < (h + hkv) * d + hkv * dv:
+        raise ValueError(f"kv_append: x{tuple(x.shape)} does not hold {B} x {Tn} rows of {h} + {hkv} heads of {d} and "
+                         f"{hkv} of {dv}")
+    if (table is None) != (q_out is None):
+        raise ValueError("kv_append: `table` and `q_out` go together (the rotated Q needs a row to go to)")
+    Ttab, ld_q = 0, 0
+    if table is not None:
+        if d % 2 or table.dim() != 3 or table.shape[0] != 2 or table.shape[2] != d // 2:
+            raise ValueError(f"kv_append: table{tuple(table.shape)} is not [2][Ttab][{d} / 2] of an even key_dim")
+        Ttab, ld_q = int(table.shape[1]), int(q_out.shape[-1])
+        if q_out.dtype != x.dtype or q_out.numel() != B * Tn * ld_q or ld_q < h * d:
+            raise ValueError(f"kv_append: q_out{tuple(q_out.shape)} {q_out.dtype} does not hold {B} x {Tn} rows of "
+                             f"{h} x {d} {x.dtype} channels")
+        _chk(table, torch.float32, "table"); _chk(q_out, x.dtype, "q_out")
+    if max(x.numel(), B * Tn * ld_q, Ttab * d) >= 2 ** 31:
+        raise ValueError("kv_append: tensors must hold fewer than 2^31 elements (32-bit index math)")
+    _chk(x, x.dtype, "x"); _chk(kcache, x.dtype, "kcache"); _chk(vcache, x.dtype, "vcache"); _chk(pos, torch.int32, "pos")
+    fn = kernels().kv_append_f32 if x.dtype == torch.float32 else kernels().kv_append_bf16
+    fn(ptr(x), ptr(table), ptr(pos), ptr(kcache), ptr(vcache), ptr(q_out), B, Tn, Tmax, Ttab, h, hkv, d, dv, ld, ld_q,
+       stream_handle(stream))
+
+
+def attention_decode_plan(batch: int, kv_heads: int, max_tokens: int, heads: Optional[int] = None, value_dim: int = 128,
+                          device=None):
+    """(splits S, keys per split KS, workspace floats) of a decode launch: the grid is (S, kv_heads, batch), about
+    two blocks per compute unit where max_tokens allows, KS a multiple of 64.  S and KS depend on the three
+    leading numbers and the device alone, never on the current lengths.  The workspace is fp32
+    [batch][kv_heads][S][heads / kv_heads][value_dim + 2], 0 floats when S == 1; without `heads` it is sized for
+    the largest group and head the kernel serves (16 query heads per key / value head, 128 channels).  `device`: the
+    device whose compute units are counted (default: the current one; without a GPU an MI355X's 256)."""
+    B, hkv, Tmax = int(batch), int(kv_heads), int(max_tokens)
+    h = 16 * hkv if heads is None else int(heads)
+    if min(B, hkv, Tmax, h, int(value_dim)) < 1:
+        raise ValueError(f"attention_decode_plan: batch, heads, max_tokens and value_dim must be positive "
+                         f"({B}, {hkv}, {Tmax}, {h}, {value_dim})")
+    if device is not None and torch.device(device).type == "cuda":
+        with torch.cuda.device(device):
+            S, KS = (int(v) for v in kernels().attention_decode_plan(B, hkv, Tmax))
+    else:
+        S, KS = (int(v) for v in kernels().attention_decode_plan(B, hkv, Tmax))
+    return S, KS, (B * S * h * (int(value_dim) + 2) if S > 1 else 0)
+
+
+def attention_decode(q: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, pos: torch.Tensor, out: torch.Tensor,
+                     heads: int, key_dim: int, value_dim: Optional[int] = None, kv_heads: Optional[int] = None,
+                     workspace: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """One decode step of causal attention (csrc/kernels/attention_decode.h): q [B][ld_q] holds one query row per
+    sequence (heads x key_dim channels, already rotated and scaled by 1/sqrt(key_dim)), sequence b attends the
+    cached keys 0 .. pos[b] inclusive (pos: int32 [B] on the device; the step's own key is appended before the
+    call), head h on key / value head h // (heads // kv_heads).  out [B][ld_out] gets heads * value_dim channels
+    and zeros in the rest of the row.  `workspace`: fp32, at least `attention_decode_plan(...)`'s third value in elements
+    (allocated here when None and the plan has more than one split).  Served: head sizes that are multiples of 16
+    up to 128, at most 16 query heads per key / value head, q and the caches aligned to 16 bytes and ld_q a
+    multiple of 4 (fp32) / 8 (bf16) elements; anything else is a ValueError, never a fall-back."""
+    B, Tmax, h, hkv, d, dv = _decode_geometry("attention_decode", kcache, vcache, pos, heads, key_dim, value_dim,
+                                              kv_heads)
+    if d % 16 or dv % 16 or max(d, dv) > 128:
+        raise ValueError(f"attention_decode: head sizes ({d}, {dv}) must be multiples of 16 up to 128")
+    if h // hkv > 16:
+        raise ValueError(f"attention_decode: {h // hkv} query heads per key / value head, at most 16 are served")
+    if q.dtype != kcache.dtype or out.dtype != kcache.dtype:
+        raise ValueError(f"attention_decode: q is {q.dtype} and out {out.dtype}, the caches are {kcache.dtype}")
+    vec = 4 if q.dtype == torch.float32 else 8
+    ld_q, ld_out = int(q.shape[-1]), int(out.shape[-1])
+    if q.numel() != B * ld_q or out.numel() != B * ld_out or ld_q < h * d or ld_out < h * dv:
+        raise ValueError(f"attention_decode: q{tuple(q.shape)} out{tuple(out.shape)} do not hold {B} rows of {h} heads "
+                         f"({d}, {dv})")
+    if ld_q % vec or any(t.data_ptr() % 16 for t in (q, kcache, vcache)):
+        raise ValueError(f"attention_decode: ld_q={ld_q} must be a multiple of {vec} elements and q and the caches "
+                         f"aligned to 16 bytes")
+    if B > 65535 or hkv > 65535:
+        raise ValueError(f"attention_decode: batch {B} and kv_heads {hkv} are grid dimensions, at most 65535")
+    _chk(q, q.dtype, "q"); _chk(out, q.dtype, "out"); _chk(kcache, q.dtype, "kcache"); _chk(vcache, q.dtype, "vcache")
+    _chk(pos, torch.int32, "pos")
+    if any(t.device != q.device for t in (kcache, vcache, pos, out)):
+        raise ValueError("attention_decode: q, the caches, pos and out must be on one device")
+    need = attention_decode_plan(B, hkv, Tmax, h, dv, device=q.device)[2]
+    if need:
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.float32, device=q.device)
+        _chk(workspace, torch.float32, "workspace")
+        if workspace.numel() < need:
+            raise ValueError(f"attention_decode: workspace of {workspace.numel()} floats, {need} needed")
+    fn = kernels().attention_decode_f32 if q.dtype == torch.float32 else kernels().attention_decode_bf16
+    with torch.cuda.device(q.device):                 # the launch plans its splits for the current device: the tensors'
+        fn(ptr(q), ptr(kcache), ptr(vcache), ptr(pos), ptr(out), ptr(workspace) if need else 0, B, Tmax, h, hkv, d, dv,
+           ld_q, ld_out, stream_handle(stream))
+    return out
+
+
+def advance_positions(pos: torch.Tensor, n: int = 1, stream=None) -> torch.Tensor:
+    """pos[b] += n on the device: the last launch of a decode step, so a replayed graph advances by itself."""
+    _chk(pos, torch.int32, "pos")
+    if pos.numel() < 1:
+        raise ValueError("advance_positions: empty pos")
+    kernels().advance_positions(ptr(pos), int(pos.numel()), int(n), stream_handle(stream))
+    return pos

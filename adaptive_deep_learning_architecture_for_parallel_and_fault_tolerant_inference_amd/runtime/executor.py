@@ -33,7 +33,7 @@ from ..graph.ir import Graph, bn_params, conv_bias, conv_kernel, depthwise_kerne
 from ..ops import attention as attn_ops
 from ..ops import conv as conv_ops
 from ..ops import eltwise as E
-from ..ops._lib import private_stream
+from ..ops._lib import kernels, private_stream
 from .plan import Step, compact_maps, compile_plan, tensor_shape
 
 TUNING_FILE = Path(__file__).resolve().parent.parent / "tuning" / "gfx950_conv.json"
@@ -92,7 +92,8 @@ class SliceExecutor:
 
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], batch: int, device="cuda",
                  outputs: Optional[Sequence[str]] = None, tune: bool = False, num_sets: int = 1,
-                 precision: str = "fp32", private_sets: bool = False, attention_math: Optional[str] = None):
+                 precision: str = "fp32", private_sets: bool = False, attention_math: Optional[str] = None,
+                 kv_cache: Optional[int] = None, _decode_of: Optional["SliceExecutor"] = None):
         """precision: "bf16" (bf16 activations / weights, fp32 accumulation: the
         fast path) or "fp32" (fp32 activations and weights on the fp32 matrix
         cores: the reference's Keras float32 numerics, csrc/kernels/conv_f32.hip).
@@ -106,7 +107,14 @@ class SliceExecutor:
         the bf16-MFMA kernel of csrc/kernels/attention_bf16.h where it serves); None
         reads ADAPT_ATTENTION_MATH, default fp32.  It reaches the launch of the
         `attention` steps with one [Q | K | V] source only: the plan is the same, and
-        cross-attention and window attention ignore it."""
+        cross-attention and window attention ignore it.
+        kv_cache: None (the default: nothing changes), or the most tokens a sequence
+        may reach: every causal self-attention step then gets a key / value cache
+        of that length outside the arena, filled by a `kv_append` launch right
+        before its attention launch, and `pos` (int32 [batch] on the device) holds
+        the prompt length after a run.  Every output is what it is without the
+        cache; `decoder()` returns the one-token step executor that goes on from
+        there (csrc/kernels/attention_decode.h)."""
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"precision must be bf16 or fp32, got {precision!r}")
         if attention_math is None:
@@ -137,7 +145,19 @@ class SliceExecutor:
             if bad:
                 raise NotImplementedError(f"fp32 execution has no kernels for {bad} (model {g.name})")
         self._graphs: List[Optional[torch.cuda.CUDAGraph]] = [None] * num_sets
-        self._pack_weights(weights)
+        self.kv_cache = None if kv_cache is None else int(kv_cache)
+        self._decode_of = _decode_of
+        self._kv: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None     # layer -> (K, V) caches
+        if self.kv_cache is not None:
+            self._plan_kv(weights)
+        if _decode_of is not None and [(st.kind, st.out) for st in self.steps] == [(st.kind, st.out)
+                                                                                   for st in _decode_of.steps]:
+            # the same steps at one token: the prefill executor's prepared weights serve, only the rotary tables
+            # (one row per position up to the cache length) are the decoder's own
+            self.packed = {i: self._decode_table(st) if st.kind == "rope" else v for i, v in _decode_of.packed.items()
+                           for st in (self.steps[i],)}
+        else:
+            self._pack_weights(weights)
         self._alloc()
         self._select_configs(tune)
 
@@ -401,12 +421,21 @@ class SliceExecutor:
             q, k, v = (b[st.ins[p[c][0]]][..., p[c][1]:p[c][1] + h * w] for c, w in (("q", d), ("k", d), ("v", dv)))
             attn_ops.cross_attention(q, k, v, b[st.out], self.batch, p["tokens_q"], p["tokens_k"], h, d, dv,
                                      stream=stream)
+        elif st.kind == "attention" and self._decode_of is not None:
+            self._launch_decode(st, b, stream)
         elif st.kind == "attention":
             p = st.p
+            if self._kv is not None and p["layer"] in self._kv:
+                # prefill: the rows the core is about to read (rotated already) go into the caches from position 0
+                kc, vc = self._kv[p["layer"]]
+                attn_ops.kv_append(b[st.ins[0]], kc, vc, self._pos0, p["tokens"], p["heads"], p["key_dim"],
+                                   p["value_dim"], kv_heads=p.get("kv_heads"), stream=stream)
             attn_ops.attention(b[st.ins[0]], b[st.out], self.batch, p["tokens"], p["heads"], p["key_dim"],
                                p["value_dim"], stream=stream, causal=bool(p.get("causal")),
                                key_mask=b[st.ins[1]] if p.get("key_mask") else None, kv_heads=p.get("kv_heads"),
                                math=self.attention_math)
+        elif st.kind == "rope" and self._decode_of is not None:
+            pass                                      # the attention step behind it rotates at the device-held position
         elif st.kind == "rope":
             p = st.p
             attn_ops.rope(b[st.ins[0]], self.packed[i], b[st.out], p["tokens"], p["heads"], p["key_dim"],
@@ -426,6 +455,123 @@ class SliceExecutor:
             cls, pos = self.packed[i]
             attn_ops.posembed(b[st.ins[0]], cls, pos, b[st.out], C=self.g.layers[st.p["layer"]].out_shape[-1],
                               stream=stream)
+
+    # ------------------------------------------------- incremental decoding
+    def _plan_kv(self, weights: Dict[str, np.ndarray]) -> None:
+        """Which steps get a cache, and what a decoder refuses (by layer name, before anything is allocated)."""
+        Tmax, dec = self.kv_cache, self._decode_of is not None
+        self._weights = weights                       # the decoder prepares from them what it cannot share
+        self._kv_layers: List[str] = []
+        self._rope_in: Dict[str, str] = {}            # layer -> the input of its rope step
+        for i, st in enumerate(self.steps):
+            p = st.p
+            if st.kind == "rope":
+                self._rope_in[p["layer"]] = st.ins[0]
+                nxt = self.steps[i + 1] if i + 1 < len(self.steps) else None
+                if dec and (nxt is None or nxt.kind != "attention" or nxt.ins[0] != st.out):
+                    raise ValueError(f"decoder: layer {p['layer']!r}: the attention step must follow its rope step "
+                                     f"directly (it reads that step's input)")
+            if dec and st.kind in ("posembed", "winattn"):
+                raise ValueError(f"decoder: layer {p['layer']!r} ({st.kind}) is not built for incremental decoding"
+                                 + (": a learned position table needs a device-held offset" if st.kind == "posembed"
+                                    else ""))
+            if st.kind != "attention":
+                continue
+            plain = "tokens_q" not in p and not p.get("key_mask") and bool(p.get("causal"))
+            if dec and not plain:
+                raise ValueError(f"decoder: layer {p['layer']!r} is not causal self-attention on one source without a "
+                                 f"padding mask")
+            if not plain:
+                continue
+            g = p["heads"] // int(p.get("kv_heads") or p["heads"])
+            if dec and not kernels().attention_decode_path(p["key_dim"], p["value_dim"], g):
+                raise ValueError(f"decoder: layer {p['layer']!r}: the decode kernel does not serve heads of "
+                                 f"({p['key_dim']}, {p['value_dim']}) in groups of {g}")
+            if p["tokens"] > Tmax:
+                raise ValueError(f"kv_cache={Tmax} is below the {p['tokens']} tokens of layer {p['layer']!r}")
+            self._kv_layers.append(p["layer"])
+
+    def _alloc_kv(self) -> None:
+        dev, B = self.device, self.batch
+        if self._decode_of is not None:               # the prefill executor's caches and positions
+            par = self._decode_of
+            self._kv, self._pos = par._kv, par._pos
+            need = 0
+            for st in self.steps:
+                if st.kind == "attention":
+                    p = st.p
+                    need = max(need, attn_ops.attention_decode_plan(B, int(p.get("kv_heads") or p["heads"]),
+                                                                    self.kv_cache, p["heads"], p["value_dim"],
+                                                                    device=dev)[2])
+            self._dec_ws = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+            return
+        tokens = 0
+        self._kv = {}
+        for st in self.steps:
+            if st.kind == "attention" and st.p["layer"] in self._kv_layers:
+                p = st.p
+                tokens = p["tokens"]
+                self._kv[p["layer"]] = attn_ops.kv_cache(B, int(p.get("kv_heads") or p["heads"]), self.kv_cache,
+                                                         p["key_dim"], p["value_dim"], self.dtype_of(st.out), dev)
+        self._pos = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._pos0 = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._pos_prompt = torch.full((B,), tokens, dtype=torch.int32, device=dev)
+
+    @property
+    def positions(self) -> torch.Tensor:
+        """int32 [batch] on the device: the tokens each sequence holds in the caches."""
+        return self._pos
+
+    def _decode_table(self, st: Step) -> torch.Tensor:
+        """The rotary table of a decoder's rope step: one row per cache position, kept on the prefill executor."""
+        key = (self.kv_cache, int(st.p["key_dim"]), float(st.p["rope"]))
+        tabs = self._decode_of._rope_tables
+        if key not in tabs:
+            tabs[key] = attn_ops.rope_table(*key, device=self.device)
+        return tabs[key]
+
+    def _launch_decode(self, st: Step, b, stream) -> None:
+        """One token per sequence: append its K and V at pos[b] (rotating Q and K there under `rope`), then the
+        decode kernel over the keys 0 .. pos[b]."""
+        p = st.p
+        kc, vc = self._kv[p["layer"]]
+        h, d, dv, hkv = p["heads"], p["key_dim"], p["value_dim"], p.get("kv_heads")
+        q = b[st.ins[0]]
+        if "rope" in p:
+            # st.ins[0] is the rope step's output, which that step left unwritten: the rotated Q goes there.  The rope
+            # step's input is read here, one step after its last reader in the arena's accounting.  Its block is
+            # intact: the rope step's output was allocated while it was live, so the two differ; no step lies
+            # between the rope step and this one; and this step's own output, which may take the freed block, is
+            # written by `attention_decode` only, behind `kv_append` on the same stream
+            table = self._decode_table(st)
+            attn_ops.kv_append(b[self._rope_in[p["layer"]]], kc, vc, self._pos, 1, h, d, dv, kv_heads=hkv, table=table,
+                               q_out=q, stream=stream)
+        else:
+            attn_ops.kv_append(q, kc, vc, self._pos, 1, h, d, dv, kv_heads=hkv, stream=stream)
+        attn_ops.attention_decode(q.view(self.batch, -1), kc, vc, self._pos, b[st.out].view(self.batch, -1), h, d, dv,
+                                  kv_heads=hkv, workspace=self._dec_ws, stream=stream)
+
+    def decoder(self) -> "SliceExecutor":
+        """The step executor behind this prefill executor (`kv_cache` set): the same model at one token per
+        sequence, on this executor's prepared weights, caches and positions.  A run appends the token's keys and
+        values at pos[b], attends keys 0 .. pos[b] and ends by advancing pos, so its captured graph replays token
+        after token.  Refused by layer name: learned position tables, padding masks, separate sources, window
+        attention, non-causal attention, heads the decode kernel does not serve; and a cut graph."""
+        from ..models.zoo import build_model
+        if self._kv is None or self._decode_of is not None:
+            raise ValueError("decoder: needs a prefill executor, SliceExecutor(..., kv_cache=max_tokens)")
+        g = self.g
+        if self.outputs != list(g.output_names) or len(g.input_names) != 1 or len(g.layers[g.input].out_shape) != 1:
+            raise ValueError(f"decoder: {g.name} is cut (inputs {g.input_names}, outputs {self.outputs}); decoding "
+                             f"runs the whole model on one executor")
+        kw = {"input_shape": (1,)}
+        if f"{g.name}_last" not in g.layers:          # the builders' all_positions: no crop of the last token
+            kw["all_positions"] = True
+        head = g.layers[g.output_names[0]]
+        if head.op == "dense":
+            kw["classes"] = int(head.attrs["units"])
+        return SliceExecutor(build_model(g.name, **kw), self._weights, self.batch, device=self.device,
+                             precision=self.precision, kv_cache=self.kv_cache, _decode_of=self)
 
     def _pack_rmsnorm(self, weights: Dict[str, np.ndarray], st: Step, cp: int):
         """scale fp32 [cp] of an rmsnorm step, with Keras' default for scale=False; the bf16 layout's padding
@@ -474,6 +620,8 @@ class SliceExecutor:
                 key = o + "#out" if o in in_names else o
                 s[key] = torch.empty(self.shape_of(o), dtype=self.dtype_of(o), device=dev)
             self.sets.append(s)
+        if self.kv_cache is not None:
+            self._alloc_kv()
         self._alloc_private()
         self._priv: List[Dict[str, object]] = []
         self._bound = 0
@@ -986,6 +1134,11 @@ class SliceExecutor:
         for a in done:                                # every branch joined (normally at its consumer)
             if a not in side or side[a] >= len(self.steps):
                 main.wait_event(done[a])
+        if self._decode_of is not None:               # the plan's last launch: a replayed graph advances by itself
+            attn_ops.advance_positions(self._pos, 1, stream=stream)
+        elif self._kv is not None:                    # prefill: the sequences now hold the prompt
+            with torch.cuda.stream(main):
+                self._pos.copy_(self._pos_prompt, non_blocking=True)
         if debug and self.steps:
             self._debug_check(len(self.steps) - 1)
         # relay frontier tensors: device copy into the output set (no aliasing with the

@@ -509,6 +509,37 @@ PYBIND11_MODULE(_C, m) {
   m.def("attention_bf16_path", &adapt::attention_bf16_path);
   m.def("attention_bf16_query_tile", &adapt::attention_bf16_query_tile);
   m.def("attention_bf16_key_tile", &adapt::attention_bf16_key_tile);
+  m.def("kv_append_f32", [](u64 x, u64 table, u64 pos, u64 kc, u64 vc, u64 q_out, int B, int Tn, int Tmax, int Ttab,
+                            int hq, int hkv, int d, int dv, int ld, int ld_q, u64 s) {
+    check(adapt::kv_append_f32(P<const float>(x), P<const float>(table), P<const int>(pos), P<float>(kc), P<float>(vc),
+                               P<float>(q_out), B, Tn, Tmax, Ttab, hq, hkv, d, dv, ld, ld_q, S(s)), "kv_append_f32");
+  });
+  m.def("kv_append_bf16", [](u64 x, u64 table, u64 pos, u64 kc, u64 vc, u64 q_out, int B, int Tn, int Tmax, int Ttab,
+                             int hq, int hkv, int d, int dv, int ld, int ld_q, u64 s) {
+    check(adapt::kv_append_bf16(P<const bf16>(x), P<const float>(table), P<const int>(pos), P<bf16>(kc), P<bf16>(vc),
+                                P<bf16>(q_out), B, Tn, Tmax, Ttab, hq, hkv, d, dv, ld, ld_q, S(s)), "kv_append_bf16");
+  });
+  m.def("attention_decode_f32", [](u64 q, u64 kc, u64 vc, u64 pos, u64 out, u64 ws, int B, int Tmax, int hq, int hkv,
+                                   int d, int dv, int ld_q, int ld_out, u64 s) {
+    check(adapt::attention_decode_f32(P<const float>(q), P<const float>(kc), P<const float>(vc), P<const int>(pos),
+                                      P<float>(out), P<float>(ws), B, Tmax, hq, hkv, d, dv, ld_q, ld_out, S(s)),
+          "attention_decode_f32");
+  });
+  m.def("attention_decode_bf16", [](u64 q, u64 kc, u64 vc, u64 pos, u64 out, u64 ws, int B, int Tmax, int hq, int hkv,
+                                    int d, int dv, int ld_q, int ld_out, u64 s) {
+    check(adapt::attention_decode_bf16(P<const bf16>(q), P<const bf16>(kc), P<const bf16>(vc), P<const int>(pos),
+                                       P<bf16>(out), P<float>(ws), B, Tmax, hq, hkv, d, dv, ld_q, ld_out, S(s)),
+          "attention_decode_bf16");
+  });
+  m.def("attention_decode_path", &adapt::attention_decode_path);
+  m.def("attention_decode_plan", [](int B, int hkv, int Tmax) {
+    int S_ = 0, KS = 0;
+    adapt::attention_decode_plan(B, hkv, Tmax, &S_, &KS);
+    return py::make_tuple(S_, KS);
+  });
+  m.def("advance_positions", [](u64 pos, int B, int n, u64 s) {
+    check(adapt::advance_positions(P<int>(pos), B, n, S(s)), "advance_positions");
+  });
   m.def("attention_qkv_f32", [](u64 q, u64 k, u64 v, u64 out, int B, int Tq, int Tk, int heads, int d, int dv, int ldq,
                                 int ldk, int ldv, int ld_out, u64 s) {
     check(adapt::attention_qkv_f32(P<const float>(q), P<const float>(k), P<const float>(v), P<float>(out), B, Tq, Tk,

@@ -457,6 +457,27 @@ hipError_t attention_mm_bf16(const bf16* qkv, bf16* out, int B, int T, int heads
 int attention_bf16_path(int d, int dv);   // 1: the bf16-MFMA kernel serves this head, 0: it does not
 int attention_bf16_query_tile();          // queries per block of the bf16-MFMA kernel
 int attention_bf16_key_tile();            // keys per LDS tile of the bf16-MFMA kernel
+// Incremental decoding (attention_decode.hip, scheme in attention_decode.h).  The caches are K [B][hkv][Tmax][d] and
+// V [B][hkv][Tmax][dv] in the activation type, pos int32 [B] on the device (tokens held per sequence).
+// kv_append: B * Tn rows [Q: hq d | K: hkv d | V: hkv dv] at stride ld, token j of sequence b at position pos[b] + j.
+// With `table` (fp32 [2][Ttab][d/2]) Q and K are rotated there, Q goes to q_out [B * Tn][ld_q] (the rest of the row
+// zeros); with table == nullptr K and V are copied and q_out is not touched.  A position outside the cache or the
+// table writes nothing.
+hipError_t kv_append_f32(const float* x, const float* table, const int* pos, float* kc, float* vc, float* q_out, int B,
+                         int Tn, int Tmax, int Ttab, int hq, int hkv, int d, int dv, int ld, int ld_q, hipStream_t s);
+hipError_t kv_append_bf16(const bf16* x, const float* table, const int* pos, bf16* kc, bf16* vc, bf16* q_out, int B,
+                          int Tn, int Tmax, int Ttab, int hq, int hkv, int d, int dv, int ld, int ld_q, hipStream_t s);
+// attention_decode: q [B][ld_q] (hq d channels, pre-scaled), sequence b attends keys 0 .. pos[b]; out [B][ld_out] gets
+// hq dv channels and zeros in the rest of the row.  ws: fp32 [B][hkv][S][hq / hkv][dv + 2], needed when the plan has
+// S > 1 splits.  d and dv multiples of 16 up to 128, hq / hkv <= 16, q and the caches aligned to 16 bytes, ld_q a
+// multiple of 4 (fp32) / 8 (bf16) elements: anything else is hipErrorInvalidValue
+hipError_t attention_decode_f32(const float* q, const float* kc, const float* vc, const int* pos, float* out, float* ws,
+                                int B, int Tmax, int hq, int hkv, int d, int dv, int ld_q, int ld_out, hipStream_t s);
+hipError_t attention_decode_bf16(const bf16* q, const bf16* kc, const bf16* vc, const int* pos, bf16* out, float* ws,
+                                 int B, int Tmax, int hq, int hkv, int d, int dv, int ld_q, int ld_out, hipStream_t s);
+int attention_decode_path(int d, int dv, int g);                       // 1: the decode kernel serves this head and group
+void attention_decode_plan(int B, int hkv, int Tmax, int* S, int* KS); // splits and keys per split, from the CU count
+hipError_t advance_positions(int* pos, int B, int n, hipStream_t s);   // pos[b] += n
 // Attention core with separate sources (cross_attention.hip): q [B*Tq][ldq], k [B*Tk][ldk], v [B*Tk][ldv], each
 // pointer already offset to its part's first column (head h at h*d for Q and K, h*dv for V; Q pre-scaled), out
 // [B*Tq][ld_out] with heads*dv true channels (the rest of a row is written as zeros).  The MFMA path takes what

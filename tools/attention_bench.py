@@ -272,6 +272,42 @@ def bench_math(name, B, T, h, hkv, d, causal, reps, rounds):
           f"{(want - out.float()).abs().max().item():.2e}, fp32 math {(want - old.float()).abs().max().item():.2e}", flush=True)
 
 
+# (name, heads, kv heads, key_dim = value_dim) of the decode rows; batches and cached lengths below
+DECODE_HEADS = [("tinyllama", 32, 4, 64), ("llama2_7b", 32, 32, 128)]
+DECODE_BATCHES, DECODE_LENGTHS = (1, 8, 32), (512, 2048, 8192)
+HBM_PEAK = 8.0e12                                                # bytes/s, the MI355X figure
+
+
+def bench_decode(name, B, L, h, hkv, d, dtype, reps, rounds):
+    """One decode step at L cached keys per sequence (cache length L): the decode kernel against (a) the
+    cross-attention kernel at tokens_q = 1 on rows with every K / V head repeated g times, the only path before the
+    decode kernel, and (b) scaled_dot_product_attention(enable_gqa=True).  Bytes: K and V once, L rows each."""
+    g = h // hkv
+    q = (torch.randn(B, h * d, device="cuda") * d ** -0.5).to(dtype)
+    kc, vc = (torch.randn(B, hkv, L, d, device="cuda").to(dtype) for _ in range(2))
+    pos = torch.full((B,), L - 1, dtype=torch.int32, device="cuda")
+    out, old = (torch.empty(B, h * d, device="cuda", dtype=dtype) for _ in range(2))
+    ws = torch.empty(max(A.attention_decode_plan(B, hkv, L, h, d)[2], 1), device="cuda")
+    # (a): [B * L][h d] rows, head-major
+    kx, vx = (t.repeat_interleave(g, dim=1).permute(0, 2, 1, 3).reshape(B * L, h * d).contiguous() for t in (kc, vc))
+    q4, k4, v4 = q.view(B, h, 1, d), kc, vc
+
+    def sdpa():
+        return F.scaled_dot_product_attention(q4, k4, v4, scale=1.0, enable_gqa=True)
+
+    t = interleaved_us({"decode": lambda: A.attention_decode(q, kc, vc, pos, out, h, d, d, kv_heads=hkv, workspace=ws),
+                        "cross": lambda: A.cross_attention(q, kx, vx, old, B, 1, L, h, d, d),
+                        "sdpa": sdpa}, reps, rounds)
+    want = sdpa().reshape(B, h * d).float()
+    nbytes = 2.0 * B * hkv * L * d * q.element_size()
+    S, KS, _ = A.attention_decode_plan(B, hkv, L)
+    print(f"{name:10s} {str(dtype)[6:]:8s} B{B:<2d} L{L:<5d} h{h}/{hkv} d{d} S{S} KS{KS}: decode {t['decode']:8.1f} us "
+          f"({nbytes / t['decode'] / 1e6:6.2f} TB/s K+V, {nbytes / t['decode'] * 1e6 / HBM_PEAK * 100:4.1f} % of HBM peak) | "
+          f"(a) cross_attention tokens_q=1 {t['cross']:8.1f} us ({t['cross'] / t['decode']:5.2f}x) | (b) sdpa gqa "
+          f"{t['sdpa']:8.1f} us ({t['sdpa'] / t['decode']:5.2f}x) | max diff vs sdpa: decode "
+          f"{(want - out.float()).abs().max().item():.2e}, cross {(want - old.float()).abs().max().item():.2e}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -282,8 +318,17 @@ def main():
     ap.add_argument("--wide", action="store_true", help="the head-split kernel on wide heads (module docstring)")
     ap.add_argument("--math", choices=["fp32", "bf16"], default="fp32",
                     help="bf16: the bf16-MFMA kernel against the fp32-math kernel on bf16 rows (module docstring)")
+    ap.add_argument("--decode", action="store_true", help="the decode kernel against cross_attention at one query "
+                                                          "and sdpa (csrc/kernels/attention_decode.h)")
     a = ap.parse_args()
     print(torch.cuda.get_device_name(0))
+    if a.decode:
+        for name, h, hkv, d in DECODE_HEADS:
+            for dtype in (torch.float32, torch.bfloat16):
+                for B in DECODE_BATCHES:
+                    for L in DECODE_LENGTHS:
+                        bench_decode(name, B, L, h, hkv, d, dtype, a.reps, a.rounds)
+        return
     if a.math == "bf16":
         for name, B, T, h, hkv, d, causal in MATH_SHAPES:
             bench_math(name, B, T, h, hkv, d, causal, a.reps, a.rounds)

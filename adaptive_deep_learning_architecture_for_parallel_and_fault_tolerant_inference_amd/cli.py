@@ -249,14 +249,16 @@ def cmd_generate(argv):
     ap.add_argument("--precision", default="fp32", choices=["bf16", "fp32"])
     ap.add_argument("--device", default=None)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--decode-gemm", default=None, choices=["tiles", "skinny"],
+                    help="GEMM path of the one-token step (default: ADAPT_DECODE_GEMM, else tiles)")
     a = ap.parse_args(argv)
     from .models.model import application
     m = application(a.model, seed=a.seed)
     vocab = int(m.graph.layers[m.graph.output_names[0]].attrs["units"])
     ids = np.random.default_rng(a.seed).integers(0, vocab, (a.batch, a.prompt_tokens))
-    m.generate(ids, a.new_tokens, device=a.device, precision=a.precision)          # build / capture
+    m.generate(ids, a.new_tokens, device=a.device, precision=a.precision, decode_gemm=a.decode_gemm)   # build / capture
     start = time.time()
-    toks = m.generate(ids, a.new_tokens, device=a.device, precision=a.precision)
+    toks = m.generate(ids, a.new_tokens, device=a.device, precision=a.precision, decode_gemm=a.decode_gemm)
     run = time.time() - start
     print(toks[0].tolist())
     print(f"{a.batch} x {a.new_tokens} tokens after a prompt of {a.prompt_tokens} in {run:.4f} seconds")

@@ -1088,6 +1088,107 @@ def ps_forward(x: torch.Tensor, pc: "PackedConv", out: torch.Tensor, residual: O
     return out
 
 
+# ------------------------------------------------- skinny GEMM (one-token decode steps)
+# csrc/kernels/gemm_skinny.h: a 1x1 / stride 1 conv at 1 <= M <= 32 rows on its packed weights (pc.w as it is, fp32
+# or bf16), W streamed once: grid (ceil(N / 16 F), KS) blocks of 4 waves, F in SKINNY_F channel fragments per block,
+# KS splits of K in chunks of 256 bytes of a weight row, merged by the last block to arrive.  Entry points of their
+# own, not a ConvFamily: the families' candidate lists, the tuners and the tuning table do not know it.
+SKINNY_F = (1, 2, 4)
+SKINNY_MAX_M = 32
+SKINNY_KC = {torch.float32: 64, torch.bfloat16: 128}        # k per chunk (gemm_skinny.h SkinnyType::KC)
+_SKINNY_VEC = {torch.float32: 4, torch.bfloat16: 8}         # elements per 16-byte vector: K and N are multiples
+_SKINNY_BK = {torch.float32: F32_BK, torch.bfloat16: BK}    # Kpad's unit in pack_conv_f32 / pack_conv
+# skinny_plan's target, blocks per CU, from tools/skinny_bench.py --sweep at M = 8 on the tinyllama_1_1b GEMMs
+# (BASELINE.md "Round 24"): fp32 is fastest near 2 blocks per CU, bf16 (half the bytes per chunk) near 1, and at
+# equal blocks the narrower channel tile wins on every shape, so F grows only where K cannot give the blocks
+SKINNY_BLOCKS_PER_CU = {torch.float32: 2, torch.bfloat16: 1}
+
+
+def skinny_chunks(K: int, dtype) -> int:
+    """Chunks of a packed weight row of K (true) input channels: the most splits a launch takes."""
+    bk = _SKINNY_BK[dtype]
+    return math.ceil(math.ceil(K / bk) * bk / SKINNY_KC[dtype])
+
+
+def skinny_supported(pc: "PackedConv", M: int) -> bool:
+    """1x1, stride 1, no padding, one output, 1 <= M <= 32 rows, K and N multiples of the 16-byte vector."""
+    vec = _SKINNY_VEC.get(pc.w.dtype)
+    return (vec is not None and (pc.kh, pc.kw, pc.stride, pc.pad_t, pc.pad_l, pc.pad_b, pc.pad_r) == (1, 1, 1, 0, 0, 0, 0)
+            and not pc.n_split and 1 <= M <= SKINNY_MAX_M and pc.cin % vec == 0 and pc.cout % vec == 0)
+
+
+def skinny_plan(M: int, N: int, K: int, dtype):
+    """(F, KS): fill the chip first (SKINNY_BLOCKS_PER_CU blocks per CU where K allows: a split is never shorter
+    than one chunk per wave, never empty), then the smaller F: measured, not the larger F the design started
+    from (more blocks of fewer registers hide the latency of a short K range better than wider tiles save on x)."""
+    chunks = skinny_chunks(K, dtype)
+    ks_max = max(1, chunks // 4)
+    want = SKINNY_BLOCKS_PER_CU[dtype] * NUM_CUS
+    best = None
+    for F in SKINNY_F:
+        tiles = math.ceil(N / (16 * F))
+        ks = min(ks_max, max(1, want // tiles))
+        cand = (min(tiles * ks, want // 2), -F, ks)    # at least half the target counts as filled; then the smaller F
+        if best is None or cand > best:
+            best = cand
+    return -best[1], best[2]
+
+
+def skinny_preferred(M: int, N: int, K: int, dtype) -> bool:
+    """Whether a decoder routes a supported step here rather than to its tile config, from the rows of
+    tools/skinny_bench.py where the tile path won (BASELINE.md "Round 24"): not above 16 rows (the second row
+    fragment on the same weight registers: behind on most shapes at M = 32), and not in bf16 at 8 or more rows and
+    N >= 8192 (llama2_7b's qkv and gate / up: the 64-row tile is 3 to 17 % ahead there)."""
+    return M <= 16 and not (dtype == torch.bfloat16 and M >= 8 and N >= 8192)
+
+
+def skinny_scratch(M: int, N: int, K: int, dtype, F: int, KS: int):
+    """(fp32 workspace elements, int32 arrival counters) of a launch, exact."""
+    return (KS * M * N if KS > 1 else 0), (math.ceil(N / (16 * F)) if KS > 1 else 0)
+
+
+def skinny_forward(x: torch.Tensor, pc: "PackedConv", out: torch.Tensor, residual: Optional[torch.Tensor] = None,
+                   relu: int = 0, F: Optional[int] = None, ksplit: Optional[int] = None,
+                   workspace: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None,
+                   stream=None) -> torch.Tensor:
+    """out [M, N] = act(x [M, K] . pc.w^T + bias (+ residual)) for 1 <= M <= 32 rows (x: [M, K] or a [B, H, W, K] map
+    of M pixels), fp32 or bf16 as pc.w is packed.  `F` / `ksplit` default to `skinny_plan`; `skinny_scratch` gives
+    the `workspace` floats (allocated when absent) and the `counters` (int32 zeros; a launch leaves them zero) of
+    a ksplit > 1."""
+    C = x.shape[-1]
+    M = x.numel() // max(C, 1)
+    if C != pc.cin:
+        raise ValueError(f"conv expects {pc.cin} input channels, got {C}")
+    if not skinny_supported(pc, M):
+        raise ValueError(f"skinny GEMM does not take this conv ({pc.kh}x{pc.kw}/s{pc.stride}, {pc.cin} -> {pc.cout} "
+                         f"channels, n_split {pc.n_split}) at {M} rows: 1x1 / stride 1, one output, 1 <= M <= "
+                         f"{SKINNY_MAX_M}")
+    dtype, N, K = pc.w.dtype, pc.cout, pc.cin
+    for t, nm in ((x, "x"), (out, "out"), (residual, "residual")):
+        if t is not None and (t.dtype != dtype or not t.is_contiguous()):
+            raise ValueError(f"skinny GEMM: {nm} must be contiguous {dtype}, as the weights are packed")
+    if out.numel() != M * N:
+        raise ValueError(f"conv output buffer has {out.numel()} elements, need {M * N}")
+    if residual is not None and residual.numel() != M * N:
+        raise ValueError("residual must have the output's shape")
+    if int(relu) not in (0, 1, 2):
+        raise ValueError("conv epilogue activation must be 0 (none), 1 (ReLU) or 2 (ReLU6)")
+    pF, pKS = skinny_plan(M, N, K, dtype)
+    F, KS = int(F or pF), int(ksplit or pKS)
+    if F not in SKINNY_F:
+        raise ValueError(f"skinny GEMM: F must be one of {SKINNY_F}, got {F}")
+    chunks = math.ceil(pc.Kpad / SKINNY_KC[dtype])
+    if not 1 <= KS <= chunks:
+        raise ValueError(f"skinny GEMM: ksplit {KS} outside 1 .. {chunks}, the chunks of K = {K}")
+    if pc.w.shape[0] < math.ceil(N / (16 * F)) * 16 * F:
+        raise ValueError("packed weights not padded to the channel tile")
+    ws_ptr, ctr_ptr = _scratch_ptrs(skinny_scratch(M, N, K, dtype, F, KS), workspace, counters, x.device)
+    fn = kernels().gemm_skinny_f32 if dtype == torch.float32 else kernels().gemm_skinny_bf16
+    fn(ptr(x), ptr(pc.w), ptr(pc.bias), ptr(residual), ptr(out), ws_ptr, ctr_ptr, M, N, K, pc.Kpad, pc.w.shape[0],
+       int(relu), F, KS, stream_handle(stream))
+    return out
+
+
 RR3_CFGS = {71: 1, 72: 2}                     # 3x3 with the filter resident in VGPRs (conv3x3_rr.hip) -> K groups
 
 

@@ -93,7 +93,8 @@ class SliceExecutor:
     def __init__(self, g: Graph, weights: Dict[str, np.ndarray], batch: int, device="cuda",
                  outputs: Optional[Sequence[str]] = None, tune: bool = False, num_sets: int = 1,
                  precision: str = "fp32", private_sets: bool = False, attention_math: Optional[str] = None,
-                 kv_cache: Optional[int] = None, _decode_of: Optional["SliceExecutor"] = None):
+                 kv_cache: Optional[int] = None, _decode_of: Optional["SliceExecutor"] = None,
+                 _decode_gemm: str = "tiles"):
         """precision: "bf16" (bf16 activations / weights, fp32 accumulation: the
         fast path) or "fp32" (fp32 activations and weights on the fp32 matrix
         cores: the reference's Keras float32 numerics, csrc/kernels/conv_f32.hip).
@@ -147,6 +148,8 @@ class SliceExecutor:
         self._graphs: List[Optional[torch.cuda.CUDAGraph]] = [None] * num_sets
         self.kv_cache = None if kv_cache is None else int(kv_cache)
         self._decode_of = _decode_of
+        self.decode_gemm = _decode_gemm               # a decoder's GEMM path (`decoder`): "tiles" or "skinny"
+        self._skinny: Dict[int, Tuple[int, int]] = {}  # conv step -> (F, KS) of its skinny_forward launch
         self._kv: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None     # layer -> (K, V) caches
         if self.kv_cache is not None:
             self._plan_kv(weights)
@@ -551,13 +554,28 @@ class SliceExecutor:
         attn_ops.attention_decode(q.view(self.batch, -1), kc, vc, self._pos, b[st.out].view(self.batch, -1), h, d, dv,
                                   kv_heads=hkv, workspace=self._dec_ws, stream=stream)
 
-    def decoder(self) -> "SliceExecutor":
+    DECODE_GEMM = ("tiles", "skinny")
+
+    @property
+    def skinny_steps(self) -> List[int]:
+        """Indices of the conv steps a decoder built with gemm="skinny" runs on the skinny GEMM."""
+        return sorted(self._skinny)
+
+    def decoder(self, gemm: Optional[str] = None) -> "SliceExecutor":
         """The step executor behind this prefill executor (`kv_cache` set): the same model at one token per
         sequence, on this executor's prepared weights, caches and positions.  A run appends the token's keys and
         values at pos[b], attends keys 0 .. pos[b] and ends by advancing pos, so its captured graph replays token
         after token.  Refused by layer name: learned position tables, padding masks, separate sources, window
-        attention, non-causal attention, heads the decode kernel does not serve; and a cut graph."""
+        attention, non-causal attention, heads the decode kernel does not serve; and a cut graph.
+        gemm: "tiles" (every conv step on the tile config the plan selects, as the prefill executor) or "skinny"
+        (each conv step `conv_ops.skinny_supported` takes at this batch, the projections and the MLP of a
+        transformer, runs `conv_ops.skinny_forward` on the same packed weights; `skinny_steps` lists them and the
+        rest keep their tile config); None reads ADAPT_DECODE_GEMM, default "tiles"."""
         from ..models.zoo import build_model
+        if gemm is None:
+            gemm = os.environ.get("ADAPT_DECODE_GEMM", "tiles")
+        if gemm not in self.DECODE_GEMM:
+            raise ValueError(f"decoder: gemm must be one of {self.DECODE_GEMM}, got {gemm!r}")
         if self._kv is None or self._decode_of is not None:
             raise ValueError("decoder: needs a prefill executor, SliceExecutor(..., kv_cache=max_tokens)")
         g = self.g
@@ -571,7 +589,7 @@ class SliceExecutor:
         if head.op == "dense":
             kw["classes"] = int(head.attrs["units"])
         return SliceExecutor(build_model(g.name, **kw), self._weights, self.batch, device=self.device,
-                             precision=self.precision, kv_cache=self.kv_cache, _decode_of=self)
+                             precision=self.precision, kv_cache=self.kv_cache, _decode_of=self, _decode_gemm=gemm)
 
     def _pack_rmsnorm(self, weights: Dict[str, np.ndarray], st: Step, cp: int):
         """scale fp32 [cp] of an rmsnorm step, with Keras' default for scale=False; the bf16 layout's padding
@@ -797,6 +815,10 @@ class SliceExecutor:
             B, H, W, _, _, _, pc = self._conv_geom(i)
             nws, nctr = scratch(cfg, ks, B, H, W, pc)
             need, ctr = max(need, nws), max(ctr, nctr)
+        for i, (F, ks) in self._skinny.items():
+            B, _, _, _, OH, OW, pc = self._conv_geom(i)
+            nws, nctr = conv_ops.skinny_scratch(B * OH * OW, pc.cout, pc.cin, pc.w.dtype, F, ks)
+            need, ctr = max(need, nws), max(ctr, nctr)
         if need and (self._ws is None or self._ws.numel() < need):
             self._ws = torch.empty(need, dtype=torch.float32, device=self.device)
             if self._side:                     # side-stream convs must not share scratch with the main stream
@@ -832,6 +854,18 @@ class SliceExecutor:
             else:
                 cfg, ks = conv_ops.choose_cfg(B * OH * OW, pc.cout, pc.Kpad)
             self.cfg[i] = (int(cfg), int(ks))
+        if self._decode_of is not None and self.decode_gemm == "skinny":
+            for i, st in enumerate(self.steps):
+                # the model's head (a Dense over the vocabulary at the output) keeps its tile config: the kernel is
+                # unmeasured at that N
+                if st.kind != "conv" or st.p.get("out2") or st.out in self.outputs:
+                    continue
+                B, _, _, _, OH, OW, pc = self._conv_geom(i)
+                bufs = self.bufs(0)                    # input and output in the weights' type (not an fp32 logits row)
+                if (conv_ops.skinny_supported(pc, B * OH * OW)
+                        and conv_ops.skinny_preferred(B * OH * OW, pc.cout, pc.cin, pc.w.dtype)
+                        and bufs[st.ins[0]].dtype == bufs[st.out].dtype == pc.w.dtype):
+                    self._skinny[i] = conv_ops.skinny_plan(B * OH * OW, pc.cout, pc.cin, pc.w.dtype)
         self._ensure_ws()
         if tune:
             self.autotune_f32() if self.fp32 else self.autotune(verbose=os.environ.get("ADAPT_TUNE_VERBOSE", "0") == "1")
@@ -1037,6 +1071,11 @@ class SliceExecutor:
             elif k == "stem":
                 conv_ops.stem_forward(b[st.ins[0]], self.packed[i], b[st.out], pool=st.p["pool"],
                                       pool_pad=st.p["pool_pad"], stream=stream)
+            elif k == "conv" and i in self._skinny:
+                F, ks = self._skinny[i]
+                conv_ops.skinny_forward(b[st.ins[0]], self.packed[i], b[st.out],
+                                        residual=b[st.ins[1]] if len(st.ins) > 1 else None, relu=st.p["relu"], F=F,
+                                        ksplit=ks, workspace=ws, counters=ctr, stream=stream)
             elif k == "conv":
                 cfg, ks = self.cfg[i]
                 res = b[st.ins[1]] if len(st.ins) > 1 else None
@@ -1155,7 +1194,12 @@ class SliceExecutor:
         """One step of the fp32 path (csrc/kernels/conv_f32.hip)."""
         k = st.kind
         ctr = self._ctr_side if stream is not None and stream is self._side_stream else self._ctr
-        if k == "conv":
+        if k == "conv" and i in self._skinny:
+            F, ks = self._skinny[i]
+            conv_ops.skinny_forward(b[st.ins[0]], self.packed[i], b[st.out],
+                                    residual=b[st.ins[1]] if len(st.ins) > 1 else None, relu=st.p["relu"], F=F,
+                                    ksplit=ks, workspace=ws, counters=ctr, stream=stream)
+        elif k == "conv":
             cfg, ks = self.cfg[i]
             res = b[st.ins[1]] if len(st.ins) > 1 else None
             out2 = b[st.p["out2"]] if st.p.get("out2") else None
@@ -1312,6 +1356,8 @@ class SliceExecutor:
         lines = []
         for i, st in enumerate(self.steps):
             extra = f" cfg={self.cfg[i]}" if i in self.cfg else ""
+            if i in self._skinny:                # a decoder's skinny GEMM step: (F, KS) instead of the tile config
+                extra = f" skinny={self._skinny[i]}"
             if st.p.get("subsample"):            # produced on the lattice its stride-s readers sample
                 extra += f" subsample={st.p['subsample']} -> {st.p['out_hw'][0]}x{st.p['out_hw'][1]}"
             lines.append(f"{i:3d} {st.kind:8s} {st.out:28s} <- {st.ins}{extra}")

@@ -250,6 +250,19 @@ PYBIND11_MODULE(_C, m) {
                                  P<float>(logits), P<float>(probs), M, N, K, Kpad, S(s)),
           "dense_small_f32");
   });
+  m.def("gemm_skinny_chunks", &adapt::gemm_skinny_chunks);
+  m.def("gemm_skinny_f32", [](u64 x, u64 w, u64 bias, u64 res, u64 out, u64 ws, u64 counters, int M, int N, int K,
+                              int Kpad, int Npad, int act, int F, int KS, u64 s) {
+    check(adapt::gemm_skinny_f32(P<const float>(x), P<const float>(w), P<const float>(bias), P<const float>(res),
+                                 P<float>(out), P<float>(ws), P<int>(counters), M, N, K, Kpad, Npad, act, F, KS, S(s)),
+          "gemm_skinny_f32");
+  });
+  m.def("gemm_skinny_bf16", [](u64 x, u64 w, u64 bias, u64 res, u64 out, u64 ws, u64 counters, int M, int N, int K,
+                               int Kpad, int Npad, int act, int F, int KS, u64 s) {
+    check(adapt::gemm_skinny_bf16(P<const bf16>(x), P<const bf16>(w), P<const float>(bias), P<const bf16>(res),
+                                  P<bf16>(out), P<float>(ws), P<int>(counters), M, N, K, Kpad, Npad, act, F, KS, S(s)),
+          "gemm_skinny_bf16");
+  });
   m.def("gap", [](u64 x, u64 y, u64 y32, int B, int HW, int C, u64 s) {
     check(adapt::gap(P<const bf16>(x), P<bf16>(y), P<float>(y32), B, HW, C, S(s)), "gap");
   });

@@ -100,6 +100,17 @@ hipError_t dense_small_f32(const float* x, const float* w, const float* bias, fl
                            float* probs, int M, int N, int K, int Kpad, hipStream_t s);
 hipError_t dense_small(const bf16* x, const bf16* w, const float* bias, float* part, float* logits, float* probs,
                        int M, int N, int K, int Kpad, hipStream_t s);
+// Skinny GEMM of the one-token decode step (gemm_skinny.h): out[M][N] = act(x[M][K] . w[Npad][Kpad]^T + bias (+ res)),
+// 1 <= M <= 32, on a 1x1 conv's packed weights.  F in 1 / 2 / 4: 16 F channels per block; KS >= 1 splits of K, at
+// most gemm_skinny_chunks (256-byte pieces of a weight row); KS > 1 needs ws (fp32 [KS][M][N]) and one zeroed int32
+// counter per channel tile (ceil(N / 16 F)), which the launch leaves zero.  K and N multiples of 4 (fp32) / 8 (bf16).
+int gemm_skinny_chunks(int Kpad, int elem_size);
+hipError_t gemm_skinny_f32(const float* x, const float* w, const float* bias, const float* res, float* out,
+                           float* ws, int* counters, int M, int N, int K, int Kpad, int Npad, int act, int F,
+                           int KS, hipStream_t s);
+hipError_t gemm_skinny_bf16(const bf16* x, const bf16* w, const float* bias, const bf16* res, bf16* out, float* ws,
+                            int* counters, int M, int N, int K, int Kpad, int Npad, int act, int F, int KS,
+                            hipStream_t s);
 hipError_t softmax_rows(const float* x, float* y, int rows, int N, int ldx, hipStream_t s);
 hipError_t cast_bf16_f32(const bf16* x, float* y, size_t n, hipStream_t s);
 hipError_t pad(const bf16* x, bf16* y, int B, int H, int W, int C, int OH, int OW, int pad_t, int pad_l,

@@ -3,9 +3,14 @@
 `Model.generate` (prefill once, then one replay of the captured one-token step graph per token) is timed end to end,
 and the step graph alone with device events.  The alternative is a full-sequence forward pass per new token; it is
 timed at the final length P + N on a captured graph (the passes at shorter lengths are cheaper, so this is its
-upper end, and a plan per length is not counted).  Prints one line per precision.
+upper end, and a plan per length is not counted).  Prints one line per precision and GEMM path.
 
-    python tools/decode_bench.py --model tinyllama_1_1b --batch 8 --prompt-tokens 128 --new-tokens 128
+`--gemm tiles,skinny` builds one executor pair per path (`SliceExecutor.decoder(gemm=...)`) and times their step
+graphs alternately, round after round in one process, then prints each path's median with the spread of its
+rounds and the ratio between the paths.
+
+    python tools/decode_bench.py --model tinyllama_1_1b --batch 8 --prompt-tokens 128 --new-tokens 128 \
+        --gemm tiles,skinny
 """
 import argparse
 import os
@@ -41,6 +46,7 @@ def main():
     ap.add_argument("--new-tokens", type=int, default=128)
     ap.add_argument("--precisions", default="fp32,bf16")
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--gemm", default="tiles", help="comma-separated decoder GEMM paths: tiles, skinny")
     a = ap.parse_args()
     B, P, N = a.batch, a.prompt_tokens, a.new_tokens
     print(torch.cuda.get_device_name(0), flush=True)
@@ -50,17 +56,26 @@ def main():
     vocab = int(g.layers[g.output_names[0]].attrs["units"])
     ids = np.random.default_rng(0).integers(0, vocab, (B, P + N))
     m = Model(g, w)
+    gemms = a.gemm.split(",")
     for precision in a.precisions.split(","):
-        toks = m.generate(ids[:, :P], N, precision=precision)               # build, capture, warm up
-        gen = []
-        for _ in range(a.rounds):
-            t0 = time.perf_counter()
-            m.generate(ids[:, :P], N, precision=precision)                  # ends in a device synchronise
-            gen.append((time.perf_counter() - t0) * 1e3)
-        ex, dec = next(v for k, v in m._executors.items() if k[0] == "generate" and k[-1] == precision)
-        prefill = sorted(events_ms(lambda: ex.forward(0), 3) for _ in range(a.rounds))[a.rounds // 2]
-        ex.forward(0)                                                       # pos = P again
-        step = sorted(events_ms(lambda: dec.forward(0), N) for _ in range(1))[0]      # N replays: positions P .. P + N - 1
+        toks, gen, steps, prefill = {}, {}, {}, {}
+        for gm in gemms:
+            toks[gm] = m.generate(ids[:, :P], N, precision=precision, decode_gemm=gm)    # build, capture, warm up
+            gen[gm], steps[gm] = [], []
+        for _ in range(a.rounds):                                           # the paths alternate within a round
+            for gm in gemms:
+                t0 = time.perf_counter()
+                m.generate(ids[:, :P], N, precision=precision, decode_gemm=gm)          # ends in a device synchronise
+                gen[gm].append((time.perf_counter() - t0) * 1e3)
+                ex, dec = next(v for k, v in m._executors.items() if k[0] == "generate" and k[-2:] == (precision, gm))
+                ex.forward(0)                                               # pos = P again
+                steps[gm].append(events_ms(lambda: dec.forward(0), N))      # N replays: positions P .. P + N - 1
+        for gm in gemms:
+            ex, dec = next(v for k, v in m._executors.items() if k[0] == "generate" and k[-2:] == (precision, gm))
+            prefill[gm] = sorted(events_ms(lambda: ex.forward(0), 3) for _ in range(a.rounds))[a.rounds // 2]
+            if dec.skinny_steps:
+                print(f"{a.model} {precision} gemm={gm}: {len(dec.skinny_steps)} conv steps on the skinny GEMM, (F, KS) "
+                      f"{sorted(set(dec._skinny.values()))}", flush=True)
         del ex, dec
         m._executors.clear()
         torch.cuda.empty_cache()
@@ -72,11 +87,22 @@ def main():
         fwd = sorted(events_ms(lambda: full.forward(0), 5) for _ in range(a.rounds))[a.rounds // 2]
         del full
         torch.cuda.empty_cache()
-        med = sorted(gen)[a.rounds // 2]
-        print(f"{a.model} {precision} B{B} prompt {P} + {N} new: generate {med:.1f} ms end to end = {med / N:.3f} ms per "
-              f"token ({B * N / med * 1e3:.0f} tokens/s; prefill {prefill:.2f} ms, step graph alone {step:.3f} ms per "
-              f"token) | full forward pass at {P + N} tokens {fwd:.2f} ms per token ({fwd / (med / N):.1f}x generate per "
-              f"token, {fwd / step:.1f}x the step graph) | first tokens {toks[0, :4].tolist()}", flush=True)
+        for gm in gemms:
+            med, step = sorted(gen[gm])[a.rounds // 2], sorted(steps[gm])[a.rounds // 2]
+            print(f"{a.model} {precision} gemm={gm} B{B} prompt {P} + {N} new: generate {med:.1f} ms end to end = "
+                  f"{med / N:.3f} ms per token ({B * N / med * 1e3:.0f} tokens/s; prefill {prefill[gm]:.2f} ms, step graph "
+                  f"alone {step:.3f} ms per token, rounds {' '.join(f'{v:.3f}' for v in steps[gm])}, spread "
+                  f"{max(steps[gm]) - min(steps[gm]):.3f}) | full forward pass at {P + N} tokens {fwd:.2f} ms per token "
+                  f"({fwd / (med / N):.1f}x generate per token, {fwd / step:.1f}x the step graph) | first tokens "
+                  f"{toks[gm][0, :4].tolist()}", flush=True)
+        if len(gemms) > 1:
+            base = sorted(steps[gemms[0]])[a.rounds // 2]
+            for gm in gemms[1:]:
+                step = sorted(steps[gm])[a.rounds // 2]
+                spread = max(max(steps[g_]) - min(steps[g_]) for g_ in (gemms[0], gm))
+                print(f"{a.model} {precision} step graph alone: {gm} {step:.3f} ms against {gemms[0]} {base:.3f} ms = "
+                      f"{base / step:.2f}x, ahead by {base - step:.3f} ms (largest spread of the rounds {spread:.3f} ms)",
+                      flush=True)
 
 
 if __name__ == "__main__":

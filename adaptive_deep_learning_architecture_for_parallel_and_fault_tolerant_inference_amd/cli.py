@@ -251,14 +251,18 @@ def cmd_generate(argv):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--decode-gemm", default=None, choices=["tiles", "skinny"],
                     help="GEMM path of the one-token step (default: ADAPT_DECODE_GEMM, else tiles)")
+    ap.add_argument("--weight-quant", default=None, choices=["mxfp4"],
+                    help="quantise the projections and the MLP (bf16 only); with --decode-gemm skinny the step "
+                         "streams the 4-bit codes")
     a = ap.parse_args(argv)
     from .models.model import application
     m = application(a.model, seed=a.seed)
     vocab = int(m.graph.layers[m.graph.output_names[0]].attrs["units"])
     ids = np.random.default_rng(a.seed).integers(0, vocab, (a.batch, a.prompt_tokens))
-    m.generate(ids, a.new_tokens, device=a.device, precision=a.precision, decode_gemm=a.decode_gemm)   # build / capture
+    kw = dict(device=a.device, precision=a.precision, decode_gemm=a.decode_gemm, weight_quant=a.weight_quant)
+    m.generate(ids, a.new_tokens, **kw)   # build / capture
     start = time.time()
-    toks = m.generate(ids, a.new_tokens, device=a.device, precision=a.precision, decode_gemm=a.decode_gemm)
+    toks = m.generate(ids, a.new_tokens, **kw)
     run = time.time() - start
     print(toks[0].tolist())
     print(f"{a.batch} x {a.new_tokens} tokens after a prompt of {a.prompt_tokens} in {run:.4f} seconds")

@@ -129,14 +129,17 @@ class Model:
         return np.concatenate(outs)
 
     def generate(self, ids, new_tokens: int, max_tokens: Optional[int] = None, device: Optional[str] = None,
-                 precision: str = "fp32", return_logits: bool = False, decode_gemm: Optional[str] = None):
+                 precision: str = "fp32", return_logits: bool = False, decode_gemm: Optional[str] = None,
+                 weight_quant: Optional[str] = None):
         """Greedy incremental decoding of a decoder-only model with rotary positions (the Llama family): `ids`
         (B, P) token ids; one prefill pass over the prompt fills the key / value caches, then every further token
         is one replay of the captured one-token step graph (csrc/kernels/attention_decode.h).  Between replays the
         argmax is a torch op on the device; ids stay float32, as everywhere here.  Returns (B, new_tokens) int64
         ids, with `return_logits` also the (B, new_tokens, V) float32 logits they are the argmax of.  `max_tokens`
         (default P + new_tokens) sizes the caches.  `decode_gemm` is `SliceExecutor.decoder`'s `gemm` ("tiles",
-        "skinny"; None: ADAPT_DECODE_GEMM, default "tiles"), and each value keeps executors of its own.  No sampling; the CPU path has no decoding.  The prefill graph
+        "skinny"; None: ADAPT_DECODE_GEMM, default "tiles"), and each value keeps executors of its own.  `weight_quant` is
+        `SliceExecutor`'s ("mxfp4", precision "bf16" only: the projections and the MLP quantised, the decode step
+        with decode_gemm="skinny" on the 4-bit codes), again with executors of its own.  No sampling; the CPU path has no decoding.  The prefill graph
         (P tokens) and the step graph (one token) are rebuilt by the zoo builder of `self.graph.name`, so the model
         must be one that `models.zoo.build_model` knows by name; any other (a Keras-JSON model) is refused."""
         import torch
@@ -162,12 +165,13 @@ class Model:
                              f"prefill and step graphs are rebuilt by name at other token counts")
         if decode_gemm is None:
             decode_gemm = os.environ.get("ADAPT_DECODE_GEMM", "tiles")
-        key = ("generate", device, B, P, Tmax, precision, decode_gemm)
+        key = ("generate", device, B, P, Tmax, precision, weight_quant, decode_gemm)
         ent = self._executors.get(key)
         V = int(self.graph.layers[self.graph.output_names[0]].attrs["units"])
         if ent is None:
             g = build_model(self.graph.name, input_shape=(P,), classes=V)
-            ex = SliceExecutor(g, self.weights, B, device=device, precision=precision, kv_cache=Tmax)
+            ex = SliceExecutor(g, self.weights, B, device=device, precision=precision, kv_cache=Tmax,
+                               weight_quant=weight_quant)
             dec = ex.decoder(gemm=decode_gemm)
             dec.capture()
             ent = self._executors[key] = (ex, dec)

@@ -19,6 +19,7 @@ from typing import Callable, NamedTuple, Optional
 import numpy as np
 import torch
 
+from . import mx as mx_format
 from ._lib import kernels, ptr, stream_handle
 
 BK = 64
@@ -104,6 +105,9 @@ class PackedConv:
     # fp32, s > 1: only output pixels (s i, s j) are read afterwards; a launch must write those and may leave the
     # others as they were (conv_forward_f32; runtime/plan.py `live_lattice`)
     out_lattice: int = 0
+    # bf16 1x1: the same weights as MXFP4 codes and scales for the decode step (pack_conv_mxfp4); `w` then holds
+    # exactly their dequantised values
+    mx: Optional["MxWeights"] = None
 
     @property
     def K(self) -> int:
@@ -137,6 +141,28 @@ def pack_conv(kernel_hwio: np.ndarray, bias: np.ndarray, stride: int, pads, devi
         w=torch.from_numpy(wt).to(device=device, dtype=torch.bfloat16).contiguous(),
         bias=torch.from_numpy(np.ascontiguousarray(bias, np.float32)).to(device),
         kh=kh, kw=kw, cin=cp, cout=cout, stride=stride, pad_t=pt, pad_l=pl, pad_b=pb, pad_r=pr)
+
+
+class MxWeights(NamedTuple):
+    """MXFP4 weights on the device in csrc/kernels/gemm_skinny_mx.h's layout (ops/mx.py pack_mxfp4)."""
+    codes: torch.Tensor      # int32 [Npad][Kpad / 128][4][4]: e2m1 codes, eight a word
+    scales: torch.Tensor     # int32 [Npad][Kpad / 128]: four e8m0 bytes a dword
+
+
+def pack_conv_mxfp4(kernel_hwio: np.ndarray, bias: np.ndarray, device) -> PackedConv:
+    """A 1x1 / stride 1 conv with its kernel quantised to MXFP4 along the input channels: `w` is `pack_conv` of the
+    dequantised kernel (exact in bf16, so every bf16 path computes the quantised model), `mx` the codes and scales
+    the decode step streams instead (`mx_forward`)."""
+    kh, kw, cin, cout = kernel_hwio.shape
+    if (kh, kw) != (1, 1):
+        raise ValueError(f"MXFP4 weights are for 1x1 convs, got a {kh}x{kw} kernel")
+    codes, exps = mx_format.quantize_mxfp4(np.asarray(kernel_hwio, np.float32).reshape(cin, cout).T)
+    deq = mx_format.dequantize_mxfp4(codes, exps)
+    pc = pack_conv(np.ascontiguousarray(deq.T).reshape(1, 1, cin, cout), bias, 1, ((0, 0), (0, 0)), device)
+    words, scales = mx_format.pack_mxfp4(codes, exps)
+    pc.mx = MxWeights(torch.from_numpy(words.view(np.int32)).to(device),
+                      torch.from_numpy(scales.view(np.int32)).to(device))
+    return pc
 
 
 def choose_cfg(M: int, N: int, Kpad: int, occupancy: int = 2):
@@ -1186,6 +1212,95 @@ def skinny_forward(x: torch.Tensor, pc: "PackedConv", out: torch.Tensor, residua
     fn = kernels().gemm_skinny_f32 if dtype == torch.float32 else kernels().gemm_skinny_bf16
     fn(ptr(x), ptr(pc.w), ptr(pc.bias), ptr(residual), ptr(out), ws_ptr, ctr_ptr, M, N, K, pc.Kpad, pc.w.shape[0],
        int(relu), F, KS, stream_handle(stream))
+    return out
+
+
+# ------------------------------------------------- skinny GEMM on MXFP4 weights (one-token decode steps)
+# csrc/kernels/gemm_skinny_mx.h: the skinny GEMM's contract on `pc.mx` (pack_conv_mxfp4) instead of `pc.w`, bf16
+# activations only.  Chunks are 128 k; channel tiles go up to F = 8, because with 4-bit weights the activations,
+# re-read by every channel tile, are the larger stream.  The functions mirror the skinny_* ones above.
+MX_F = (1, 2, 4, 8)
+MX_KC = mx_format.MX_KC
+MX_BLOCKS_PER_CU = 2
+MX_MAX_KS = 4
+
+
+def mx_chunks(K: int) -> int:
+    """Chunks of a row of K input channels: the most splits a launch takes."""
+    return math.ceil(K / MX_KC)
+
+
+def mx_supported(pc: "PackedConv", M: int) -> bool:
+    """`skinny_supported` in bf16, on a conv that carries MXFP4 codes."""
+    return pc.mx is not None and pc.w.dtype == torch.bfloat16 and skinny_supported(pc, M)
+
+
+def mx_plan(M: int, N: int, K: int):
+    """(F, KS), from tools/skinny_bench.py --weights mxfp4 --sweep at M = 1, 8, 16 (BASELINE.md "Round 25").  KS: a
+    split of about 8 chunks, two per wave, but at most MX_MAX_KS splits (on every K from 4096 to 11008 four splits
+    were fastest: more of them cost more in the merge than they save), and more only where a small N leaves CUs
+    without a block.  Then the widest F that keeps MX_BLOCKS_PER_CU blocks per CU: below that the narrow tile wins
+    as in `skinny_plan`, at it the wider tile's smaller x traffic does (llama2_7b qkv and gate / up: F = 4)."""
+    chunks, tiles = mx_chunks(K), math.ceil(N / 16)
+    ks = min(MX_MAX_KS, max(1, chunks // 8))
+    if tiles * ks < NUM_CUS:
+        ks = min(max(1, chunks // 4), max(ks, NUM_CUS // tiles))
+    return max((F for F in MX_F if math.ceil(N / (16 * F)) * ks >= MX_BLOCKS_PER_CU * NUM_CUS), default=1), ks
+
+
+def mx_preferred(M: int, N: int, K: int) -> bool:
+    """Whether a decoder routes a supported quantised step here rather than where it goes without the codes.  Every
+    supported launch, except the region where tools/skinny_bench.py --weights mxfp4 shows the kernel behind
+    (BASELINE.md "Round 25"): up to 16 rows on 2^22 to 2^23 weights (tinyllama_1_1b's out and qkv, 2 to 13 % behind
+    the bf16 skinny kernel: at 8 to 10 MB of bf16 both run at the latency floor and the conversions only add to
+    it).  Above 16 rows the alternative is the tile config (`skinny_preferred`), and the kernel is ahead of it on
+    every shape; GEMMs below 2^22 weights are unmeasured and keep the starting rule."""
+    return M > 16 or not (1 << 22) <= N * K < (1 << 23)
+
+
+def mx_scratch(M: int, N: int, K: int, F: int, KS: int):
+    """(fp32 workspace elements, int32 arrival counters) of a launch, exact."""
+    return skinny_scratch(M, N, K, torch.bfloat16, F, KS)
+
+
+def mx_forward(x: torch.Tensor, pc: "PackedConv", out: torch.Tensor, residual: Optional[torch.Tensor] = None,
+               relu: int = 0, F: Optional[int] = None, ksplit: Optional[int] = None,
+               workspace: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None,
+               stream=None) -> torch.Tensor:
+    """`skinny_forward` on the MXFP4 codes of `pc` (pack_conv_mxfp4): out [M, N] = act(x [M, K] . deq(W)^T + bias
+    (+ residual)), bf16 tensors, 1 <= M <= 32.  `F` / `ksplit` default to `mx_plan`, scratch is `mx_scratch`'s."""
+    C = x.shape[-1]
+    M = x.numel() // max(C, 1)
+    if C != pc.cin:
+        raise ValueError(f"conv expects {pc.cin} input channels, got {C}")
+    if pc.mx is None:
+        raise ValueError("MXFP4 skinny GEMM: this PackedConv carries no MXFP4 codes (pack_conv_mxfp4)")
+    if not mx_supported(pc, M):
+        raise ValueError(f"MXFP4 skinny GEMM does not take this conv ({pc.kh}x{pc.kw}/s{pc.stride}, {pc.cin} -> "
+                         f"{pc.cout} channels, n_split {pc.n_split}) at {M} rows: 1x1 / stride 1, one output, "
+                         f"1 <= M <= {SKINNY_MAX_M}")
+    N, K = pc.cout, pc.cin
+    for t, nm in ((x, "x"), (out, "out"), (residual, "residual")):
+        if t is not None and (t.dtype != torch.bfloat16 or not t.is_contiguous()):
+            raise ValueError(f"MXFP4 skinny GEMM: {nm} must be contiguous bf16")
+    if out.numel() != M * N:
+        raise ValueError(f"conv output buffer has {out.numel()} elements, need {M * N}")
+    if residual is not None and residual.numel() != M * N:
+        raise ValueError("residual must have the output's shape")
+    if int(relu) not in (0, 1, 2):
+        raise ValueError("conv epilogue activation must be 0 (none), 1 (ReLU) or 2 (ReLU6)")
+    pF, pKS = mx_plan(M, N, K)
+    F, KS = int(F or pF), int(ksplit or pKS)
+    if F not in MX_F:
+        raise ValueError(f"MXFP4 skinny GEMM: F must be one of {MX_F}, got {F}")
+    Npad, nch = pc.mx.scales.shape
+    if not 1 <= KS <= nch:
+        raise ValueError(f"MXFP4 skinny GEMM: ksplit {KS} outside 1 .. {nch}, the chunks of K = {K}")
+    if Npad < math.ceil(N / (16 * F)) * 16 * F or nch != mx_chunks(K) or pc.mx.codes.numel() != Npad * nch * 16:
+        raise ValueError("MXFP4 codes not in the kernel's layout for this conv (ops.mx.pack_mxfp4)")
+    ws_ptr, ctr_ptr = _scratch_ptrs(mx_scratch(M, N, K, F, KS), workspace, counters, x.device)
+    kernels().gemm_skinny_mx(ptr(x), ptr(pc.mx.codes), ptr(pc.mx.scales), ptr(pc.bias), ptr(residual), ptr(out),
+                             ws_ptr, ctr_ptr, M, N, K, nch * MX_KC, Npad, int(relu), F, KS, stream_handle(stream))
     return out
 
 

@@ -94,7 +94,7 @@ class SliceExecutor:
                  outputs: Optional[Sequence[str]] = None, tune: bool = False, num_sets: int = 1,
                  precision: str = "fp32", private_sets: bool = False, attention_math: Optional[str] = None,
                  kv_cache: Optional[int] = None, _decode_of: Optional["SliceExecutor"] = None,
-                 _decode_gemm: str = "tiles"):
+                 _decode_gemm: str = "tiles", weight_quant: Optional[str] = None):
         """precision: "bf16" (bf16 activations / weights, fp32 accumulation: the
         fast path) or "fp32" (fp32 activations and weights on the fp32 matrix
         cores: the reference's Keras float32 numerics, csrc/kernels/conv_f32.hip).
@@ -115,9 +115,23 @@ class SliceExecutor:
         before its attention launch, and `pos` (int32 [batch] on the device) holds
         the prompt length after a run.  Every output is what it is without the
         cache; `decoder()` returns the one-token step executor that goes on from
-        there (csrc/kernels/attention_decode.h)."""
+        there (csrc/kernels/attention_decode.h).
+        weight_quant: None (the default: nothing changes) or "mxfp4" (precision "bf16"
+        only): the kernel of every 1x1 conv step the skinny GEMM takes by shape, whatever
+        the batch, except the graph's output layer, is quantised to MXFP4 as it is packed
+        (ops/mx.py; in a decoder-only transformer: the projections and the MLP).  Every
+        path then computes the model with the dequantised weights: the tile configs on
+        their bf16 copy (exact), and a `decoder(gemm="skinny")` on the 4-bit codes
+        (csrc/kernels/gemm_skinny_mx.h; `mx_steps`).  The codes come on top of the bf16
+        copy: device memory grows, the bytes a decode step streams shrink."""
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"precision must be bf16 or fp32, got {precision!r}")
+        if weight_quant not in self.WEIGHT_QUANT:
+            raise ValueError(f"weight_quant must be one of {self.WEIGHT_QUANT}, got {weight_quant!r}")
+        if weight_quant is not None and precision != "bf16":
+            raise ValueError(f"weight_quant={weight_quant!r} needs precision=\"bf16\": the dequantised weights are "
+                             f"bf16 numbers and the kernel takes bf16 activations")
+        self.weight_quant = weight_quant
         if attention_math is None:
             attention_math = os.environ.get("ADAPT_ATTENTION_MATH", "fp32")
         if attention_math not in attn_ops.ATTENTION_MATH:
@@ -150,6 +164,7 @@ class SliceExecutor:
         self._decode_of = _decode_of
         self.decode_gemm = _decode_gemm               # a decoder's GEMM path (`decoder`): "tiles" or "skinny"
         self._skinny: Dict[int, Tuple[int, int]] = {}  # conv step -> (F, KS) of its skinny_forward launch
+        self._mx: Dict[int, Tuple[int, int]] = {}      # conv step -> (F, KS) of its mx_forward launch
         self._kv: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None     # layer -> (K, V) caches
         if self.kv_cache is not None:
             self._plan_kv(weights)
@@ -234,6 +249,9 @@ class SliceExecutor:
                     kf, bf = np.concatenate([kf, k2], axis=-1), np.concatenate([bf, b2])
                 pc = conv_ops.pack_conv(kf, bf, p["stride"], p["pads"], dev, cin_pad=cin_pad)
                 pc.n_split = n_split
+                if (self.weight_quant == "mxfp4" and not st.p.get("out2") and st.out not in self.outputs
+                        and cin_pad == kf.shape[2] and conv_ops.skinny_supported(pc, 1)):
+                    pc = conv_ops.pack_conv_mxfp4(kf, bf, dev)
                 self.packed[i] = pc
             elif st.kind == "bottleneck":
                 p = st.p
@@ -555,11 +573,18 @@ class SliceExecutor:
                                   kv_heads=hkv, workspace=self._dec_ws, stream=stream)
 
     DECODE_GEMM = ("tiles", "skinny")
+    WEIGHT_QUANT = (None, "mxfp4")
 
     @property
     def skinny_steps(self) -> List[int]:
         """Indices of the conv steps a decoder built with gemm="skinny" runs on the skinny GEMM."""
         return sorted(self._skinny)
+
+    @property
+    def mx_steps(self) -> List[int]:
+        """Indices of the quantised conv steps (`weight_quant`) a decoder built with gemm="skinny" runs on the
+        MXFP4 skinny GEMM."""
+        return sorted(self._mx)
 
     def decoder(self, gemm: Optional[str] = None) -> "SliceExecutor":
         """The step executor behind this prefill executor (`kv_cache` set): the same model at one token per
@@ -570,7 +595,9 @@ class SliceExecutor:
         gemm: "tiles" (every conv step on the tile config the plan selects, as the prefill executor) or "skinny"
         (each conv step `conv_ops.skinny_supported` takes at this batch, the projections and the MLP of a
         transformer, runs `conv_ops.skinny_forward` on the same packed weights; `skinny_steps` lists them and the
-        rest keep their tile config); None reads ADAPT_DECODE_GEMM, default "tiles"."""
+        rest keep their tile config); None reads ADAPT_DECODE_GEMM, default "tiles".  On an executor with
+        `weight_quant`, "skinny" routes each quantised step `conv_ops.mx_supported` and `mx_preferred` take to
+        `conv_ops.mx_forward` on the 4-bit codes (`mx_steps`), and "tiles" runs the dequantised bf16 weights."""
         from ..models.zoo import build_model
         if gemm is None:
             gemm = os.environ.get("ADAPT_DECODE_GEMM", "tiles")
@@ -589,7 +616,8 @@ class SliceExecutor:
         if head.op == "dense":
             kw["classes"] = int(head.attrs["units"])
         return SliceExecutor(build_model(g.name, **kw), self._weights, self.batch, device=self.device,
-                             precision=self.precision, kv_cache=self.kv_cache, _decode_of=self, _decode_gemm=gemm)
+                             precision=self.precision, kv_cache=self.kv_cache, _decode_of=self, _decode_gemm=gemm,
+                             weight_quant=self.weight_quant)
 
     def _pack_rmsnorm(self, weights: Dict[str, np.ndarray], st: Step, cp: int):
         """scale fp32 [cp] of an rmsnorm step, with Keras' default for scale=False; the bf16 layout's padding
@@ -819,6 +847,10 @@ class SliceExecutor:
             B, _, _, _, OH, OW, pc = self._conv_geom(i)
             nws, nctr = conv_ops.skinny_scratch(B * OH * OW, pc.cout, pc.cin, pc.w.dtype, F, ks)
             need, ctr = max(need, nws), max(ctr, nctr)
+        for i, (F, ks) in self._mx.items():
+            B, _, _, _, OH, OW, pc = self._conv_geom(i)
+            nws, nctr = conv_ops.mx_scratch(B * OH * OW, pc.cout, pc.cin, F, ks)
+            need, ctr = max(need, nws), max(ctr, nctr)
         if need and (self._ws is None or self._ws.numel() < need):
             self._ws = torch.empty(need, dtype=torch.float32, device=self.device)
             if self._side:                     # side-stream convs must not share scratch with the main stream
@@ -862,7 +894,10 @@ class SliceExecutor:
                     continue
                 B, _, _, _, OH, OW, pc = self._conv_geom(i)
                 bufs = self.bufs(0)                    # input and output in the weights' type (not an fp32 logits row)
-                if (conv_ops.skinny_supported(pc, B * OH * OW)
+                if (conv_ops.mx_supported(pc, B * OH * OW) and conv_ops.mx_preferred(B * OH * OW, pc.cout, pc.cin)
+                        and bufs[st.ins[0]].dtype == bufs[st.out].dtype == pc.w.dtype):
+                    self._mx[i] = conv_ops.mx_plan(B * OH * OW, pc.cout, pc.cin)     # the 4-bit codes of the step
+                elif (conv_ops.skinny_supported(pc, B * OH * OW)
                         and conv_ops.skinny_preferred(B * OH * OW, pc.cout, pc.cin, pc.w.dtype)
                         and bufs[st.ins[0]].dtype == bufs[st.out].dtype == pc.w.dtype):
                     self._skinny[i] = conv_ops.skinny_plan(B * OH * OW, pc.cout, pc.cin, pc.w.dtype)
@@ -1071,6 +1106,11 @@ class SliceExecutor:
             elif k == "stem":
                 conv_ops.stem_forward(b[st.ins[0]], self.packed[i], b[st.out], pool=st.p["pool"],
                                       pool_pad=st.p["pool_pad"], stream=stream)
+            elif k == "conv" and i in self._mx:
+                F, ks = self._mx[i]
+                conv_ops.mx_forward(b[st.ins[0]], self.packed[i], b[st.out],
+                                    residual=b[st.ins[1]] if len(st.ins) > 1 else None, relu=st.p["relu"], F=F,
+                                    ksplit=ks, workspace=ws, counters=ctr, stream=stream)
             elif k == "conv" and i in self._skinny:
                 F, ks = self._skinny[i]
                 conv_ops.skinny_forward(b[st.ins[0]], self.packed[i], b[st.out],
@@ -1358,6 +1398,8 @@ class SliceExecutor:
             extra = f" cfg={self.cfg[i]}" if i in self.cfg else ""
             if i in self._skinny:                # a decoder's skinny GEMM step: (F, KS) instead of the tile config
                 extra = f" skinny={self._skinny[i]}"
+            if i in self._mx:                    # ... or its MXFP4 skinny GEMM step
+                extra = f" mx={self._mx[i]}"
             if st.p.get("subsample"):            # produced on the lattice its stride-s readers sample
                 extra += f" subsample={st.p['subsample']} -> {st.p['out_hw'][0]}x{st.p['out_hw'][1]}"
             lines.append(f"{i:3d} {st.kind:8s} {st.out:28s} <- {st.ins}{extra}")

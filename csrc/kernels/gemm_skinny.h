@@ -108,6 +108,81 @@ struct SkinnyItems {
   static constexpr int NI = F * MF * 64, PER = (NI + 255) / 256;
 };
 
+// The tail every skinny kernel shares (gemm_skinny_mx.h too): merge of the four waves' accumulators, the split-K
+// arrival protocol and the epilogue, as the header describes them.  `red` and `flag` are the block's LDS.
+// P: SkinnyParams<T> or SkinnyMxParams (bias, res, out, ws, counters, M, N, act).
+template <typename T, int F, int MF, typename P>
+__device__ __forceinline__ void sk_finish(const f32x4 (&acc)[F][MF], f32x4 (&red)[4][SkinnyItems<F, MF>::NI],
+                                          int& flag, const P& p, int nb0, int wave, int lane) {
+  using IT = SkinnyItems<F, MF>;
+  const int KS = gridDim.y, ks = blockIdx.y;
+  // the four waves' sums meet in LDS (a wave without a chunk brings zeros) and are added in wave order
+#pragma unroll
+  for (int f = 0; f < F; ++f)
+#pragma unroll
+    for (int mf = 0; mf < MF; ++mf) red[wave][(f * MF + mf) * 64 + lane] = acc[f][mf];
+  __syncthreads();
+  f32x4 own[IT::PER];
+  int om[IT::PER], on[IT::PER];                                // item j: row and first channel; row -1 = nothing
+#pragma unroll
+  for (int j = 0; j < IT::PER; ++j) {
+    const int idx = threadIdx.x + 256 * j;
+    own[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    om[j] = -1;
+    on[j] = 0;
+    if (idx < IT::NI) {
+      const int fm = idx >> 6, l = idx & 63;
+      const int m = 16 * (fm % MF) + (l & 15), n = nb0 + 16 * (fm / MF) + 4 * (l >> 4);
+      own[j] = ((red[0][idx] + red[1][idx]) + red[2][idx]) + red[3][idx];
+      if (m < p.M && n < p.N) {
+        om[j] = m;
+        on[j] = n;
+      }
+    }
+  }
+  if (KS > 1) {
+    const __amdgpu_buffer_rsrc_t wsr = sk_rsrc(p.ws);
+    const int MN = p.M * p.N;
+#pragma unroll
+    for (int j = 0; j < IT::PER; ++j)
+      if (om[j] >= 0)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, own[j]), wsr,
+                                               (ks * MN + om[j] * p.N + on[j]) * 4, 0, SK_CPOL_SC1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int old = __hip_atomic_fetch_add(p.counters + blockIdx.x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int last = old == KS - 1;
+      if (last) __hip_atomic_store(p.counters + blockIdx.x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      flag = last;
+    }
+    __syncthreads();
+    if (!flag) return;
+#pragma unroll
+    for (int j = 0; j < IT::PER; ++j) {
+      if (om[j] < 0) continue;
+      f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int s = 0; s < KS; ++s) {
+        if (s == ks) sum += own[j];
+        else
+          sum += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                               wsr, (s * MN + om[j] * p.N + on[j]) * 4, 0, SK_CPOL_SC1));
+      }
+      own[j] = sum;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < IT::PER; ++j) {
+    if (om[j] < 0) continue;
+    const size_t o = (size_t)om[j] * p.N + on[j];
+    f32x4 v = own[j] + *(const f32x4*)(p.bias + on[j]);
+    if (p.res) v += sk_widen(p.res + o);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = act_relu(v[e], p.act);
+    sk_store(p.out + o, v);
+  }
+}
+
 template <typename T, int F, int MF>
 __global__ __launch_bounds__(256, (F * MF >= 8) ? 1 : 2) void gemm_skinny_kernel(SkinnyParams<T> p) {
   using ST = SkinnyType<T>;
@@ -181,71 +256,7 @@ __global__ __launch_bounds__(256, (F * MF >= 8) ? 1 : 2) void gemm_skinny_kernel
       if (c >= c1) break;
     }
   }
-  // the four waves' sums meet in LDS (a wave without a chunk brings zeros) and are added in wave order
-#pragma unroll
-  for (int f = 0; f < F; ++f)
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf) red[wave][(f * MF + mf) * 64 + lane] = acc[f][mf];
-  __syncthreads();
-  f32x4 own[IT::PER];
-  int om[IT::PER], on[IT::PER];                                // item j: row and first channel; row -1 = nothing
-#pragma unroll
-  for (int j = 0; j < IT::PER; ++j) {
-    const int idx = threadIdx.x + 256 * j;
-    own[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    om[j] = -1;
-    on[j] = 0;
-    if (idx < IT::NI) {
-      const int fm = idx >> 6, l = idx & 63;
-      const int m = 16 * (fm % MF) + (l & 15), n = nb0 + 16 * (fm / MF) + 4 * (l >> 4);
-      own[j] = ((red[0][idx] + red[1][idx]) + red[2][idx]) + red[3][idx];
-      if (m < p.M && n < p.N) {
-        om[j] = m;
-        on[j] = n;
-      }
-    }
-  }
-  if (KS > 1) {
-    const __amdgpu_buffer_rsrc_t wsr = sk_rsrc(p.ws);
-    const int MN = p.M * p.N;
-#pragma unroll
-    for (int j = 0; j < IT::PER; ++j)
-      if (om[j] >= 0)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, own[j]), wsr,
-                                               (ks * MN + om[j] * p.N + on[j]) * 4, 0, SK_CPOL_SC1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int old = __hip_atomic_fetch_add(p.counters + blockIdx.x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int last = old == KS - 1;
-      if (last) __hip_atomic_store(p.counters + blockIdx.x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      flag = last;
-    }
-    __syncthreads();
-    if (!flag) return;
-#pragma unroll
-    for (int j = 0; j < IT::PER; ++j) {
-      if (om[j] < 0) continue;
-      f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f};
-      for (int s = 0; s < KS; ++s) {
-        if (s == ks) sum += own[j];
-        else
-          sum += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                               wsr, (s * MN + om[j] * p.N + on[j]) * 4, 0, SK_CPOL_SC1));
-      }
-      own[j] = sum;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < IT::PER; ++j) {
-    if (om[j] < 0) continue;
-    const size_t o = (size_t)om[j] * p.N + on[j];
-    f32x4 v = own[j] + *(const f32x4*)(p.bias + on[j]);
-    if (p.res) v += sk_widen(p.res + o);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = act_relu(v[e], p.act);
-    sk_store(p.out + o, v);
-  }
+  sk_finish<T, F, MF>(acc, red, flag, p, nb0, wave, lane);
 }
 
 }  // namespace adapt

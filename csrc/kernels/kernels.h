@@ -111,6 +111,13 @@ hipError_t gemm_skinny_f32(const float* x, const float* w, const float* bias, co
 hipError_t gemm_skinny_bf16(const bf16* x, const bf16* w, const float* bias, const bf16* res, bf16* out, float* ws,
                             int* counters, int M, int N, int K, int Kpad, int Npad, int act, int F, int KS,
                             hipStream_t s);
+// The skinny GEMM on MXFP4 weights (gemm_skinny_mx.h): bf16 x / res / out, e2m1 codes [Npad][Kpad / 128][4][4] words
+// and e8m0 scales [Npad][Kpad / 128] dwords (ops/mx.py pack_mxfp4), Kpad a multiple of 128.  F in 1 / 2 / 4 / 8; KS,
+// ws and counters as above, KS at most gemm_skinny_mx_chunks (128 k each).  K and N multiples of 8.
+int gemm_skinny_mx_chunks(int Kpad);
+hipError_t gemm_skinny_mx(const bf16* x, const uint32_t* codes, const uint32_t* scales, const float* bias,
+                          const bf16* res, bf16* out, float* ws, int* counters, int M, int N, int K, int Kpad,
+                          int Npad, int act, int F, int KS, hipStream_t s);
 hipError_t softmax_rows(const float* x, float* y, int rows, int N, int ldx, hipStream_t s);
 hipError_t cast_bf16_f32(const bf16* x, float* y, size_t n, hipStream_t s);
 hipError_t pad(const bf16* x, bf16* y, int B, int H, int W, int C, int OH, int OW, int pad_t, int pad_l,

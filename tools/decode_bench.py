@@ -9,8 +9,11 @@ upper end, and a plan per length is not counted).  Prints one line per precision
 graphs alternately, round after round in one process, then prints each path's median with the spread of its
 rounds and the ratio between the paths.
 
+`--weight-quant mxfp4` adds, in bf16, every path once more on MXFP4 weights (`SliceExecutor(weight_quant=...)`,
+a path named `skinny+mxfp4`): another model, so its tokens differ; what compares is the time.
+
     python tools/decode_bench.py --model tinyllama_1_1b --batch 8 --prompt-tokens 128 --new-tokens 128 \
-        --gemm tiles,skinny
+        --gemm tiles,skinny [--weight-quant mxfp4]
 """
 import argparse
 import os
@@ -47,6 +50,7 @@ def main():
     ap.add_argument("--precisions", default="fp32,bf16")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--gemm", default="tiles", help="comma-separated decoder GEMM paths: tiles, skinny")
+    ap.add_argument("--weight-quant", default=None, choices=["mxfp4"], help="bf16: each path also on MXFP4 weights")
     a = ap.parse_args()
     B, P, N = a.batch, a.prompt_tokens, a.new_tokens
     print(torch.cuda.get_device_name(0), flush=True)
@@ -56,26 +60,41 @@ def main():
     vocab = int(g.layers[g.output_names[0]].attrs["units"])
     ids = np.random.default_rng(0).integers(0, vocab, (B, P + N))
     m = Model(g, w)
-    gemms = a.gemm.split(",")
     for precision in a.precisions.split(","):
+        # a path: the decoder's GEMM and the weights' quantisation, named as it is printed
+        paths = {gm: (gm, None) for gm in a.gemm.split(",")}
+        if a.weight_quant and precision == "bf16":
+            paths.update({f"{gm}+{a.weight_quant}": (gm, a.weight_quant) for gm in a.gemm.split(",")})
+        gemms = list(paths)
+
+        def generate(gm):
+            return m.generate(ids[:, :P], N, precision=precision, decode_gemm=paths[gm][0], weight_quant=paths[gm][1])
+
+        def pair(gm):
+            return next(v for k, v in m._executors.items()
+                        if k[0] == "generate" and k[-3:] == (precision, paths[gm][1], paths[gm][0]))
+
         toks, gen, steps, prefill = {}, {}, {}, {}
         for gm in gemms:
-            toks[gm] = m.generate(ids[:, :P], N, precision=precision, decode_gemm=gm)    # build, capture, warm up
+            toks[gm] = generate(gm)                                         # build, capture, warm up
             gen[gm], steps[gm] = [], []
         for _ in range(a.rounds):                                           # the paths alternate within a round
             for gm in gemms:
                 t0 = time.perf_counter()
-                m.generate(ids[:, :P], N, precision=precision, decode_gemm=gm)          # ends in a device synchronise
+                generate(gm)                                                # ends in a device synchronise
                 gen[gm].append((time.perf_counter() - t0) * 1e3)
-                ex, dec = next(v for k, v in m._executors.items() if k[0] == "generate" and k[-2:] == (precision, gm))
+                ex, dec = pair(gm)
                 ex.forward(0)                                               # pos = P again
                 steps[gm].append(events_ms(lambda: dec.forward(0), N))      # N replays: positions P .. P + N - 1
         for gm in gemms:
-            ex, dec = next(v for k, v in m._executors.items() if k[0] == "generate" and k[-2:] == (precision, gm))
+            ex, dec = pair(gm)
             prefill[gm] = sorted(events_ms(lambda: ex.forward(0), 3) for _ in range(a.rounds))[a.rounds // 2]
             if dec.skinny_steps:
                 print(f"{a.model} {precision} gemm={gm}: {len(dec.skinny_steps)} conv steps on the skinny GEMM, (F, KS) "
                       f"{sorted(set(dec._skinny.values()))}", flush=True)
+            if dec.mx_steps:
+                print(f"{a.model} {precision} gemm={gm}: {len(dec.mx_steps)} conv steps on the MXFP4 skinny GEMM, (F, KS) "
+                      f"{sorted(set(dec._mx.values()))}", flush=True)
         del ex, dec
         m._executors.clear()
         torch.cuda.empty_cache()

@@ -251,9 +251,10 @@ def cmd_generate(argv):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--decode-gemm", default=None, choices=["tiles", "skinny"],
                     help="GEMM path of the one-token step (default: ADAPT_DECODE_GEMM, else tiles)")
-    ap.add_argument("--weight-quant", default=None, choices=["mxfp4"],
+    ap.add_argument("--weight-quant", default=None, choices=["mxfp4", "mxfp4_only"],
                     help="quantise the projections and the MLP (bf16 only); with --decode-gemm skinny the step "
-                         "streams the 4-bit codes")
+                         "streams the 4-bit codes; mxfp4_only keeps no bf16 copy of them (0.53 bytes a weight): "
+                         "the prefill and every step run on the codes")
     a = ap.parse_args(argv)
     from .models.model import application
     m = application(a.model, seed=a.seed)

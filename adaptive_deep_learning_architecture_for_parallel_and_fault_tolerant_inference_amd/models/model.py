@@ -139,7 +139,8 @@ class Model:
         (default P + new_tokens) sizes the caches.  `decode_gemm` is `SliceExecutor.decoder`'s `gemm` ("tiles",
         "skinny"; None: ADAPT_DECODE_GEMM, default "tiles"), and each value keeps executors of its own.  `weight_quant` is
         `SliceExecutor`'s ("mxfp4", precision "bf16" only: the projections and the MLP quantised, the decode step
-        with decode_gemm="skinny" on the 4-bit codes), again with executors of its own.  No sampling; the CPU path has no decoding.  The prefill graph
+        with decode_gemm="skinny" on the 4-bit codes; "mxfp4_only": the same without a bf16 copy, the prefill and
+        every step on the codes), again with executors of its own.  No sampling; the CPU path has no decoding.  The prefill graph
         (P tokens) and the step graph (one token) are rebuilt by the zoo builder of `self.graph.name`, so the model
         must be one that `models.zoo.build_model` knows by name; any other (a Keras-JSON model) is refused."""
         import torch

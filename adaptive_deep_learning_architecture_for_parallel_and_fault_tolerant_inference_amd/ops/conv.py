@@ -149,16 +149,20 @@ class MxWeights(NamedTuple):
     scales: torch.Tensor     # int32 [Npad][Kpad / 128]: four e8m0 bytes a dword
 
 
-def pack_conv_mxfp4(kernel_hwio: np.ndarray, bias: np.ndarray, device) -> PackedConv:
+def pack_conv_mxfp4(kernel_hwio: np.ndarray, bias: np.ndarray, device, keep_bf16: bool = True) -> PackedConv:
     """A 1x1 / stride 1 conv with its kernel quantised to MXFP4 along the input channels: `w` is `pack_conv` of the
     dequantised kernel (exact in bf16, so every bf16 path computes the quantised model), `mx` the codes and scales
-    the decode step streams instead (`mx_forward`)."""
+    the decode step streams instead (`mx_forward`).  keep_bf16=False keeps the codes alone: `w` is an empty bf16
+    [0][Kpad] tensor, and only `mx_forward` / `mx_tile_forward` take the conv (0.53 bytes a weight, not 2.53)."""
     kh, kw, cin, cout = kernel_hwio.shape
     if (kh, kw) != (1, 1):
         raise ValueError(f"MXFP4 weights are for 1x1 convs, got a {kh}x{kw} kernel")
     codes, exps = mx_format.quantize_mxfp4(np.asarray(kernel_hwio, np.float32).reshape(cin, cout).T)
     deq = mx_format.dequantize_mxfp4(codes, exps)
-    pc = pack_conv(np.ascontiguousarray(deq.T).reshape(1, 1, cin, cout), bias, 1, ((0, 0), (0, 0)), device)
+    pc = pack_conv(np.ascontiguousarray(deq.T).reshape(1, 1, cin, cout), bias, 1, ((0, 0), (0, 0)),
+                   device if keep_bf16 else "cpu")
+    if not keep_bf16:
+        pc.w, pc.bias = pc.w[:0].to(device), pc.bias.to(device)
     words, scales = mx_format.pack_mxfp4(codes, exps)
     pc.mx = MxWeights(torch.from_numpy(words.view(np.int32)).to(device),
                       torch.from_numpy(scales.view(np.int32)).to(device))
@@ -278,6 +282,9 @@ def conv_forward(x: torch.Tensor, pc: PackedConv, out: torch.Tensor, residual: O
         B, H, W, C = x.shape
     if C != pc.cin:
         raise ValueError(f"conv expects {pc.cin} input channels, got {C}")
+    if pc.w.shape[0] == 0:
+        raise ValueError("this conv keeps its MXFP4 codes alone (pack_conv_mxfp4(keep_bf16=False)): no bf16 weights "
+                         "to run a tile config on; mx_forward / mx_tile_forward take it")
     if int(relu) not in (0, 1, 2) or int(relu2) not in (0, 1, 2):
         raise ValueError("conv epilogue activation must be 0 (none), 1 (ReLU) or 2 (ReLU6)")
     if x.dtype != torch.bfloat16 or not x.is_contiguous():
@@ -1185,6 +1192,9 @@ def skinny_forward(x: torch.Tensor, pc: "PackedConv", out: torch.Tensor, residua
     M = x.numel() // max(C, 1)
     if C != pc.cin:
         raise ValueError(f"conv expects {pc.cin} input channels, got {C}")
+    if pc.w.shape[0] == 0:
+        raise ValueError("skinny GEMM: this conv keeps its MXFP4 codes alone (pack_conv_mxfp4(keep_bf16=False)), no "
+                         "weights to stream; mx_forward / mx_tile_forward take it")
     if not skinny_supported(pc, M):
         raise ValueError(f"skinny GEMM does not take this conv ({pc.kh}x{pc.kw}/s{pc.stride}, {pc.cin} -> {pc.cout} "
                          f"channels, n_split {pc.n_split}) at {M} rows: 1x1 / stride 1, one output, 1 <= M <= "
@@ -1304,7 +1314,98 @@ def mx_forward(x: torch.Tensor, pc: "PackedConv", out: torch.Tensor, residual: O
     return out
 
 
-RR3_CFGS = {71: 1, 72: 2}                     # 3x3 with the filter resident in VGPRs (conv3x3_rr.hip) -> K groups
+# ------------------------------------------------- tile GEMM on MXFP4 weights (the prefill, any M)
+# csrc/kernels/gemm_tile_mx.h: the same codes and scales, x through LDS, blocks of 16 MT rows x 64 F channels, K split
+# over gridDim.z in whole chunks.  With it a quantised conv needs no bf16 copy (pack_conv_mxfp4(keep_bf16=False)).
+MX_TILES = ((4, 8), (2, 4), (1, 4))      # (F, MT), gemm_tile_mx.hip's instantiations, the widest first
+MX_TILE_MAX_KS = 8
+# the least chunks of a split per tile (0: the tile is never split), from the sweep `mx_tile_plan` follows
+MX_TILE_SPLIT_CHUNKS = {(4, 8): 0, (2, 4): 16, (1, 4): 4}
+
+
+def mx_tile_supported(pc: "PackedConv", M: int) -> bool:
+    """A conv that carries MXFP4 codes, 1x1 / stride 1 / no padding / one output, K and N multiples of 8, M >= 1, and
+    every index of x, out and the codes within 32 bits."""
+    if pc.mx is None or pc.w.dtype != torch.bfloat16 or M < 1:
+        return False
+    return ((pc.kh, pc.kw, pc.stride, pc.pad_t, pc.pad_l, pc.pad_b, pc.pad_r) == (1, 1, 1, 0, 0, 0, 0)
+            and not pc.n_split and pc.cin % 8 == 0 and pc.cout % 8 == 0
+            and max(M * pc.cin, M * pc.cout, pc.mx.codes.numel()) < 2 ** 31)
+
+
+def mx_tile_plan(M: int, N: int, K: int):
+    """(F, MT, KS), following tools/mx_tile_bench.py --sweep at M = 64 .. 4096 on the tinyllama_1_1b and llama2_7b
+    GEMMs (BASELINE.md "Round 26").  The widest tile that gives 1.25 blocks per CU (at exactly one per CU the next
+    narrower tile was 10 to 20 % faster), else the narrowest.  Then K is split towards four blocks per CU, in at
+    most MX_TILE_MAX_KS splits of at least MX_TILE_SPLIT_CHUNKS chunks: the (1, 4) tile gained from every split
+    the sweep tried, the (2, 4) tile from two splits at K >= 4096 only, the (4, 8) tile from none (its blocks
+    already hold 128 accumulator registers' worth of partials to write and read back)."""
+    for F, MT in MX_TILES:
+        tiles = math.ceil(M / (16 * MT)) * math.ceil(N / (64 * F))
+        if 4 * tiles >= 5 * NUM_CUS:
+            break
+    least = MX_TILE_SPLIT_CHUNKS[(F, MT)]
+    if not least or M * N * 4 >= 2 ** 31:
+        return F, MT, 1
+    return F, MT, max(1, min(MX_TILE_MAX_KS, mx_chunks(K) // least, 4 * NUM_CUS // tiles))
+
+
+def mx_tile_scratch(M: int, N: int, K: int, F: int, MT: int, KS: int):
+    """(fp32 workspace elements, int32 arrival counters) of a launch, exact: KS partial outputs and one counter per
+    output tile."""
+    return (KS * M * N if KS > 1 else 0), (math.ceil(M / (16 * MT)) * math.ceil(N / (64 * F)) if KS > 1 else 0)
+
+
+def mx_tile_forward(x: torch.Tensor, pc: "PackedConv", out: torch.Tensor, residual: Optional[torch.Tensor] = None,
+                    relu: int = 0, F: Optional[int] = None, MT: Optional[int] = None, ksplit: Optional[int] = None,
+                    workspace: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None,
+                    stream=None) -> torch.Tensor:
+    """out [M, N] = act(x [M, K] . deq(W)^T + bias (+ residual)) on the MXFP4 codes of `pc`, bf16 tensors, any M >= 1
+    (x: [M, K] or a [B, H, W, K] map of M pixels); `pc.w` is not read and may have no rows.  `F` / `MT` / `ksplit`
+    default to `mx_tile_plan`; `mx_tile_scratch` gives the `workspace` floats (allocated when absent) and the
+    `counters` (int32 zeros; a launch leaves them zero) of a ksplit > 1."""
+    C = x.shape[-1]
+    M = x.numel() // max(C, 1)
+    if C != pc.cin:
+        raise ValueError(f"conv expects {pc.cin} input channels, got {C}")
+    if pc.mx is None:
+        raise ValueError("MXFP4 tile GEMM: this PackedConv carries no MXFP4 codes (pack_conv_mxfp4)")
+    if not mx_tile_supported(pc, M):
+        raise ValueError(f"MXFP4 tile GEMM does not take this conv ({pc.kh}x{pc.kw}/s{pc.stride}, {pc.cin} -> "
+                         f"{pc.cout} channels, n_split {pc.n_split}) at {M} rows: 1x1 / stride 1, one output, "
+                         f"channels in multiples of 8, 32-bit indices")
+    N, K = pc.cout, pc.cin
+    for t, nm in ((x, "x"), (out, "out"), (residual, "residual")):
+        if t is not None and (t.dtype != torch.bfloat16 or not t.is_contiguous()):
+            raise ValueError(f"MXFP4 tile GEMM: {nm} must be contiguous bf16")
+    if out.numel() != M * N:
+        raise ValueError(f"conv output buffer has {out.numel()} elements, need {M * N}")
+    if residual is not None and residual.numel() != M * N:
+        raise ValueError("residual must have the output's shape")
+    if int(relu) not in (0, 1, 2):
+        raise ValueError("conv epilogue activation must be 0 (none), 1 (ReLU) or 2 (ReLU6)")
+    pF, pMT, pKS = mx_tile_plan(M, N, K)
+    if (F is None) != (MT is None):
+        raise ValueError("MXFP4 tile GEMM: F and MT name one tile, give both or neither")
+    if F is None:
+        F, MT = pF, pMT
+    F, MT, KS = int(F), int(MT), int(ksplit or (pKS if (F, MT) == (pF, pMT) else 1))
+    if (F, MT) not in MX_TILES:
+        raise ValueError(f"MXFP4 tile GEMM: (F, MT) must be one of {MX_TILES}, got {(F, MT)}")
+    Npad, nch = pc.mx.scales.shape
+    if not 1 <= KS <= nch:
+        raise ValueError(f"MXFP4 tile GEMM: ksplit {KS} outside 1 .. {nch}, the chunks of K = {K}")
+    if KS > 1 and M * N * 4 >= 2 ** 31:
+        raise ValueError(f"MXFP4 tile GEMM: a ksplit > 1 needs M N 4 < 2^31 bytes a partial, got {M} x {N}")
+    if Npad % 16 or Npad < N or nch != mx_chunks(K) or pc.mx.codes.numel() != Npad * nch * 16:
+        raise ValueError("MXFP4 codes not in the kernel's layout for this conv (ops.mx.pack_mxfp4)")
+    ws_ptr, ctr_ptr = _scratch_ptrs(mx_tile_scratch(M, N, K, F, MT, KS), workspace, counters, x.device)
+    kernels().gemm_tile_mx(ptr(x), ptr(pc.mx.codes), ptr(pc.mx.scales), ptr(pc.bias), ptr(residual), ptr(out),
+                           ws_ptr, ctr_ptr, M, N, K, nch * MX_KC, Npad, int(relu), F, MT, KS, stream_handle(stream))
+    return out
+
+
+RR3_CFGS = {71: 1, 72: 2}                    # 3x3 with the filter resident in VGPRs (conv3x3_rr.hip) -> K groups
 
 
 def rr3_supported(pc: "PackedConv") -> bool:

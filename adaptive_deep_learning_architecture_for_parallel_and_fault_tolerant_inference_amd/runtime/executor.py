@@ -123,7 +123,11 @@ class SliceExecutor:
         path then computes the model with the dequantised weights: the tile configs on
         their bf16 copy (exact), and a `decoder(gemm="skinny")` on the 4-bit codes
         (csrc/kernels/gemm_skinny_mx.h; `mx_steps`).  The codes come on top of the bf16
-        copy: device memory grows, the bytes a decode step streams shrink."""
+        copy: device memory grows, the bytes a decode step streams shrink.
+        "mxfp4_only" quantises the same steps and keeps the codes alone, 0.53 bytes a
+        weight instead of 2.53: such a step runs `mx_forward` up to 32 rows, whatever the
+        decoder's `gemm`, and the tile GEMM on the codes above (csrc/kernels/gemm_tile_mx.h;
+        `mx_tile_steps`); no tile config and no tuner sees it."""
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"precision must be bf16 or fp32, got {precision!r}")
         if weight_quant not in self.WEIGHT_QUANT:
@@ -165,6 +169,7 @@ class SliceExecutor:
         self.decode_gemm = _decode_gemm               # a decoder's GEMM path (`decoder`): "tiles" or "skinny"
         self._skinny: Dict[int, Tuple[int, int]] = {}  # conv step -> (F, KS) of its skinny_forward launch
         self._mx: Dict[int, Tuple[int, int]] = {}      # conv step -> (F, KS) of its mx_forward launch
+        self._mx_tile: Dict[int, Tuple[int, int, int]] = {}   # conv step -> (F, MT, KS) of its mx_tile_forward launch
         self._kv: Optional[Dict[str, Tuple[torch.Tensor, torch.Tensor]]] = None     # layer -> (K, V) caches
         if self.kv_cache is not None:
             self._plan_kv(weights)
@@ -249,9 +254,9 @@ class SliceExecutor:
                     kf, bf = np.concatenate([kf, k2], axis=-1), np.concatenate([bf, b2])
                 pc = conv_ops.pack_conv(kf, bf, p["stride"], p["pads"], dev, cin_pad=cin_pad)
                 pc.n_split = n_split
-                if (self.weight_quant == "mxfp4" and not st.p.get("out2") and st.out not in self.outputs
+                if (self.weight_quant is not None and not st.p.get("out2") and st.out not in self.outputs
                         and cin_pad == kf.shape[2] and conv_ops.skinny_supported(pc, 1)):
-                    pc = conv_ops.pack_conv_mxfp4(kf, bf, dev)
+                    pc = conv_ops.pack_conv_mxfp4(kf, bf, dev, keep_bf16=self.weight_quant == "mxfp4")
                 self.packed[i] = pc
             elif st.kind == "bottleneck":
                 p = st.p
@@ -573,7 +578,7 @@ class SliceExecutor:
                                   kv_heads=hkv, workspace=self._dec_ws, stream=stream)
 
     DECODE_GEMM = ("tiles", "skinny")
-    WEIGHT_QUANT = (None, "mxfp4")
+    WEIGHT_QUANT = (None, "mxfp4", "mxfp4_only")
 
     @property
     def skinny_steps(self) -> List[int]:
@@ -586,6 +591,12 @@ class SliceExecutor:
         MXFP4 skinny GEMM."""
         return sorted(self._mx)
 
+    @property
+    def mx_tile_steps(self) -> List[int]:
+        """Indices of the quantised conv steps without a bf16 copy (weight_quant="mxfp4_only") that run the MXFP4
+        tile GEMM: every one of them above 32 rows."""
+        return sorted(self._mx_tile)
+
     def decoder(self, gemm: Optional[str] = None) -> "SliceExecutor":
         """The step executor behind this prefill executor (`kv_cache` set): the same model at one token per
         sequence, on this executor's prepared weights, caches and positions.  A run appends the token's keys and
@@ -597,7 +608,8 @@ class SliceExecutor:
         transformer, runs `conv_ops.skinny_forward` on the same packed weights; `skinny_steps` lists them and the
         rest keep their tile config); None reads ADAPT_DECODE_GEMM, default "tiles".  On an executor with
         `weight_quant`, "skinny" routes each quantised step `conv_ops.mx_supported` and `mx_preferred` take to
-        `conv_ops.mx_forward` on the 4-bit codes (`mx_steps`), and "tiles" runs the dequantised bf16 weights."""
+        `conv_ops.mx_forward` on the 4-bit codes (`mx_steps`), and "tiles" runs the dequantised bf16 weights.  With
+        weight_quant="mxfp4_only" there are no such weights: every quantised step is in `mx_steps` under both."""
         from ..models.zoo import build_model
         if gemm is None:
             gemm = os.environ.get("ADAPT_DECODE_GEMM", "tiles")
@@ -851,6 +863,10 @@ class SliceExecutor:
             B, _, _, _, OH, OW, pc = self._conv_geom(i)
             nws, nctr = conv_ops.mx_scratch(B * OH * OW, pc.cout, pc.cin, F, ks)
             need, ctr = max(need, nws), max(ctr, nctr)
+        for i, (F, MT, ks) in self._mx_tile.items():
+            B, _, _, _, OH, OW, pc = self._conv_geom(i)
+            nws, nctr = conv_ops.mx_tile_scratch(B * OH * OW, pc.cout, pc.cin, F, MT, ks)
+            need, ctr = max(need, nws), max(ctr, nctr)
         if need and (self._ws is None or self._ws.numel() < need):
             self._ws = torch.empty(need, dtype=torch.float32, device=self.device)
             if self._side:                     # side-stream convs must not share scratch with the main stream
@@ -868,6 +884,18 @@ class SliceExecutor:
             if st.kind not in ("conv", "dense") or i in self._dense_part:    # small-M heads: head.hip
                 continue
             B, H, W, C, OH, OW, pc = self._conv_geom(i)
+            if getattr(pc, "mx", None) is not None and pc.w.shape[0] == 0:
+                # the codes alone (weight_quant="mxfp4_only"): no tile config; the skinny kernel up to its 32 rows,
+                # the tile GEMM on the codes above
+                M = B * OH * OW
+                if not (conv_ops.mx_tile_supported(pc, M) and self.bufs(0)[st.ins[0]].dtype
+                        == self.bufs(0)[st.out].dtype == torch.bfloat16):
+                    raise NotImplementedError(f"conv {st.out}: no MXFP4 kernel takes this step at {M} rows")
+                if conv_ops.mx_supported(pc, M):
+                    self._mx[i] = conv_ops.mx_plan(M, pc.cout, pc.cin)
+                else:
+                    self._mx_tile[i] = conv_ops.mx_tile_plan(M, pc.cout, pc.cin)
+                continue
             if self.fp32:
                 key = "f32|" + conv_key(B, H, W, C, pc)
                 if key not in table and pc.out_lattice > 1:     # no entry of its own: the full conv's (legal: a
@@ -891,6 +919,8 @@ class SliceExecutor:
                 # the model's head (a Dense over the vocabulary at the output) keeps its tile config: the kernel is
                 # unmeasured at that N
                 if st.kind != "conv" or st.p.get("out2") or st.out in self.outputs:
+                    continue
+                if i in self._mx or i in self._mx_tile:       # the codes alone: routed above, whatever `gemm`
                     continue
                 B, _, _, _, OH, OW, pc = self._conv_geom(i)
                 bufs = self.bufs(0)                    # input and output in the weights' type (not an fp32 logits row)
@@ -939,7 +969,7 @@ class SliceExecutor:
         ranked: Dict[str, List[Tuple[float, int, int]]] = {}
         prev = dict(load_tuning())              # the table in force: a known-good starting point
         for i, st in enumerate(self.steps):
-            if st.kind not in ("conv", "dense") or i in self._dense_part:
+            if st.kind not in ("conv", "dense") or i in self._dense_part or i not in self.cfg:
                 continue
             B, H, W, C, OH, OW, pc = self._conv_geom(i)
             M, N = B * OH * OW, pc.cout
@@ -1025,7 +1055,7 @@ class SliceExecutor:
                          verbose: bool = False, prefix: str = "") -> None:
         steps_of: Dict[str, List[int]] = {}
         for i, st in enumerate(self.steps):
-            if st.kind in ("conv", "dense") and i not in self._dense_part:
+            if st.kind in ("conv", "dense") and i not in self._dense_part and i in self.cfg:
                 B, H, W, C, OH, OW, pc = self._conv_geom(i)
                 steps_of.setdefault(prefix + conv_key(B, H, W, C, pc), []).append(i)
         # start from the previous table where it is still a valid candidate, so a
@@ -1111,6 +1141,11 @@ class SliceExecutor:
                 conv_ops.mx_forward(b[st.ins[0]], self.packed[i], b[st.out],
                                     residual=b[st.ins[1]] if len(st.ins) > 1 else None, relu=st.p["relu"], F=F,
                                     ksplit=ks, workspace=ws, counters=ctr, stream=stream)
+            elif k == "conv" and i in self._mx_tile:
+                F, MT, ks = self._mx_tile[i]
+                conv_ops.mx_tile_forward(b[st.ins[0]], self.packed[i], b[st.out],
+                                         residual=b[st.ins[1]] if len(st.ins) > 1 else None, relu=st.p["relu"], F=F,
+                                         MT=MT, ksplit=ks, workspace=ws, counters=ctr, stream=stream)
             elif k == "conv" and i in self._skinny:
                 F, ks = self._skinny[i]
                 conv_ops.skinny_forward(b[st.ins[0]], self.packed[i], b[st.out],
@@ -1400,6 +1435,8 @@ class SliceExecutor:
                 extra = f" skinny={self._skinny[i]}"
             if i in self._mx:                    # ... or its MXFP4 skinny GEMM step
                 extra = f" mx={self._mx[i]}"
+            if i in self._mx_tile:               # ... or the MXFP4 tile GEMM of a step without a bf16 copy
+                extra = f" mxt={self._mx_tile[i]}"
             if st.p.get("subsample"):            # produced on the lattice its stride-s readers sample
                 extra += f" subsample={st.p['subsample']} -> {st.p['out_hw'][0]}x{st.p['out_hw'][1]}"
             lines.append(f"{i:3d} {st.kind:8s} {st.out:28s} <- {st.ins}{extra}")

@@ -271,6 +271,13 @@ PYBIND11_MODULE(_C, m) {
                                 P<int>(counters), M, N, K, Kpad, Npad, act, F, KS, S(s)),
           "gemm_skinny_mx");
   });
+  m.def("gemm_tile_mx", [](u64 x, u64 codes, u64 scales, u64 bias, u64 res, u64 out, u64 ws, u64 counters, int M,
+                           int N, int K, int Kpad, int Npad, int act, int F, int MT, int KS, u64 s) {
+    check(adapt::gemm_tile_mx(P<const bf16>(x), P<const uint32_t>(codes), P<const uint32_t>(scales),
+                              P<const float>(bias), P<const bf16>(res), P<bf16>(out), P<float>(ws), P<int>(counters),
+                              M, N, K, Kpad, Npad, act, F, MT, KS, S(s)),
+          "gemm_tile_mx");
+  });
   m.def("gap", [](u64 x, u64 y, u64 y32, int B, int HW, int C, u64 s) {
     check(adapt::gap(P<const bf16>(x), P<bf16>(y), P<float>(y32), B, HW, C, S(s)), "gap");
   });

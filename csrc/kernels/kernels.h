@@ -118,6 +118,12 @@ int gemm_skinny_mx_chunks(int Kpad);
 hipError_t gemm_skinny_mx(const bf16* x, const uint32_t* codes, const uint32_t* scales, const float* bias,
                           const bf16* res, bf16* out, float* ws, int* counters, int M, int N, int K, int Kpad,
                           int Npad, int act, int F, int KS, hipStream_t s);
+// The tile GEMM on the same codes and scales (gemm_tile_mx.h) for any M >= 1: blocks of 16 MT rows x 64 F channels,
+// (F, MT) one of (4, 8), (2, 4), (1, 4); KS splits of K in chunks of 128 k over gridDim.z; KS > 1 needs ws (fp32
+// [KS][M][N], M N 4 < 2^31) and one zeroed int32 counter per output tile, which the launch leaves zero.
+hipError_t gemm_tile_mx(const bf16* x, const uint32_t* codes, const uint32_t* scales, const float* bias,
+                        const bf16* res, bf16* out, float* ws, int* counters, int M, int N, int K, int Kpad, int Npad,
+                        int act, int F, int MT, int KS, hipStream_t s);
 hipError_t softmax_rows(const float* x, float* y, int rows, int N, int ldx, hipStream_t s);
 hipError_t cast_bf16_f32(const bf16* x, float* y, size_t n, hipStream_t s);
 hipError_t pad(const bf16* x, bf16* y, int B, int H, int W, int C, int OH, int OW, int pad_t, int pad_l,

@@ -10,10 +10,12 @@ graphs alternately, round after round in one process, then prints each path's me
 rounds and the ratio between the paths.
 
 `--weight-quant mxfp4` adds, in bf16, every path once more on MXFP4 weights (`SliceExecutor(weight_quant=...)`,
-a path named `skinny+mxfp4`): another model, so its tokens differ; what compares is the time.
+a path named `skinny+mxfp4`): another model, so its tokens differ; what compares is the time.  The value may be a
+comma-separated list: `mxfp4,mxfp4_only` times the codes next to a bf16 copy and the codes alone (the prefill on
+csrc/kernels/gemm_tile_mx.h), round by round in one process, and prints the device memory of each path's executors.
 
     python tools/decode_bench.py --model tinyllama_1_1b --batch 8 --prompt-tokens 128 --new-tokens 128 \
-        --gemm tiles,skinny [--weight-quant mxfp4]
+        --gemm tiles,skinny [--weight-quant mxfp4,mxfp4_only]
 """
 import argparse
 import os
@@ -50,7 +52,8 @@ def main():
     ap.add_argument("--precisions", default="fp32,bf16")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--gemm", default="tiles", help="comma-separated decoder GEMM paths: tiles, skinny")
-    ap.add_argument("--weight-quant", default=None, choices=["mxfp4"], help="bf16: each path also on MXFP4 weights")
+    ap.add_argument("--weight-quant", default=None,
+                    help="bf16: each path also on MXFP4 weights; comma-separated: mxfp4, mxfp4_only")
     a = ap.parse_args()
     B, P, N = a.batch, a.prompt_tokens, a.new_tokens
     print(torch.cuda.get_device_name(0), flush=True)
@@ -64,7 +67,7 @@ def main():
         # a path: the decoder's GEMM and the weights' quantisation, named as it is printed
         paths = {gm: (gm, None) for gm in a.gemm.split(",")}
         if a.weight_quant and precision == "bf16":
-            paths.update({f"{gm}+{a.weight_quant}": (gm, a.weight_quant) for gm in a.gemm.split(",")})
+            paths.update({f"{gm}+{wq}": (gm, wq) for wq in a.weight_quant.split(",") for gm in a.gemm.split(",")})
         gemms = list(paths)
 
         def generate(gm):
@@ -74,10 +77,14 @@ def main():
             return next(v for k, v in m._executors.items()
                         if k[0] == "generate" and k[-3:] == (precision, paths[gm][1], paths[gm][0]))
 
-        toks, gen, steps, prefill = {}, {}, {}, {}
+        toks, gen, steps, prefill, pre = {}, {}, {}, {}, {}
         for gm in gemms:
+            torch.cuda.synchronize()
+            before = torch.cuda.memory_allocated()
             toks[gm] = generate(gm)                                         # build, capture, warm up
-            gen[gm], steps[gm] = [], []
+            gen[gm], steps[gm], pre[gm] = [], [], []
+            print(f"{a.model} {precision} gemm={gm}: {(torch.cuda.memory_allocated() - before) / 2 ** 20:.0f} MiB of "
+                  f"device memory for its executors (weights, caches, activations)", flush=True)
         for _ in range(a.rounds):                                           # the paths alternate within a round
             for gm in gemms:
                 t0 = time.perf_counter()
@@ -86,9 +93,13 @@ def main():
                 ex, dec = pair(gm)
                 ex.forward(0)                                               # pos = P again
                 steps[gm].append(events_ms(lambda: dec.forward(0), N))      # N replays: positions P .. P + N - 1
+                pre[gm].append(events_ms(lambda: ex.forward(0), 3))
         for gm in gemms:
             ex, dec = pair(gm)
-            prefill[gm] = sorted(events_ms(lambda: ex.forward(0), 3) for _ in range(a.rounds))[a.rounds // 2]
+            prefill[gm] = sorted(pre[gm])[a.rounds // 2]
+            if ex.mx_tile_steps:
+                print(f"{a.model} {precision} gemm={gm}: prefill with {len(ex.mx_tile_steps)} conv steps on the MXFP4 "
+                      f"tile GEMM, (F, MT, KS) {sorted(set(ex._mx_tile.values()))}", flush=True)
             if dec.skinny_steps:
                 print(f"{a.model} {precision} gemm={gm}: {len(dec.skinny_steps)} conv steps on the skinny GEMM, (F, KS) "
                       f"{sorted(set(dec._skinny.values()))}", flush=True)
@@ -109,7 +120,8 @@ def main():
         for gm in gemms:
             med, step = sorted(gen[gm])[a.rounds // 2], sorted(steps[gm])[a.rounds // 2]
             print(f"{a.model} {precision} gemm={gm} B{B} prompt {P} + {N} new: generate {med:.1f} ms end to end = "
-                  f"{med / N:.3f} ms per token ({B * N / med * 1e3:.0f} tokens/s; prefill {prefill[gm]:.2f} ms, step graph "
+                  f"{med / N:.3f} ms per token ({B * N / med * 1e3:.0f} tokens/s; prefill {prefill[gm]:.2f} ms (spread "
+                  f"{max(pre[gm]) - min(pre[gm]):.2f}), step graph "
                   f"alone {step:.3f} ms per token, rounds {' '.join(f'{v:.3f}' for v in steps[gm])}, spread "
                   f"{max(steps[gm]) - min(steps[gm]):.3f}) | full forward pass at {P + N} tokens {fwd:.2f} ms per token "
                   f"({fwd / (med / N):.1f}x generate per token, {fwd / step:.1f}x the step graph) | first tokens "
